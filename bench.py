@@ -37,6 +37,8 @@ PAIR_SAMPLE_EVERY = 5          # the density+acceleration pair is timed (two HIP
                                # stream time each) on every 5th step of the timed region
 DENSITY_FORCE_BYTES = 64       # algorithmic bytes per particle of the density+force pass
                                # (density 20 B + force 44 B)
+DUMP_SAMPLE = 1 << 19          # --dump-outputs: particles written (52 bytes each: 27 MB in all)
+DUMP_SEED = 20240607           # ... chosen by this fixed seed, the same in every run of a given size
 
 
 def parse_args():
@@ -78,13 +80,24 @@ def parse_args():
                     help="N = 1: skip the 40 untimed steps on a scratch context right before the "
                          "warm-up (after ANY idle period of 50 ms or more - an upload is one - "
                          "the device needs ~15 steps to settle its clocks: tools/idle_ramp.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: after the timed steps, write what the last timed step computed "
+                         "(positions, velocities, densities, accelerations, neighbour counts of a "
+                         "fixed seeded sample of 524 288 particles - all of them in smaller runs - and "
+                         "the step's energies) as "
+                         "DIR/<name>.npy, so that two builds can be compared output for output")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch rehearsal: start the ranks, form the process group, count them, "
                          "print {\"dry_run\": true, \"ranks\": N}; no GPU work (checks a node's "
                          "launch shape, and runs in the CPU test suite)")
     ap.add_argument("--preflight-child", metavar="STORE", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--preflight-kind", choices=("native", "torch"), default="torch", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs is implemented for --gpus 1")
+    return args
 
 
 def self_launch(args):
@@ -450,6 +463,32 @@ def timed_steps(sph, S, torch, warmup, steps):
     return dt, pair[2] / covered, covered
 
 
+def last_step_outputs(sph, n):
+    """What a caller of the timed path receives after its last step (SPH.getParticles(), energy()),
+    for a fixed seeded sample of DUMP_SAMPLE particles (all of them when n is no larger), in the
+    particles' upload order; float32 as computed, counts and indices as exact floats."""
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    part = sph.getParticles()
+    ke, pe = sph.energy()
+    return {"particle_index": idx.astype(np.float64),
+            "position": part.mPosition.reshape(-1, 3)[idx].astype(np.float32),
+            "velocity": part.mVelocity.reshape(-1, 3)[idx].astype(np.float32),
+            "density": part.mDensity[idx].astype(np.float32),
+            "acceleration": part.mAcceleration.reshape(-1, 3)[idx].astype(np.float32),
+            "neighbor_count": part.mNeighborCount[idx].astype(np.float32),
+            "energy": np.array([ke, pe], np.float64)}
+
+
+def dump_outputs(outputs, directory):
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(outputs)
+
+
 def run_single(args, S, scenes, torch, local_rank):
     """N = 1: one context holds the whole grid."""
     n = args.particles
@@ -470,6 +509,8 @@ def run_single(args, S, scenes, torch, local_rank):
         heater.run(PREHEAT_STEPS)
         heater.synchronize()
     dt, pair_ms, covered = timed_steps(sph, S, torch, args.warmup, args.steps)
+    # (read back before anything else steps this context: the state of the last timed step)
+    outputs = last_step_outputs(sph, n) if args.dump_outputs else None
     totals = phase_split(sph, S, lambda: sph.step(), sph.synchronize, sph.setTiming, sph.phaseTotals)
     totals["pair_ms"] = pair_ms
     totals["tiles"] = tile_summary(sph.tileStats())
@@ -490,7 +531,7 @@ def run_single(args, S, scenes, torch, local_rank):
     sph.close()
     if heater is not None:
         heater.close()
-    return p, dt, totals, covered, n, nb_mean, "1 GPU", other, parity
+    return p, dt, totals, covered, n, nb_mean, "1 GPU", other, parity, outputs
 
 
 def arithmetic_parity(sph, S, mass):
@@ -752,6 +793,7 @@ def main():
     strong_scaling = None
     other_arith = None
     parity = None
+    dumped = None
     fast = args.arithmetic == "fast"
     if world > 1:
         # RCCL gets a group of its own that only torch's halo exchange uses (the native loop has its
@@ -807,8 +849,14 @@ def main():
     else:
         n = args.particles or C3_PARTICLES
         args.particles = n
-        p, dt, totals, covered, n_rank, nb_mean, par, other_arith, parity = run_single(args, S, scenes, torch,
-                                                                                       local_rank)
+        p, dt, totals, covered, n_rank, nb_mean, par, other_arith, parity, outputs = run_single(
+            args, S, scenes, torch, local_rank)
+        if outputs is not None:
+            dumped = {"dir": args.dump_outputs, "files": dump_outputs(outputs, args.dump_outputs),
+                      "particles": int(outputs["particle_index"].size),
+                      "step": args.warmup + args.steps,
+                      "note": "state after the last timed step (step %d of the timed context), "
+                              "sample seed %d" % (args.warmup + args.steps, DUMP_SEED)}
         box, other, ranks = (1.0, 1.0, 1.0), None, 1
 
     if rank == 0:
@@ -904,6 +952,8 @@ def main():
             line["value_%s_arithmetic" % other_arith["arithmetic"]] = other_arith["value"]
         if parity is not None:
             line["parity"] = parity
+        if dumped is not None:
+            line["outputs_dumped"] = dumped
         if not args.no_preheat:
             line["config"]["preheat"] = (
                 "%d untimed steps of the same workload %s right before the warm-up (device clocks settle ~15 "

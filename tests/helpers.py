@@ -1,8 +1,12 @@
 """Shared helpers for the parity tests."""
 import ctypes as C
 import hashlib
+import json
+import os
 
 import numpy as np
+
+PINS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_pins.json")
 
 
 def to_oracle_params(p):
@@ -25,6 +29,47 @@ def to_product_params(o):
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def pin_sha(a):
+    """sha() with every NaN written as the one quiet NaN: what np.array_equal(..., equal_nan=True)
+    treats as equal hashes equal"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f" and np.isnan(a).any():
+        a = np.where(np.isnan(a), np.array(np.nan, a.dtype), a)
+    return sha(a)
+
+
+def _pin(v):
+    if isinstance(v, np.ndarray):
+        return pin_sha(v)
+    if isinstance(v, (tuple, list)):
+        return [float(x) for x in v]
+    return float(v)
+
+
+def reference_pins(case, run):
+    """What the reference's own compiled sph.cpp computes for one test's inputs: pin_sha() of every
+    array, the exact value of every number.  `run(reference)` drives the live library
+    (oracle/_ref/libsphref.so) and returns {name: array, number or sequence of numbers}.  Where that
+    library can be loaded, its answers are returned and must equal the pins stored for `case` in
+    tests/golden/reference_pins.json; elsewhere the stored pins stand in for it.  With
+    SPH_RECORD_REFERENCE_PINS=1 the live answers are written to that file instead of checked."""
+    from oracle.oracle import Reference, reference_available
+    with open(PINS_PATH) as f:
+        stored = json.load(f)
+    if not reference_available():
+        assert case in stored, "no pins stored for " + case
+        return stored[case]
+    got = {name: _pin(v) for name, v in run(Reference()).items()}
+    if os.environ.get("SPH_RECORD_REFERENCE_PINS") == "1":
+        stored[case] = got
+        with open(PINS_PATH, "w") as f:
+            json.dump(stored, f, indent=1, sort_keys=True)
+            f.write("\n")
+    else:
+        assert stored.get(case) == got, "the live reference disagrees with the pins stored for " + case
+    return got
 
 
 def live_mask(counts, cap):

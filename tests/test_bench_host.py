@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -164,3 +165,54 @@ def test_source_hash_ignores_comments():
     assert _code_only(a).split() == _code_only(b).split()
     assert '"// kept /* kept */"' in _code_only(a)
     assert _code_only(a) != _code_only(a.replace("= 2", "= 3"))
+
+
+def test_dump_outputs_are_a_fixed_sample_of_the_last_step(bench, tmp_path):
+    """--dump-outputs: what SPH.getParticles() / energy() hand a caller, float32 / float64 only, the
+    same seeded sample of particles in every run, at most 64 MB for the flagship's 4M particles"""
+    from types import SimpleNamespace
+
+    class FakeContext:
+        def __init__(self, n):
+            r = np.random.default_rng(1)
+            self.part = SimpleNamespace(mPosition=r.random(3 * n, dtype=np.float32),
+                                        mVelocity=r.random(3 * n, dtype=np.float32),
+                                        mDensity=r.random(n, dtype=np.float32),
+                                        mAcceleration=r.random(3 * n, dtype=np.float32),
+                                        mNeighborCount=r.integers(0, 200, n).astype(np.int32))
+
+        def getParticles(self):
+            return self.part
+
+        def energy(self):
+            return 1.5, -2.25
+
+    n = 4 * 1024 * 1024
+    ctx = FakeContext(n)
+    out = bench.last_step_outputs(ctx, n)
+    again = bench.last_step_outputs(ctx, n)
+    names = bench.dump_outputs(out, str(tmp_path))
+    total = 0
+    for name in names:
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64), name
+        assert np.array_equal(a, again[name]), name
+        total += os.path.getsize(tmp_path / (name + ".npy"))
+    assert total <= 64 * 1024 * 1024
+    idx = out["particle_index"].astype(np.int64)
+    assert idx.size == bench.DUMP_SAMPLE and np.all(np.diff(idx) > 0) and idx[-1] < n
+    assert np.array_equal(out["position"], ctx.part.mPosition.reshape(-1, 3)[idx])
+    assert np.array_equal(out["acceleration"], ctx.part.mAcceleration.reshape(-1, 3)[idx])
+    assert np.array_equal(out["neighbor_count"], ctx.part.mNeighborCount[idx].astype(np.float32))
+    assert list(out["energy"]) == [1.5, -2.25]
+    small = bench.last_step_outputs(FakeContext(1000), 1000)     # a small run: every particle
+    assert np.array_equal(small["particle_index"], np.arange(1000))
+
+
+def test_steps_must_be_positive(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--dump-outputs", "d"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()

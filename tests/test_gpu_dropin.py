@@ -4,8 +4,9 @@ vec3.cpp and moc output) run as a headless program, like the reference's `./sph 
 
 The host mirrors it leaves behind — Particle::mPosition/mVelocity/mDensity/mAcceleration/
 mNeighborCount — must hash to the golden vectors produced by the reference itself for its
-default scene (N = 32*1024, srand(42) sphere).  The binary is built by `make -C integration`
-where /root/reference exists and travels with the tree; elsewhere the test is skipped."""
+default scene (N = 32*1024, srand(42) sphere).  The binary is built by `make -C oracle dropin`
+(build()) where /root/reference exists and travels with the tree under oracle/_ref/; elsewhere the
+test is skipped."""
 import json
 import os
 import subprocess
@@ -18,13 +19,13 @@ from helpers import sha
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEMO = os.path.join(ROOT, "integration", "_ref", "sph_dropin_demo")
+DEMO = os.path.join(ROOT, "oracle", "_ref", "sph_dropin_demo")
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "golden.json")))
 
 
 def run_demo(tmp_path, steps, full=False, sync=False, phases=False):
     if not os.path.exists(DEMO):
-        pytest.skip("integration/_ref/sph_dropin_demo not built (needs the reference tree)")
+        pytest.skip("oracle/_ref/sph_dropin_demo not built (needs the reference tree)")
     out = str(tmp_path / "state.bin")
     env = dict(os.environ)
     env.pop("SPH_HIP_FULL", None)

@@ -1,21 +1,24 @@
-"""The CPU restatement against the reference's own compiled sph.cpp, live (needs
-oracle/_ref/libsphref.so: `make -C oracle ref` where /root/reference exists; the built library
-travels with the tree).  Skipped where that library cannot be loaded — test_oracle_golden.py
-carries the same pins as data."""
+"""The CPU restatement against the reference's own compiled sph.cpp.  Live where
+oracle/_ref/libsphref.so can be loaded (`make -C oracle ref` where the reference tree exists; the
+built library travels with the tree); elsewhere against what that library computed for the same
+inputs, pinned in tests/golden/reference_pins.json (helpers.reference_pins: SHA-256 of every array,
+exact numbers).  test_oracle_golden.py carries more pins of the same kind."""
 import numpy as np
 import pytest
 
-from helpers import live_mask
+from helpers import live_mask, pin_sha, reference_pins
+
+CONSTANT_NAMES = ["h", "h2", "hscaled", "hscaled2", "hscaled6", "hscaled9", "htimes2", "htimes2inv",
+                  "kernel1", "kernel2", "kernel3", "softening", "rho0", "stiffness", "viscosity",
+                  "time_step", "cfl_limit", "cfl_limit2", "grav_const", "central_mass"]
 
 
-def test_constructor_constants(oracle, reference):
+def test_constructor_constants(oracle):
     """A0: every constant SPH::SPH() derives (reference src/sph.cpp:46-98)"""
     p = oracle.params_for_h(0.1)
-    c = reference.constants()
-    names = ["h", "h2", "hscaled", "hscaled2", "hscaled6", "hscaled9", "htimes2", "htimes2inv",
-             "kernel1", "kernel2", "kernel3", "softening", "rho0", "stiffness", "viscosity",
-             "time_step", "cfl_limit", "cfl_limit2", "grav_const", "central_mass"]
-    for i, nm in enumerate(names):
+    ref = reference_pins("constructor_constants", lambda R: {"constants": list(R.constants())})
+    c = np.float32(ref["constants"])
+    for i, nm in enumerate(CONSTANT_NAMES):
         assert np.float32(getattr(p, nm)) == c[i], nm
     assert list(np.float32(p.central_pos)) == list(c[20:23])
     assert np.float32(p.cell_size) == c[23]
@@ -24,49 +27,67 @@ def test_constructor_constants(oracle, reference):
     assert [p.cells_x, p.cells_y, p.cells_z] == [int(v) for v in c[29:32]]
 
 
+def _ref_phases(p, n, cap):
+    """the reference's phases one by one on its default scene, every intermediate result"""
+    def run(R):
+        out = {}
+        R.configure(p, n)
+        R.init_sphere()
+        s = R.get_state()
+        out.update(pos0=s["pos"], vel0=s["vel"], mass=s["mass"])
+        R.voxelize()
+        out["voxel_coords"], out["voxel_ids"] = R.get_voxels()
+        out["grid_counts"] = R.get_grid_counts(32 ** 3)
+        R.find_neighbors()
+        nb, nd = R.get_lists()
+        out["ncount"] = R.get_state()["ncount"]
+        live = live_mask(out["ncount"], cap)
+        out["nb_live"], out["nd_live"] = nb[live], nd[live]
+        R.compute_density()
+        out["rho"] = R.get_state()["rho"]
+        R.compute_acceleration()
+        out["acc"] = R.get_state()["acc"]
+        R.integrate()
+        s = R.get_state()
+        out["pos"], out["vel"] = s["pos"], s["vel"]
+        out["energy"] = R.energy()
+        return out
+    return run
+
+
 @pytest.mark.parametrize("m", [8, 32, 96])
-def test_ref_phases_bit_exact(oracle, reference, m):
+def test_ref_phases_bit_exact(oracle, m):
     """A0', A1-A6 phase by phase on the reference's default scene at N = m*1024"""
     p = oracle.params_for_h(0.1)
     n = m * 1024
-    reference.configure(p, n)
-    reference.init_sphere()
-    s = reference.get_state()
-    pos, vel = oracle.init_sphere(p, n)
-    assert np.array_equal(pos, s["pos"]) and np.array_equal(vel, s["vel"])
-    mass = s["mass"]
     cap = p.examine_count
+    ref = reference_pins("ref_phases_M%d" % m, _ref_phases(p, n, cap))
+    pos, vel = oracle.init_sphere(p, n)
+    assert pin_sha(pos) == ref["pos0"] and pin_sha(vel) == ref["vel0"]
+    mass = np.ones(n, np.float32)
+    assert pin_sha(mass) == ref["mass"]
 
-    reference.voxelize()
-    rc, ri = reference.get_voxels()
     oc, oi, cs, ci = oracle.voxelize(p, pos)
-    assert np.array_equal(rc, oc) and np.array_equal(ri, oi)
-    assert np.array_equal(reference.get_grid_counts(32 ** 3), np.diff(cs))
+    assert pin_sha(oc) == ref["voxel_coords"] and pin_sha(oi) == ref["voxel_ids"]
+    assert pin_sha(np.diff(cs).astype(np.int32)) == ref["grid_counts"]
 
-    reference.find_neighbors()
-    rnb, rnd = reference.get_lists()
-    rcnt = reference.get_state()["ncount"]
     onb, ond, ocnt = oracle.find_neighbors(p, pos, oc, cs, ci)
-    assert np.array_equal(ocnt, rcnt)
+    assert pin_sha(ocnt) == ref["ncount"]
     live = live_mask(ocnt, cap)
-    assert np.array_equal(onb[live], rnb[live]) and np.array_equal(ond[live], rnd[live])
+    assert pin_sha(onb[live]) == ref["nb_live"] and pin_sha(ond[live]) == ref["nd_live"]
 
-    reference.compute_density()
     orho = oracle.density_lists(p, cap, onb, ond, ocnt, mass)
-    assert np.array_equal(orho, reference.get_state()["rho"])
+    assert pin_sha(orho) == ref["rho"]
 
-    reference.compute_acceleration()
     oacc = oracle.accel_lists(p, cap, onb, ond, ocnt, pos, vel, mass, orho)
-    assert np.array_equal(oacc, reference.get_state()["acc"])
+    assert pin_sha(oacc) == ref["acc"]
 
-    reference.integrate()
-    s = reference.get_state()
     oke, ope = oracle.integrate(p, pos, vel, oacc, mass)
-    assert np.array_equal(pos, s["pos"]) and np.array_equal(vel, s["vel"])
-    assert (oke, ope) == reference.energy()
+    assert pin_sha(pos) == ref["pos"] and pin_sha(vel) == ref["vel"]
+    assert [oke, ope] == ref["energy"]
 
 
-def test_ref_five_whole_steps_through_SPH_step(oracle, reference):
+def test_ref_five_whole_steps_through_SPH_step(oracle):
     """SPH::step() itself, five times, on a scene where the search finds many neighbours"""
     from test_oracle_golden import box_fill
     p = oracle.params_for_h(0.1)
@@ -74,20 +95,26 @@ def test_ref_five_whole_steps_through_SPH_step(oracle, reference):
     pos = box_fill(n, (1.0, 1.0, 1.0), (2.4, 2.2, 2.3), 17)
     vel = box_fill(n, (-3.0,) * 3, (3.0,) * 3, 18)
     mass = np.ones(n, np.float32)
-    reference.configure(p, n)
-    reference.set_state(pos, vel, mass)
+
+    def run(R):
+        R.configure(p, n)
+        R.set_state(pos, vel, mass)
+        for _ in range(5):
+            R.step()
+        s = R.get_state()
+        return {k: s[k] for k in ("pos", "vel", "rho", "acc", "ncount")}
+
+    ref = reference_pins("five_whole_steps", run)
     for _ in range(5):
-        reference.step()
         out = oracle.step(p, pos, vel, mass, mode="ref")
-    s = reference.get_state()
-    for a, b in ((pos, s["pos"]), (vel, s["vel"]), (out["rho"], s["rho"]), (out["acc"], s["acc"]),
-                 (out["ncount"], s["ncount"])):
-        assert np.array_equal(a, b)
+    for name, a in (("pos", pos), ("vel", vel), ("rho", out["rho"]), ("acc", out["acc"]),
+                    ("ncount", out["ncount"])):
+        assert pin_sha(a) == ref[name], name
     assert out["ncount"].max() > 20
 
 
 @pytest.mark.parametrize("scale", [1.0, 0.5])
-def test_full_mode_against_reference_pair_functions(oracle, reference, scale):
+def test_full_mode_against_reference_pair_functions(oracle, scale):
     """FULL mode: the oracle's lists (canonical order) fed to the reference's own
     computeDensity / computeAcceleration == the oracle's list-free FULL sums."""
     from test_oracle_golden import box_fill
@@ -101,21 +128,28 @@ def test_full_mode_against_reference_pair_functions(oracle, reference, scale):
     cap = 128
     nb, nd, cnt, worst = oracle.full_build_lists(p, pos, cap)
     assert worst <= cap and cnt.mean() > 20
-    reference.configure(p, n)
-    reference.set_state(pos, vel, mass)
-    reference.set_lists(cap, nb, nd, cnt)
-    reference.compute_density()
-    reference.compute_acceleration()
-    s = reference.get_state()
+
+    def run(R):
+        R.configure(p, n)
+        R.set_state(pos, vel, mass)
+        R.set_lists(cap, nb, nd, cnt)
+        R.compute_density()
+        R.compute_acceleration()
+        s = R.get_state()
+        out = {"rho": s["rho"], "acc": s["acc"]}
+        R.integrate()
+        s = R.get_state()
+        out.update(pos=s["pos"], vel=s["vel"], energy=R.energy())
+        return out
+
+    ref = reference_pins("full_pair_functions_scale%g" % scale, run)
     ids, cs, ci = oracle.full_cells(p, pos)
     orho, ocnt = oracle.full_density(p, pos, mass, cs, ci)
     oacc = oracle.full_accel(p, pos, vel, mass, orho, cs, ci)
     assert np.array_equal(ocnt, cnt)
-    assert np.array_equal(orho, s["rho"])
-    assert np.array_equal(oacc, s["acc"])
-    reference.integrate()
-    s = reference.get_state()
+    assert pin_sha(orho) == ref["rho"]
+    assert pin_sha(oacc) == ref["acc"]
     opos, ovel = pos.copy(), vel.copy()
     energies = oracle.integrate(p, opos, ovel, oacc, mass)
-    assert np.array_equal(opos, s["pos"]) and np.array_equal(ovel, s["vel"])
-    assert energies == reference.energy()
+    assert pin_sha(opos) == ref["pos"] and pin_sha(ovel) == ref["vel"]
+    assert list(energies) == ref["energy"]
