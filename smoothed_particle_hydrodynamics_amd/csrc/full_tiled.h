@@ -23,6 +23,7 @@
 // code of full_kernels.h inline — same results, slower, no extra launch.
 #pragma once
 
+#include "launch_policy.h"
 #include "common_kernels.h"
 #include "full_kernels.h"
 #include "slab_kernels.h"
@@ -97,13 +98,8 @@ __device__ unsigned int g_phase[2][PHASE_WGS][8];   // [kernel][workgroup][phase
 #define PHASE_COUNT(i)
 #endif
 
-// The tile lives in dynamic LDS: its capacity (candidate positions per workgroup) is a launch
-// parameter, chosen by the host from the tile sizes the previous steps needed, because the
-// workgroups a CU can hold (and with them the latency hiding of both passes) is set by the LDS
-// a workgroup asks for: 12 B (density) / 16 B (acceleration) per tile entry.
-#define TILE_PAD 32                      // slots past the capacity that aligned 8-slot reads may touch
-#define TILE_CAP_MAX (4096 - TILE_PAD)        // tile indices are 12-bit in narrow list entries
-#define TILE_CAP_MAX_WIDE (16384 - TILE_PAD)  // ... 14-bit in wide ones
+// The tile lives in dynamic LDS, its capacity chosen by the host per launch (launch_policy.h:
+// TILE_PAD, TILE_CAP_MAX, TILE_CAP_MAX_WIDE).
 #ifndef TILE_BATCH
 #define TILE_BATCH 8
 #endif

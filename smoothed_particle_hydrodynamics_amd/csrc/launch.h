@@ -1,0 +1,645 @@
+// Phase launches of a step and the step sequence built from them (no host sync inside a step
+// except where the tile capacity, the pacing or the list growth needs one, as commented).
+#pragma once
+
+#include <math.h>
+
+#include <type_traits>
+
+#include "context.h"
+
+namespace {
+
+// run-time flags -> template arguments: f(std::bool_constant..., one per flag)
+template <class F>
+void bind_flags(F&& f) { f(); }
+template <class F, class... Rest>
+void bind_flags(F&& f, bool flag, Rest... rest)
+{
+   if (flag) bind_flags([&](auto... later) { f(std::true_type{}, later...); }, rest...);
+   else bind_flags([&](auto... later) { f(std::false_type{}, later...); }, rest...);
+}
+
+PairConsts pair_consts(const sph_hip_params& p, bool fast)
+{
+   PairConsts k;
+   k.h2 = p.h2;
+   // SPH_HIP_TEST_SCREEN widens the screen (tests: many candidates then reach the exact
+   // confirmation and the list rewrite; the results must not change)
+   static const float screen = getenv("SPH_HIP_TEST_SCREEN") ? (float)atof(getenv("SPH_HIP_TEST_SCREEN"))
+                                                             : TEST_SCREEN_FACTOR;
+   k.h2_screen = p.h2 * (screen >= TEST_SCREEN_FACTOR ? screen : TEST_SCREEN_FACTOR);
+   k.hscaled = p.hscaled;
+   k.hscaled2 = p.hscaled2;
+   k.sim_scale = p.sim_scale;
+   k.kernel1 = p.kernel1;
+   k.kernel2 = p.kernel2;
+   k.kernel3 = p.kernel3;
+   {
+      // (pair_math.h: accel_pair_fast_pressure) |k2 s| * 2^-shift in [2^-8, 2^-7): times 1 / (d + 0.01)
+      // <= 100 the per-pair factor stays below 1, so it cannot overflow unless the reference's own
+      // term has; a zero or non-finite product keeps shift 0
+      const float k2s = p.kernel2 * p.sim_scale;
+      int e = 0, shift = 0;
+      if (std::isfinite(k2s) && k2s != 0.0f) {
+         (void)frexpf(k2s, &e);            // |k2s| = m * 2^e, m in [0.5, 1)
+         shift = e + 7;
+         shift = shift < -120 ? -120 : shift > 120 ? 120 : shift;
+      }
+      k.fast_k2s = ldexpf(k2s, -shift);
+      k.fast_unscale = ldexpf(1.0f, shift);
+   }
+   k.rho0 = p.rho0;
+   k.stiffness = p.stiffness;
+   k.viscosity = p.viscosity;
+   k.grav_const = p.grav_const;
+   k.central_mass = p.central_mass;
+   k.cx = p.central_pos[0];
+   k.cy = p.central_pos[1];
+   k.cz = p.central_pos[2];
+   k.softening = p.softening;
+   k.cfl_limit = p.cfl_limit;
+   k.cfl_limit2 = p.cfl_limit2;
+   k.dt = p.time_step;
+   k.sim_scale_inv = p.sim_scale_inv;
+   k.gx = p.gravity[0];
+   k.gy = p.gravity[1];
+   k.gz = p.gravity[2];
+   k.damping = p.damping;
+   k.max_x = p.max_x;
+   k.max_y = p.max_y;
+   k.max_z = p.max_z;
+   k.apply_gravity = p.apply_gravity;
+   k.apply_walls = p.apply_walls;
+   k.skip_point_mass = fast && p.central_mass == 0.0f && p.softening > 0.0f && std::isfinite(p.grav_const) ? 1 : 0;
+   return k;
+}
+
+// The kernels' UNIT_SCALE instantiations: mSimulationScale = 1 (no multiplication by it) and - what
+// lets the FULL-mode density sums drop the reference's "d > hscaled" test for pairs that passed
+// d2 < h2 (pair_math.h: density_accumulate<INSIDE>) - a smoothing length whose constants agree:
+// sqrtf(h2) <= hscaled.  Parameters that do not (a caller may set any) take the general
+// instantiations, which multiply by a scale of 1.0: the same bits.
+bool unit_scale(const sph_hip_params& p)
+{
+   return p.sim_scale == 1.0f && p.sim_scale_inv == 1.0f && sqrtf(p.h2) <= p.hscaled;
+}
+
+// ---- phase launches (no event recording, no host sync) ---------------------------------------
+
+// ---- LDS tile capacity (the decisions: launch_policy.h) -------------------------------------
+// The capacity levels of one tiled kernel: the runtime's occupancy calculator for registers and
+// waves, the MI355X's LDS granule for the rest.
+template <class Kernel>
+TileLevels tile_levels(Kernel kernel, int bytes_per_entry)
+{
+   hipFuncAttributes attr;
+   size_t static_lds = 2048;   // (no answer: the old slack)
+   if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel)) == hipSuccess)
+      static_lds = attr.sharedSizeBytes;
+   else
+      (void)hipGetLastError();
+   auto blocks_at = [&](int cap) {
+      int nb = 0;
+      const size_t bytes = (size_t)(cap + TILE_PAD) * bytes_per_entry;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, TILE_THREADS, bytes) != hipSuccess) {
+         (void)hipGetLastError();
+         return 0;
+      }
+      const size_t granules = (static_lds + bytes + LDS_GRANULE - 1) / LDS_GRANULE;
+      const int by_lds = (int)(LDS_PER_CU / (granules * LDS_GRANULE));
+      return nb < by_lds ? nb : by_lds;
+   };
+   const TileLevels t = search_levels(blocks_at, bytes_per_entry);
+   if (getenv("SPH_HIP_DEBUG")) {
+      fprintf(stderr, "sph_hip: tile capacity levels (%d B/entry):", bytes_per_entry);
+      for (int l = 0; l < t.n; l++) fprintf(stderr, " %d (%d/CU)", t.cap[l], blocks_at(t.cap[l]));
+      fprintf(stderr, "\n");
+   }
+   return t;
+}
+
+// the tiled kernels may ask for all of a CU's LDS as dynamic shared memory (set per context: the
+// attribute belongs to the function on the current device)
+void allow_large_tiles()
+{
+   const int most = 160 * 1024;
+   for (int m = 0; m < 16; m++) {
+      bind_flags([&](auto U, auto M, auto W, auto F) {
+         (void)hipFuncSetAttribute((const void*)(k_full_density_tiled<U.value, M.value, W.value, F.value>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, most);
+         (void)hipFuncSetAttribute((const void*)(k_full_density_chunked<U.value, M.value, W.value, F.value>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, most);
+         if constexpr (M.value || !F.value)   // (FAST never gathers masses: only its M = true form exists)
+            (void)hipFuncSetAttribute((const void*)(k_full_accel_lists<U.value, M.value, W.value, F.value>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      }, (m & 1) != 0, (m & 2) != 0, (m & 4) != 0, (m & 8) != 0);
+   }
+   (void)hipGetLastError();
+}
+
+// The density pass of an earlier step reported particles with more neighbours than their lists
+// hold (those lanes walk their candidates one by one in both passes, an order of magnitude
+// slower per particle): enlarge the lists for the steps from here on.  The device has
+// to be idle for the exchange of the allocation - once or twice in a run that compresses.
+// Never changes results, only which route a particle takes.
+void grow_lists(sph_hip_context* ctx)
+{
+   // the largest capacity the device has room for, at once (a second reallocation later would be
+   // a second stall); allocated while the device still works through the steps already enqueued
+   DevBuf<uint32_t> bigger;
+   int want = ctx->list_cap_max;
+   while (want > ctx->list_cap) {
+      const size_t words = ctx->list_blocks * list_rows(want) * TILE_THREADS;
+      if (dev_alloc(bigger, words) == hipSuccess) break;
+      (void)hipGetLastError();
+      bigger.reset();
+      want = smaller_list_cap(want);
+   }
+   if (!bigger || want <= ctx->list_cap) {
+      ctx->list_cap_max = ctx->list_cap;   // no memory for it: stay, and do not ask again
+      return;
+   }
+   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return;   // (an error is reported by the step itself)
+   ctx->nlist = std::move(bigger);
+   ctx->list_cap = want;
+   ctx->list_cap_max = want < ctx->list_cap_max ? want : ctx->list_cap_max;
+   ((volatile int*)ctx->tile_feedback)[TSTAT_NO_LIST] = 0;
+   static const bool debug = getenv("SPH_HIP_DEBUG") != nullptr;
+   if (debug) fprintf(stderr, "sph_hip: neighbour lists enlarged to %d entries\n", want);
+}
+
+// Capacities for the step about to be launched (before its k_tile_desc, which lists the
+// workgroups that will not fit them), from the feedback the device left in pinned memory.
+void pick_tile_caps(sph_hip_context* ctx)
+{
+   TileCaps& caps = ctx->caps;
+   if (ctx->list_cap < ctx->list_cap_max) {
+      const volatile int* word = ctx->tile_feedback;
+      if (lists_should_grow(word[TSTAT_NO_LIST], word[TSTAT_BLOCKS])) grow_lists(ctx);
+   }
+   if (caps.n_cand == 0) {
+      allow_large_tiles();
+      bind_flags([&](auto F) {
+         ctx->density_levels = tile_levels(k_full_density_tiled<true, true, false, F.value>, DENSITY_TILE_BYTES);
+         ctx->accel_levels = tile_levels(k_full_accel_lists<true, true, false, F.value>, ACCEL_TILE_BYTES);
+      }, ctx->fast != 0);
+      merge_candidates(ctx->density_levels, ctx->accel_levels, caps);
+      // The arithmetic was switched (sph_hip_set_arithmetic): other kernels, possibly other levels.
+      // The statistics the host holds were counted against the old candidate list: they stay valid
+      // when the list is the same, and mean nothing otherwise.
+      bool same = ctx->n_cand_kept == caps.n_cand;
+      for (int c = 0; same && c < caps.n_cand; c++) same = ctx->cand_kept[c] == caps.cand[c];
+      if (!same && ctx->n_cand_kept > 0 && ctx->tile_feedback) memset(ctx->tile_feedback, 0, TSTAT_COUNT * sizeof(int));
+      ctx->n_cand_kept = caps.n_cand;
+      for (int c = 0; c < caps.n_cand; c++) ctx->cand_kept[c] = caps.cand[c];
+   }
+   int fb[TSTAT_COUNT];
+   for (int i = 0; i < TSTAT_COUNT; i++) fb[i] = ((volatile int*)ctx->tile_feedback)[i];
+   choose_caps(caps, fb, ctx->density_levels, ctx->accel_levels, ctx->tile_cap_forced, ctx->tile_cap_accel,
+               ctx->tile_cap_density);
+   static int debug_left = getenv("SPH_HIP_DEBUG") ? 6 : 0;
+   if (ctx->tile_cap_forced <= 0 && debug_left > 0 && debug_left--)
+      fprintf(stderr, "sph_hip: %d workgroups, largest tile %d -> capacities %d / %d\n",
+              fb[TSTAT_BLOCKS], fb[TSTAT_MAX], caps.cap_density, caps.cap_accel);
+}
+
+// what the cell build has to know about the slab's neighbours
+SlabZone slab_zone(const sph_hip_context* ctx)
+{
+   SlabZone z;
+   z.lo = ctx->plane_lo;
+   z.hi = ctx->plane_hi;
+   z.halo = ctx->halo;
+   z.have_left = ctx->plane_lo > 0;
+   z.have_right = ctx->plane_hi < ctx->grid.nz_global;
+   z.drop_ghosts = ctx->mode == SPH_HIP_MODE_FULL;
+   z.early = ctx->early_exchange;
+   return z;
+}
+
+// clear_left/right: message buffers whose record counters this build zeroes (early exchange)
+int launch_cell_build(sph_hip_context* ctx, void* clear_left = nullptr, void* clear_right = nullptr,
+                      bool keep_sums = false)
+{
+   const int n = ctx->n;  // host upper bound of entries; the exact count is meta[META_N_IN]
+   if (n == 0) return SPH_HIP_OK;
+   const int blocks = div_up(n, 256);
+   const CellGrid g = ctx->grid;
+   hipStream_t st = ctx->stream;
+   const int cur = ctx->cur;
+   const SlabZone zone = slab_zone(ctx);
+   if (ctx->prehashed == 2) {
+      // a slab whose last step was integrated and hashed by its acceleration pass: only last
+      // step's ghosts (to the trash cell) and the records received since are left
+      ctx->prehashed = 0;
+      hipLaunchKernelGGL(k_hash_tail, dim3(SLAB_PACK_BLOCKS), dim3(256), 0, st, ctx->posm[cur], ctx->meta, g,
+                         ctx->key, ctx->slot, ctx->cell_count);
+   } else if (ctx->prehashed) {
+      ctx->prehashed = 0;   // the last integrate hashed and counted this very state already
+   } else {
+      const bool ref = ctx->mode == SPH_HIP_MODE_REF;
+      bind_flags([&](auto R, auto D) {
+         if constexpr (!(R.value && D.value))
+            hipLaunchKernelGGL((k_hash_count<R.value, D.value>), dim3(blocks), dim3(256), 0, st, ctx->posm[cur],
+                               ctx->velp[cur], ctx->meta, g, zone, ctx->key, ctx->slot, ctx->cell_count,
+                               R.value ? ctx->vox.get() : nullptr);
+      }, ref, !ref && ctx->may_hold_dead != 0);
+   }
+   ctx->early_exchange = 0;  // consumed: it described the step before this build
+   ctx->may_hold_dead = 0;   // the build drops dead entries
+   // the scan covers the real cells plus the trash cell, so cell_start[ncells] = live entries
+   const int tiles = ctx->scan_tiles;
+   const int ncells_scan = g.ncells + 1;
+   hipLaunchKernelGGL(k_scan_reduce, dim3(tiles), dim3(SCAN_THREADS), 0, st, ctx->cell_count,
+                      ncells_scan, ctx->scan_part);
+   hipLaunchKernelGGL(k_scan_final, dim3(tiles), dim3(SCAN_THREADS), 0, st, ctx->cell_count,
+                      ncells_scan, ctx->scan_part, ctx->cell_start, ctx->big_cells, (uint32_t)ctx->capacity,
+                      ctx->meta);
+   // sorted ranges: owned planes, density planes, owned planes next to a neighbouring slab
+   const PlaneRanges r = plane_ranges(ctx->plane_lo, ctx->plane_hi, g.z0, g.nz, ctx->halo, zone.have_left,
+                                      zone.have_right);
+   hipLaunchKernelGGL(k_scatter, dim3(blocks), dim3(256), 0, st, ctx->key, ctx->slot,
+                      ctx->cell_start, ctx->meta, ctx->perm, g.nx * g.ny, g.ncells, r.own_lo, r.own_hi,
+                      r.sum_lo, r.sum_hi, r.bnd_lo, r.bnd_hi, ctx->tile_stats, (int32_t*)clear_left,
+                      (int32_t*)clear_right, ctx->big_cells, (uint32_t)ctx->capacity);
+   // crowded cells (listed by k_scatter; none in an ordinary scene: the workgroups then leave at
+   // once) are ranked by sorting, behind the per-member scan that skips them; scratch = the
+   // staging buffer, idle during a step
+   uint32_t* scratch_key = reinterpret_cast<uint32_t*>(ctx->stage.get());
+   uint32_t* scratch_src = scratch_key + ctx->capacity;
+   // keep_sums (stand-alone voxelize of a FULL-mode context that holds the whole grid): note where
+   // every entry goes (in `slot`, free once k_scatter has run) and move rho / acc / ncount along
+   uint32_t* remap = (keep_sums && ctx->mode == SPH_HIP_MODE_FULL && !ctx->had_exchange) ? ctx->slot : nullptr;
+   if (ctx->mode == SPH_HIP_MODE_REF) {
+      hipLaunchKernelGGL(k_rank_order, dim3(blocks), dim3(256), 0, st, ctx->perm, ctx->key,
+                         ctx->cell_start, ctx->meta, ctx->order);
+      hipLaunchKernelGGL(k_rank_big<false>, dim3(RANK_BIG_BLOCKS), dim3(256), 0, st, ctx->big_cells,
+                         ctx->perm, ctx->cell_start, (const float4*)nullptr, (const float4*)nullptr,
+                         (float4*)nullptr, (float4*)nullptr, ctx->order, scratch_key, scratch_src,
+                         (uint32_t*)nullptr);
+   } else {
+      const int nxt = cur ^ 1;
+      if (ctx->use_tiled) {
+         // + the LDS tile layout of every 256-particle workgroup of the density range, with the
+         // statistics and give-up lists for the capacities chosen here for this step's sums
+         static_assert(sizeof(TileDesc) == 20 * sizeof(int), "TileDesc is 20 ints");
+         pick_tile_caps(ctx);
+         const int ntiles = div_up(n, TILE_THREADS), desc_blocks = div_up(ntiles, 256);
+         hipLaunchKernelGGL(k_rank_gather_tile_desc, dim3(desc_blocks + blocks), dim3(256), 0, st,
+                            desc_blocks, ntiles, ctx->perm, ctx->key, ctx->cell_start, ctx->meta,
+                            g, ctx->posm[cur], ctx->velp[cur], ctx->posm[nxt], ctx->velp[nxt],
+                            ctx->tile_desc, ctx->caps, ctx->tile_stats, ctx->giveup_density,
+                            ctx->giveup_accel, remap);
+      } else {
+         hipLaunchKernelGGL(k_rank_gather, dim3(blocks), dim3(256), 0, st, ctx->perm, ctx->key,
+                            ctx->cell_start, ctx->meta, g.ncells, ctx->posm[cur], ctx->velp[cur],
+                            ctx->posm[nxt], ctx->velp[nxt], remap);
+      }
+      hipLaunchKernelGGL(k_rank_big<true>, dim3(RANK_BIG_BLOCKS), dim3(256), 0, st, ctx->big_cells,
+                         ctx->perm, ctx->cell_start, ctx->posm[cur], ctx->velp[cur], ctx->posm[nxt],
+                         ctx->velp[nxt], (uint32_t*)nullptr, scratch_key, scratch_src, remap);
+      if (remap) {
+         // a build that is not followed by the sums: their last results move with the particles
+         // (temporaries in the staging buffer behind k_rank_big's scratch; the float4 part 16-byte aligned)
+         float4* acc_t = reinterpret_cast<float4*>(ctx->stage.get() + ((2 * (size_t)ctx->capacity + 3) & ~(size_t)3));
+         float* rho_t = reinterpret_cast<float*>(acc_t + (size_t)ctx->capacity);
+         int32_t* cnt_t = reinterpret_cast<int32_t*>(rho_t + (size_t)ctx->capacity);
+         hipLaunchKernelGGL(k_permute_sums, dim3(blocks), dim3(256), 0, st, remap, ctx->key, ctx->meta,
+                            (uint32_t)g.ncells, ctx->rho, ctx->acc, ctx->ncount, rho_t, acc_t, cnt_t);
+         SPH_TRY(hipMemcpyAsync(ctx->rho, rho_t, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+         SPH_TRY(hipMemcpyAsync(ctx->acc, acc_t, sizeof(float4) * n, hipMemcpyDeviceToDevice, st));
+         SPH_TRY(hipMemcpyAsync(ctx->ncount, cnt_t, sizeof(int32_t) * n, hipMemcpyDeviceToDevice, st));
+      }
+      ctx->cur = nxt;
+      // The live set is now compacted at the front of the new buffers.  meta[N_IN] still holds
+      // this build's input count: without an exchange nothing was dropped (n_live == n_in), and
+      // with one, sph_hip_slab_unpack resets it to n_live before appending.
+   }
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+int launch_find_neighbors(sph_hip_context* ctx)
+{
+   if (ctx->mode != SPH_HIP_MODE_REF || ctx->n == 0) return SPH_HIP_OK;
+   const sph_hip_params& p = ctx->prm;
+   hipLaunchKernelGGL(k_ref_find_neighbors, dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream,
+                      ctx->posm[0], ctx->vox, ctx->cell_start, ctx->order, ctx->n, p.cells_x,
+                      p.cells_y, p.cells_z, p.h, p.htimes2, p.h2, p.sim_scale, p.examine_count,
+                      ctx->nb, ctx->nd, ctx->ncount);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// message buffers of a slab whose acceleration pass does the rest of the step (FusedStep.slab)
+struct SlabFused {
+   void* left;
+   void* right;
+   int capacity;
+};
+
+// tiled kernels of the two sums, specialised on (unit simulation scale, uniform mass)
+void launch_density_tiled(sph_hip_context* ctx, bool unit, int blocks, const PairConsts& k)
+{
+   const int cap = ctx->caps.cap_density;
+   const size_t lds = (size_t)(cap + TILE_PAD) * DENSITY_TILE_BYTES;
+   // (a slab: the fused acceleration pass writes energy partials only for workgroups that own
+   // particles; this launch zeroes the others' - same grid, one pair per workgroup)
+   const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global;
+   double* epart_clear = whole ? nullptr : ctx->epart + 2;
+   // Many workgroups whose tile fits no capacity (a scene several times denser than the
+   // benchmark's): a launch of its own stages their candidates through LDS piece by piece and
+   // writes their lists (k_full_density_chunked) instead of the tiled kernel's first workgroups
+   // walking them untiled.  Decided from what the last step reported; both kernels read the same
+   // device-side list, the flag only says who works it off.
+   const int reported = ((volatile int*)ctx->tile_feedback)[TSTAT_GIVEUP_DENSITY];
+   const bool chunked = ctx->chunked_giveups == 1 || (ctx->chunked_giveups < 0 && reported >= 32);
+   // The two kernels work on disjoint workgroups: the chunked one runs beside the tiled one on a
+   // stream of its own (forked here, joined before anything else is enqueued) - alone it would
+   // leave the device to ~1 000 long workgroups while the other 15 000 wait.
+   hipStream_t side = ctx->stream;
+   if (chunked) {
+      if (!ctx->chunk_stream) {
+         if (hipStreamCreateWithFlags(ctx->chunk_stream.out(), hipStreamNonBlocking) != hipSuccess ||
+             event_create(ctx->ev_chunk_fork) != hipSuccess || event_create(ctx->ev_chunk_join) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->chunk_stream.reset();
+         }
+      }
+      if (ctx->chunk_stream && hipEventRecord(ctx->ev_chunk_fork, ctx->stream) == hipSuccess &&
+          hipStreamWaitEvent(ctx->chunk_stream, ctx->ev_chunk_fork, 0) == hipSuccess)
+         side = ctx->chunk_stream;
+   }
+   bind_flags([&](auto U, auto M, auto W, auto F) {
+      if (chunked)
+         hipLaunchKernelGGL((k_full_density_chunked<U.value, M.value, W.value, F.value>), dim3(1024),
+                            dim3(TILE_THREADS), lds, side, ctx->posm[ctx->cur], ctx->velp[ctx->cur],
+                            ctx->cell_start, ctx->meta, ctx->grid, k, ctx->rho, ctx->velB, ctx->auxc,
+                            ctx->ncount, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, cap,
+                            ctx->tile_stats, ctx->giveup_density, ctx->list_cap);
+      hipLaunchKernelGGL((k_full_density_tiled<U.value, M.value, W.value, F.value>), dim3(blocks),
+                         dim3(TILE_THREADS), lds, ctx->stream, ctx->posm[ctx->cur], ctx->velp[ctx->cur],
+                         ctx->cell_start, ctx->meta, ctx->grid, k, ctx->rho, ctx->velB, ctx->auxc,
+                         ctx->ncount, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, cap,
+                         ctx->tile_stats, ctx->giveup_density, ctx->tile_feedback, ctx->list_cap,
+                         epart_clear, chunked ? 0 : 1);
+   }, unit, ctx->uniform_mass != 0, ctx->caps.wide != 0, ctx->fast != 0);
+   if (side != ctx->stream) {
+      // (a failure here would leave the streams unordered: drain the side stream the hard way)
+      if (hipEventRecord(ctx->ev_chunk_join, side) != hipSuccess ||
+          hipStreamWaitEvent(ctx->stream, ctx->ev_chunk_join, 0) != hipSuccess) {
+         (void)hipGetLastError();
+         (void)hipStreamSynchronize(side);
+      }
+   }
+}
+
+void launch_accel_lists(sph_hip_context* ctx, bool unit, int blocks, const PairConsts& k, int part,
+                        hipStream_t st, bool fused = false, const SlabFused* slab = nullptr)
+{
+   FusedStep fs;
+   memset(&fs, 0, sizeof(fs));
+   if (fused) {
+      fs.on = 1;
+      fs.velp_in = ctx->velp[ctx->cur];
+      fs.posm_out = ctx->posm[ctx->cur ^ 1];
+      fs.velp_out = ctx->velp[ctx->cur ^ 1];
+      fs.epart = ctx->epart + 2;
+      fs.key = ctx->key;
+      fs.slot = ctx->slot;
+      fs.cell_count = ctx->cell_count;
+      if (slab) {
+         fs.slab = 1;
+         fs.zone = slab_zone(ctx);
+         fs.left = (SlabMsg*)slab->left;
+         fs.right = (SlabMsg*)slab->right;
+         fs.msg_capacity = slab->capacity;
+         fs.meta = ctx->meta;
+      }
+   }
+   const int cap = ctx->caps.cap_accel;
+   const size_t lds = (size_t)(cap + TILE_PAD) * ACCEL_TILE_BYTES;
+   // (a FAST context's density pass folds the mass into B: its acceleration pass never gathers masses)
+   bind_flags([&](auto U, auto M, auto W, auto F) {
+      if constexpr (M.value || !F.value)
+      hipLaunchKernelGGL((k_full_accel_lists<U.value, M.value, W.value, F.value>), dim3(blocks),
+                         dim3(TILE_THREADS), lds, st, ctx->posm[ctx->cur], ctx->velB, ctx->rho, ctx->auxc,
+                         ctx->ncount, ctx->cell_start, ctx->meta, ctx->grid, k, ctx->acc, ctx->tile_desc,
+                         ctx->nlist, ctx->nlist_overflow, cap, ctx->tile_stats, ctx->giveup_accel, part,
+                         ctx->list_cap, ctx->tile_feedback, fs, ctx->caps.cap_density);
+   }, unit, ctx->uniform_mass != 0 || ctx->fast != 0, ctx->caps.wide != 0, ctx->fast != 0);
+}
+
+int launch_density(sph_hip_context* ctx)
+{
+   const int n = ctx->n;
+   if (n == 0) return SPH_HIP_OK;
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const int blocks = div_up(n, 256);
+   if (ctx->mode == SPH_HIP_MODE_REF) {
+      hipLaunchKernelGGL(k_ref_density, dim3(blocks), dim3(256), 0, ctx->stream, ctx->posm[0],
+                         ctx->nb, ctx->nd, ctx->ncount, n, ctx->prm.examine_count, k, ctx->rho);
+   } else {
+      const bool unit = unit_scale(ctx->prm);
+      if (ctx->use_tiled) {
+         launch_density_tiled(ctx, unit, div_up(n, TILE_THREADS), k);  // give-up workgroups fall back inline
+      } else {                                         // SPH_HIP_UNTILED=1: untiled everywhere
+         bind_flags([&](auto U, auto F) {
+            hipLaunchKernelGGL((k_full_density<U.value, F.value>), dim3(blocks), dim3(256), 0, ctx->stream,
+                               ctx->posm[ctx->cur], ctx->cell_start, ctx->velp[ctx->cur], ctx->meta,
+                               ctx->grid, k, ctx->rho, ctx->velB, ctx->auxc, ctx->ncount);
+         }, unit, ctx->fast != 0);
+      }
+   }
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// part: 0 = all workgroups; 1 / 2 = those with / without particles of the owned planes next to
+// a neighbouring slab (early exchange; tiled FULL mode only)
+int launch_accel(sph_hip_context* ctx, int part = 0, hipStream_t part_stream = nullptr, bool fused = false,
+                 const SlabFused* slab = nullptr)
+{
+   const int n = ctx->n;
+   if (n == 0) return SPH_HIP_OK;
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const int blocks = div_up(n, 256);
+   if (ctx->mode == SPH_HIP_MODE_REF) {
+      hipLaunchKernelGGL(k_ref_accel, dim3(blocks), dim3(256), 0, ctx->stream, ctx->posm[0],
+                         ctx->velp[0], ctx->rho, ctx->nb, ctx->nd, ctx->ncount, n,
+                         ctx->prm.examine_count, k, ctx->acc);
+   } else {
+      const bool unit = unit_scale(ctx->prm);
+      if (ctx->use_tiled) {
+         // same tiling (and tile descriptors) as the density pass of this step
+         launch_accel_lists(ctx, unit, div_up(n, TILE_THREADS), k, part, part ? part_stream : ctx->stream, fused, slab);
+      } else {
+         bind_flags([&](auto U, auto F) {
+            hipLaunchKernelGGL((k_full_accel<U.value, F.value>), dim3(blocks), dim3(256), 0, ctx->stream,
+                               ctx->posm[ctx->cur], ctx->velB, ctx->rho, ctx->auxc, ctx->cell_start,
+                               ctx->meta, ctx->grid, k, ctx->acc, ctx->ncount);
+         }, unit, ctx->fast != 0);
+      }
+   }
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// with_hash: the kernel also does the first step of the next cell build (see k_integrate)
+int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
+{
+   const int n = ctx->n;
+   if (n == 0) return SPH_HIP_OK;
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const int blocks = div_up(n, RED_THREADS);
+   bind_flags([&](auto U, auto H) {
+      hipLaunchKernelGGL((k_integrate<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                         ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                         ctx->grid, ctx->key, ctx->slot, ctx->cell_count);
+   }, unit_scale(ctx->prm), with_hash);
+   ctx->energy_blocks = blocks;  // totals are formed on demand (sph_hip_get_energy)
+   ctx->prehashed = with_hash ? 1 : 0;
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
+// buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
+// (prehashed: 1 whole grid, 2 a slab's owned entries).
+void fused_step_done(sph_hip_context* ctx, int prehashed)
+{
+   ctx->cur ^= 1;
+   ctx->energy_blocks = div_up(ctx->n, TILE_THREADS);
+   ctx->prehashed = prehashed;
+}
+
+// The state is about to change behind the back of a prehash (upload, exchange, stand-alone
+// integrate): forget it, and clear the counts it left in the histogram.
+int drop_prehash(sph_hip_context* ctx)
+{
+   if (!ctx->prehashed) return SPH_HIP_OK;
+   ctx->prehashed = 0;
+   SPH_TRY(hipMemsetAsync(ctx->cell_count, 0, ((size_t)ctx->scan_tiles * SCAN_TILE + 16) * sizeof(uint32_t),
+                          ctx->stream));
+   return SPH_HIP_OK;
+}
+
+// Keeps the host from running arbitrarily far ahead of the device.  Launch parameters that follow
+// the scene - the LDS tile capacities, chosen from statistics the device writes into pinned memory
+// (tile_feedback) - are fixed when a step is ENQUEUED: a host that enqueues hundreds of steps at
+// once (sph_hip_run(500)) would pick them all from the state before the first one, and a scene that
+// compresses meanwhile ends up with nearly every workgroup on the untiled route.  Every PACE_STEPS
+// steps an event is recorded and the event of PACE_STEPS steps ago waited for: the device always has
+// at least PACE_STEPS steps queued (no bubble), the statistics are at most 2 * PACE_STEPS steps old.
+int pace_host(sph_hip_context* ctx)
+{
+   const long long k = ctx->steps_enqueued++;
+   if (k % PACE_STEPS != 0) return SPH_HIP_OK;
+   const int slot = (int)((k / PACE_STEPS) & 1);
+   if (k >= 2 * PACE_STEPS) SPH_TRY(hipEventSynchronize(ctx->ev_pace[slot]));   // recorded 2 * PACE_STEPS steps ago
+   SPH_TRY(hipEventRecord(ctx->ev_pace[slot], ctx->stream));
+   return SPH_HIP_OK;
+}
+
+// The phase events of the step being enqueued: its timing level (launch_policy.h:
+// next_step_level) and the event ring slot they go to.
+struct StepEvents {
+   Event* ev;
+   int level;
+   bool full;
+};
+
+StepEvents step_events(sph_hip_context* ctx, int level)
+{
+   return {ctx->ev[ctx->ev_steps % EV_RING], level, ctx->mode == SPH_HIP_MODE_FULL};
+}
+
+// opens a step: pacing, then the level and ring slot of its events
+int open_step(sph_hip_context* ctx, bool timed, StepEvents& se)
+{
+   int rc = pace_host(ctx);
+   if (rc) return rc;
+   se = step_events(ctx, next_step_level(timed, ctx->timing_level, ctx->timing_seen, ctx->timing_stride));
+   return SPH_HIP_OK;
+}
+
+// phase boundary k (0 .. 6) on stream st, if the step's level records it; boundary 6 ends the step
+int mark_phase(sph_hip_context* ctx, const StepEvents& se, int k, hipStream_t st)
+{
+   if (records_boundary(se.level, se.full, k)) SPH_TRY(hipEventRecord(se.ev[k], st));
+   if (k == 6 && se.level != SPH_HIP_TIMING_OFF) ctx->ev_steps++;
+   return SPH_HIP_OK;
+}
+
+int step_impl(sph_hip_context* ctx, bool timed)
+{
+   int rc;
+   hipStream_t st = ctx->stream;
+   StepEvents se;
+   if ((rc = open_step(ctx, timed, se))) return rc;
+   if ((rc = mark_phase(ctx, se, 0, st))) return rc;
+   if ((rc = launch_cell_build(ctx))) return rc;
+   if ((rc = mark_phase(ctx, se, 1, st))) return rc;
+   if ((rc = launch_find_neighbors(ctx))) return rc;
+   if ((rc = mark_phase(ctx, se, 2, st))) return rc;
+   if ((rc = launch_density(ctx))) return rc;
+   if ((rc = mark_phase(ctx, se, 3, st))) return rc;
+   // a context that holds the whole grid and has never exchanged anything: the integrate also
+   // hashes and counts for the next cell build - and the tiled acceleration pass does both itself
+   const bool hash_too = ctx->mode == SPH_HIP_MODE_FULL && !ctx->had_exchange && ctx->plane_lo == 0 &&
+                         ctx->plane_hi == ctx->grid.nz_global && !ctx->no_prehash;
+   const bool fused = hash_too && ctx->use_tiled && ctx->n > 0 && !ctx->no_fused_integrate;
+   if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;
+   if ((rc = mark_phase(ctx, se, 5, st))) return rc;
+   if (fused) fused_step_done(ctx, 1);
+   else if ((rc = launch_integrate(ctx, hash_too))) return rc;
+   return mark_phase(ctx, se, 6, st);
+}
+
+// the six phase times of the step in ring slot `ev` (see sph_hip_set_timing)
+int read_phases(sph_hip_context* ctx, const Event* ev, float ms[6])
+{
+   for (int k = 0; k < 6; k++) ms[k] = 0.0f;
+   if (ctx->timing_level == SPH_HIP_TIMING_SUMS) {
+      SPH_TRY(hipEventSynchronize(ev[5]));
+      SPH_TRY(hipEventElapsedTime(&ms[2], ev[1], ev[5]));
+      return SPH_HIP_OK;
+   }
+   SPH_TRY(hipEventSynchronize(ev[6]));
+   const bool full = ctx->mode == SPH_HIP_MODE_FULL;
+   for (int k = 0; k < 6; k++)
+      SPH_TRY(hipEventElapsedTime(&ms[k], ev[phase_event(full, k)], ev[phase_event(full, k + 1)]));
+   return SPH_HIP_OK;
+}
+
+// ---- error word of the slab exchange, watched without draining the stream ------------------------
+// Request a copy of meta[META_ERRORS] into the pinned watch word.  Before that, wait for the
+// PREVIOUS request (made one polling interval ago): normally long done; when the host has run far
+// ahead of the device it holds the host back to at most two intervals of queued steps, which is
+// what makes "reported within two intervals" true.
+int watch_enqueue(sph_hip_context* ctx)
+{
+   if (ctx->watch_pending) SPH_TRY(hipEventSynchronize(ctx->watch_event));
+   SPH_TRY(hipMemcpyAsync((void*)ctx->err_watch.get(), ctx->meta + META_ERRORS, sizeof(int32_t),
+                          hipMemcpyDeviceToHost, ctx->stream));
+   SPH_TRY(hipEventRecord(ctx->watch_event, ctx->stream));
+   ctx->watch_pending = 1;
+   return SPH_HIP_OK;
+}
+
+// what the last arrived copy said
+int watch_check(sph_hip_context* ctx, const char* who)
+{
+   const int32_t bits = ctx->err_watch[0];
+   if (bits == 0) return SPH_HIP_OK;
+   char text[256];
+   snprintf(text, sizeof(text),
+            "%s: the slab exchange lost particles, error bits %d (1 entry outside slab and halo, "
+            "2 message overflow, 4 context capacity, 8 missed by the early exchange, 16 a particle id "
+            "held twice)", who, (int)bits);
+   ctx->err = text;
+   return SPH_HIP_ERR_EXCHANGE;
+}
+
+} // namespace

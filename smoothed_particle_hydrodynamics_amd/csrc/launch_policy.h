@@ -1,0 +1,282 @@
+// Launch decisions of the host code as functions of plain values: which LDS tile capacities the
+// tiled FULL-mode passes get, when the neighbour lists and the trimmed slab messages grow, which
+// plane ranges a slab's cell build sorts, and which phase events a timed step records.
+// Pure C++17 without HIP (tests/test_launch_policy.py compiles it with g++); the runtime queries,
+// environment switches and pinned feedback words are read by the callers and passed in.
+#pragma once
+
+#include <stdint.h>
+
+#include "../../include/sph_hip.h"
+
+// particles (= threads) of one workgroup of the tiled FULL-mode passes
+#ifndef TILE_THREADS
+#define TILE_THREADS 256
+#endif
+// The tile lives in dynamic LDS: its capacity (candidate positions per workgroup) is a launch
+// parameter, chosen by the host from the tile sizes the previous steps needed, because the
+// workgroups a CU can hold (and with them the latency hiding of both passes) is set by the LDS
+// a workgroup asks for: 12 B (density) / 16 B (acceleration) per tile entry.
+#define TILE_PAD 32                      // slots past the capacity that aligned 8-slot reads may touch
+#define TILE_CAP_MAX (4096 - TILE_PAD)        // tile indices are 12-bit in narrow list entries
+#define TILE_CAP_MAX_WIDE (16384 - TILE_PAD)  // ... 14-bit in wide ones
+
+// Per-step statistics of the LDS tiles (k_tile_desc), fed back to the host's choice of tile
+// capacity: how many workgroups would not fit each candidate capacity.
+#define TILE_CANDS 12
+enum {
+   TSTAT_OVER = 0,            // [TILE_CANDS] workgroups whose tile exceeds candidate i
+   TSTAT_BLOCKS = 12,         // workgroups counted
+   TSTAT_MAX = 13,            // largest tile
+   TSTAT_GIVEUP_DENSITY = 14, // entries of the give-up lists of the current step
+   TSTAT_GIVEUP_ACCEL = 15,
+   TSTAT_NO_LIST = 16,        // particles with more neighbours than their list holds (density pass)
+   TSTAT_COUNT = 17
+};
+struct TileCaps {
+   int cand[TILE_CANDS];    // ascending candidate capacities (the occupancy levels of both kernels)
+   int n_cand;
+   int cap_density;         // capacities the current step's launches use
+   int cap_accel;
+   int wide;                // list entries carry a 14-bit tile index (a capacity above 4064)
+};
+
+// trimmed slab messages grow back to their allocated size when one is more than 4/5 full
+#define SLAB_GROW_FILL_NUM 4
+#define SLAB_GROW_FILL_DEN 5
+
+// ---- LDS tile capacity ---------------------------------------------------------------------
+// For every workgroups-per-CU count B a tiled kernel can reach, the largest tile (multiple of
+// 32 entries) that still lets B workgroups share a CU.  Registers and waves: the runtime's
+// occupancy calculator.  LDS: the MI355X hands a workgroup its LDS (static + dynamic) in units of
+// 1280 bytes out of 160 KiB per CU - measured with a sweep of pinned capacities (tools/cap_sweep.py:
+// the density pass drops from 6 to 5 workgroups per CU between 2176 and 2208 entries and from 5 to
+// 4 between 2624 and 2656, the acceleration pass from 4 to 3 between 2496 and 2528; the
+// calculator's own rounding is finer, and a size it rated 3/CU ran at 2/CU, which rounds 1-2 used
+// to cover with 2 KiB of slack per workgroup at the price of 130-190 entries per level).
+#define LDS_PER_CU (160 * 1024)
+#define LDS_GRANULE 1280
+
+// relative throughput by workgroups per CU (index 1..6)
+// (On the 4M column at rest, with one pass pinned to each level - tools/occupancy_prices.py,
+// round 3 - the passes lose more than this below 5 per CU: density 1 / 0.97 / 0.87 / 0.74 / 0.54 at
+// 6 .. 2, acceleration 1 / 0.935 / 0.82 / 0.60 at 5 .. 2.  With those figures the breaking dam,
+// whose large tiles also hold more work per workgroup, ran 2-10 % slower in five of its sixteen
+// windows and faster in none: the tables stay as the breaking dam tuned them.)
+static const float DENSITY_THR[7] = {0.0f, 0.33f, 0.62f, 0.85f, 0.93f, 0.97f, 1.0f};
+static const float ACCEL_THR[7] = {0.0f, 0.40f, 0.68f, 0.87f, 0.98f, 1.0f, 1.0f};
+// what a workgroup whose tile fits no capacity costs, in units of a tiled one: the density pass
+// (k_full_density_chunked) and the acceleration pass searching untiled ...
+// (Round 4: 3 since that kernel confirms at the pop and stages its appends; the 600-step transient of the
+// breaking 4M dam - tools/dam_windows.py - takes 1712 ms with 6, 1690 with 3, 1697 with 2, 1799 with 1.5.)
+#ifndef DENSITY_GIVEUP_COST
+#define DENSITY_GIVEUP_COST 3.0f
+#endif
+#define ACCEL_UNTILED_COST 8.0f
+// ... and what a workgroup of the acceleration pass costs on the list-driven route without a tile
+// (accel_from_lists)
+#ifndef ACCEL_LISTED_COST
+#define ACCEL_LISTED_COST 2.5f
+#endif
+
+// the capacity levels of one tiled kernel, ascending, with the workgroups per CU each allows
+struct TileLevels {
+   int cap[TILE_CANDS];
+   int per_cu[TILE_CANDS];
+   int n;
+};
+
+// blocks_at(cap): workgroups per CU of a tile of `cap` entries (0: no answer from the runtime)
+template <class BlocksAt>
+TileLevels search_levels(BlocksAt blocks_at, int bytes_per_entry)
+{
+   TileLevels t = {};
+   // a workgroup may take the whole LDS of a CU (160 KiB); the 14-bit tile index of wide list
+   // entries stops a little earlier for 12-byte entries
+   int cap_max = TILE_CAP_MAX_WIDE;
+   while (cap_max > 256 && (long long)(cap_max + TILE_PAD) * bytes_per_entry > 156 * 1024) cap_max -= 32;
+   const int cap_min = 1024 - TILE_PAD;
+   int prev = 0;
+   for (int want = blocks_at(cap_min); want >= 1 && t.n < TILE_CANDS / 2; want--) {
+      int lo = cap_min, hi = cap_max;            // largest cap with blocks_at(cap) >= want
+      while (lo < hi) {
+         const int mid = lo + ((hi - lo) / 32 + 1) / 2 * 32;
+         if (blocks_at(mid) >= want) lo = mid;
+         else hi = mid - 32;
+      }
+      if (lo > prev) {
+         t.per_cu[t.n] = want;
+         t.cap[t.n++] = prev = lo;
+      }
+      if (lo >= cap_max) break;
+   }
+   if (t.n == 0) {                                 // no answer from the runtime: a size that fits
+      t.per_cu[t.n] = 3;
+      t.cap[t.n++] = 3008;
+   }
+   return t;
+}
+
+// candidates = ascending union of both kernels' levels
+inline void merge_candidates(const TileLevels& d, const TileLevels& a, TileCaps& caps)
+{
+   int nd = 0, na = 0;
+   caps.n_cand = 0;
+   while ((nd < d.n || na < a.n) && caps.n_cand < TILE_CANDS) {
+      const int x = nd < d.n ? d.cap[nd] : INT32_MAX;
+      const int y = na < a.n ? a.cap[na] : INT32_MAX;
+      const int v = x < y ? x : y;
+      if (x == v) nd++;
+      if (y == v) na++;
+      caps.cand[caps.n_cand++] = v;
+   }
+}
+
+// workgroups of the last reported step whose tile exceeds `cap` (all of them when it is no candidate)
+inline int over_at(const TileCaps& caps, const int* fb, int cap)
+{
+   int over = fb[TSTAT_BLOCKS];
+   for (int c = 0; c < caps.n_cand; c++)
+      if (caps.cand[c] == cap) over = fb[TSTAT_OVER + c];
+   return over;
+}
+
+// Level with the least expected cost for the workgroups of the latest reported step.  A larger
+// tile means fewer workgroups per CU (relative throughput thr), a smaller one sends the workgroups
+// that do not fit down the untiled route (several times the work, and ~100 us from start to end
+// however little else there is to do - launches too short to hide that must not have any).
+// Nothing reported yet: the level next to 3008 entries.
+inline int pick_level(const TileCaps& caps, const int* fb, const TileLevels& lv, const float* thr,
+                      float untiled_cost, int over_other = -1, float listed_cost = 0.0f)
+{
+   const int blocks = fb[TSTAT_BLOCKS];
+   if (blocks <= 0) {
+      for (int l = 0; l < lv.n; l++)
+         if (lv.cap[l] >= 3008) return lv.cap[l];
+      return lv.cap[lv.n - 1];
+   }
+   const bool hides_untiled = blocks >= 8192 * 256 / TILE_THREADS;
+   int best = lv.cap[lv.n - 1];
+   float best_cost = 1e30f;
+   for (int l = 0; l < lv.n; l++) {
+      const int over = over_at(caps, fb, lv.cap[l]);
+      if (over > 0 && !hides_untiled && l + 1 < lv.n) continue;
+      const float f = (float)over / (float)blocks;
+      const int b = lv.per_cu[l] < 1 ? 1 : (lv.per_cu[l] > 6 ? 6 : lv.per_cu[l]);
+      // (acceleration pass: of the workgroups that do not fit, those that fitted the density pass
+      // have their lists and take the cheaper list-driven route without a tile)
+      float f_search = f;
+      if (over_other >= 0) f_search = (float)(over_other < over ? over_other : over) / (float)blocks;
+      const float cost = (1.0f - f) / thr[b] + untiled_cost * f_search + listed_cost * (f - f_search);
+      if (cost < best_cost) {
+         best_cost = cost;
+         best = lv.cap[l];
+      }
+   }
+   return best;
+}
+
+// The capacities of the step about to be launched, from the feedback counters fb[TSTAT_COUNT].
+// forced > 0 (SPH_HIP_TILE_CAP) pins both; forced_accel / forced_density (SPH_HIP_TILE_CAP_ACCEL /
+// _DENSITY, multiples of 32) then make one pass's capacity smaller, and are ignored when they are not.
+inline void choose_caps(TileCaps& caps, const int* fb, const TileLevels& density, const TileLevels& accel,
+                        int forced, int forced_accel, int forced_density)
+{
+   if (forced > 0) {
+      caps.cap_density = caps.cap_accel = forced;
+      // (tests: a smaller capacity for the acceleration pass alone sends the workgroups in between
+      // down its list-driven route without a tile)
+      if (forced_accel >= 256 && forced_accel < caps.cap_accel) caps.cap_accel = forced_accel;
+      // (... and a smaller one for the density pass alone: workgroups that fit the acceleration
+      // pass's capacity but are on the give-up lists all the same)
+      if (forced_density >= 256 && forced_density < caps.cap_density) caps.cap_density = forced_density;
+      caps.wide = forced > TILE_CAP_MAX;
+      return;
+   }
+   caps.cap_density = pick_level(caps, fb, density, DENSITY_THR, DENSITY_GIVEUP_COST);
+   caps.cap_accel = pick_level(caps, fb, accel, ACCEL_THR, ACCEL_UNTILED_COST,
+                               over_at(caps, fb, caps.cap_density), ACCEL_LISTED_COST);
+   // both passes of a step read and write the same lists: one entry format for the two
+   caps.wide = caps.cap_density > TILE_CAP_MAX || caps.cap_accel > TILE_CAP_MAX;
+}
+
+// ---- neighbour lists -----------------------------------------------------------------------
+// The density pass reported `without` particles with more neighbours than their lists hold out
+// of `blocks` workgroups: enlarge the lists when that is more than 0.4 %.
+inline bool lists_should_grow(int without, int blocks)
+{
+   return without > 64 && without > blocks * (TILE_THREADS / 256);
+}
+
+// the next smaller list capacity to try when an allocation fails: 1022 -> 510 -> 254
+inline int smaller_list_cap(int want) { return (want / 2 - 1) & ~1; }
+
+// ---- trimmed slab messages -----------------------------------------------------------------
+// `most` records in the fullest message of any rank: back to the allocated size when that is
+// more than 4/5 of the active size
+inline int grown_active_records(long long most, int active, int capacity)
+{
+   const bool grow = most * SLAB_GROW_FILL_DEN > (long long)active * SLAB_GROW_FILL_NUM && active < capacity;
+   return grow ? capacity : active;
+}
+
+// one rank's wish for the message size: what it packed last with head room, at most what the
+// buffers hold, at least one record
+inline int trim_records(int most, float slack, int extra, int capacity)
+{
+   const double want_d = (double)most * (double)slack + (double)extra;
+   const int want = want_d > (double)capacity ? capacity : (int)want_d;
+   return want < 1 ? 1 : want;
+}
+
+// ---- slab plane ranges (local planes, 0 = the first plane held) -----------------------------
+struct PlaneRanges {
+   int own_lo, own_hi;   // owned planes
+   int sum_lo, sum_hi;   // density planes: one wider, clipped to what is held
+   int bnd_lo, bnd_hi;   // owned planes next to a neighbouring slab end / begin here
+};
+
+inline PlaneRanges plane_ranges(int plane_lo, int plane_hi, int z0, int nz, int halo, bool have_left,
+                                bool have_right)
+{
+   PlaneRanges r;
+   r.own_lo = plane_lo - z0;
+   r.own_hi = plane_hi - z0;
+   r.sum_lo = r.own_lo - 1 < 0 ? 0 : r.own_lo - 1;
+   r.sum_hi = r.own_hi + 1 > nz ? nz : r.own_hi + 1;
+   // owned planes next to a neighbouring slab, one wider than the halo (early exchange): a
+   // particle further inside cannot reach the planes that are sent within one step
+   const int border = halo + 1;
+   r.bnd_lo = !have_left ? r.own_lo : (r.own_lo + border < r.own_hi ? r.own_lo + border : r.own_hi);
+   r.bnd_hi = !have_right ? r.own_hi : (r.own_hi - border > r.own_lo ? r.own_hi - border : r.own_lo);
+   return r;
+}
+
+// ---- timing --------------------------------------------------------------------------------
+// Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
+// slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary
+// with no launch before it shares the previous boundary's event: FULL mode has no separate
+// neighbour search, and computePressure is a no-op in the reference (src/sph.cpp:253-263).
+inline int phase_event(bool full_mode, int k)
+{
+   if (k == 4) return 3;
+   if (k == 2 && full_mode) return 1;
+   return k;
+}
+
+// whether a step at timing `level` records the event of boundary k (SUMS: the interval 1 .. 5)
+inline bool records_boundary(int level, bool full_mode, int k)
+{
+   if (level == SPH_HIP_TIMING_PHASES) return phase_event(full_mode, k) == k;
+   return level == SPH_HIP_TIMING_SUMS && (k == 1 || k == 5);
+}
+
+// Which events the step about to be enqueued records: `level` on every stride-th timed step,
+// nothing on the others (an event record is a barrier packet of ~10 us on the stream: sampling
+// keeps the measurement from weighing on what it measures).  `seen` counts the timed steps.
+inline int next_step_level(bool timed, int level, long long& seen, int stride)
+{
+   if (!timed || level == SPH_HIP_TIMING_OFF) return SPH_HIP_TIMING_OFF;
+   const bool sample = (seen++ % stride) == 0;
+   return sample ? level : SPH_HIP_TIMING_OFF;
+}

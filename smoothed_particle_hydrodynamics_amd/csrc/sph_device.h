@@ -1,4 +1,4 @@
-// Shared device-side helpers and the context layout of the gfx950 SPH step.
+// Shared device-side helpers and types of the gfx950 SPH step (the context: context.h).
 // Written for MI355X only: wave = 64 lanes, no other targets, no compatibility paths.
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/sph_hip.h"
+#include "launch_policy.h"
 
 #define SPH_WAVE 64
 #define EV_RING 128
@@ -60,24 +61,8 @@ struct SlabZone {
    int early;           // the previous step packed its messages early: check nothing was missed
 };
 
-// Per-step statistics of the LDS tiles (k_tile_desc), fed back to the host's choice of tile
-// capacity: how many workgroups would not fit each candidate capacity.
-#define TILE_CANDS 12
 // density pass: widening of h2 for the fused screening test (csrc/full_tiled.h, "TEST screens")
 #define TEST_SCREEN_FACTOR 1.000002f
-// particles (= threads) of one workgroup of the tiled FULL-mode passes
-#ifndef TILE_THREADS
-#define TILE_THREADS 256
-#endif
-enum {
-   TSTAT_OVER = 0,            // [TILE_CANDS] workgroups whose tile exceeds candidate i
-   TSTAT_BLOCKS = 12,         // workgroups counted
-   TSTAT_MAX = 13,            // largest tile
-   TSTAT_GIVEUP_DENSITY = 14, // entries of the give-up lists of the current step
-   TSTAT_GIVEUP_ACCEL = 15,
-   TSTAT_NO_LIST = 16,        // particles with more neighbours than their list holds (density pass)
-   TSTAT_COUNT = 17
-};
 // The rest of the step, done by the acceleration pass itself (a context that holds the whole
 // grid and exchanges with nobody): every particle is integrated where its acceleration was just
 // computed - into the state buffers the cell build left free, the neighbours still read the old
@@ -105,14 +90,6 @@ struct FusedStep {
    int msg_capacity;
    int32_t* meta;           // error bits
 };
-struct TileCaps {
-   int cand[TILE_CANDS];    // ascending candidate capacities (the occupancy levels of both kernels)
-   int n_cand;
-   int cap_density;         // capacities the current step's launches use
-   int cap_accel;
-   int wide;                // list entries carry a 14-bit tile index (a capacity above 4064)
-};
-
 #define SPH_DEAD_ID 0xffffffffu
 
 // Constants of the per-pair arithmetic, by value in kernarg (scalar registers).
@@ -136,122 +113,6 @@ struct PairConsts {
    // tolerance mode, no point mass (central_mass == 0, softening > 0): the point-mass terms of
    // computeAcceleration / integrate (src/sph.cpp:892-915, 966-989) are +-0 and are skipped
    int skip_point_mass;
-};
-
-struct sph_hip_context {
-   sph_hip_params prm;
-   int mode = 0;
-   int device = 0;
-   int capacity = 0;
-   int n = 0;       // host upper bound of resident entries (owned + ghosts + dead)
-   int n_owned = 0; // owned particles at the last upload / count query
-   int32_t* meta = nullptr; // META_* (device)
-   // slab (FULL mode): owned global z-planes [plane_lo, plane_hi), halo planes on each side
-   int plane_lo = 0, plane_hi = 0, halo = 0;
-   hipStream_t stream = nullptr;     // the stream every launch goes to
-   hipStream_t own_stream = nullptr; // created with the context; `stream` may be redirected
-   // per-phase event ring: EV_RING steps x 7 events; `ev_steps` counts timed steps since the
-   // last reset (phase totals cover the last min(ev_steps, EV_RING) of them)
-   hipEvent_t* ev = nullptr;
-   long long ev_steps = 0;
-   std::string err;
-
-   CellGrid grid;
-
-   // particle state: {x,y,z,m} and {vx,vy,vz,id-bits}.  FULL mode keeps it cell-sorted and
-   // ping-pongs between the two buffers at every cell build; REF mode keeps it in index order
-   // in buffer 0.
-   float4* posm[2] = {nullptr, nullptr};
-   float4* velp[2] = {nullptr, nullptr};
-   int cur = 0;
-
-   // cell build
-   uint32_t* key = nullptr;        // cell id per particle
-   uint32_t* slot = nullptr;       // arrival rank inside the cell (from the counting atomic)
-   uint32_t* perm = nullptr;       // cell-sorted, arbitrary order inside a cell
-   uint32_t* order = nullptr;      // REF: cell-sorted, ascending index inside a cell
-   uint32_t* cell_count = nullptr; // ncells
-   uint32_t* cell_start = nullptr; // ncells + 1
-   uint32_t* scan_part = nullptr;  // per-tile partial sums of the scan
-   uint32_t* big_cells = nullptr;  // [0] = count, then the cells with more than RANK_BIG members
-   int scan_tiles = 0;
-
-   // sums
-   float* rho = nullptr;
-   float4* velB = nullptr; // per particle {vx, vy, vz, B = p_j * rhojInv^2}: the acceleration gather
-   float* auxc = nullptr;  // per particle C = (rhojInv * m_j) * k3 (FAST: m_j * B): staged in the acceleration tile
-   float4* acc = nullptr; // {ax, ay, az, unused}
-   int32_t* ncount = nullptr;
-   struct TileDesc* tile_desc = nullptr; // per 256-particle workgroup: LDS tile layout
-   uint32_t* nlist = nullptr;            // neighbour lists density pass -> acceleration pass
-   uint32_t* nlist_overflow = nullptr;   // per workgroup: 1 = tile or a list did not fit
-   int fast = 0;                   // tolerance-mode pair arithmetic (SPH_HIP_MODE_FULL_FAST / sph_hip_set_arithmetic)
-   int uniform_mass = 0;           // every resident particle has bit-identical mass
-   int use_tiled = 1;              // FULL mode: LDS-tiled kernels (0 = untiled everywhere)
-   int prehashed = 0;              // the last integrate also did the next build's cell hash + counts
-                                   // (2: a slab's fused step - owned entries only, see k_hash_tail)
-   int no_prehash = 0, no_fused_integrate = 0, no_fused_slab = 0;   // SPH_HIP_NO_* switches, read at creation
-   hipStream_t chunk_stream = nullptr;          // k_full_density_chunked runs beside the tiled density pass
-   hipEvent_t ev_chunk_fork = nullptr, ev_chunk_join = nullptr;
-   int chunked_giveups = -1;       // SPH_HIP_CHUNKED: 1 always / 0 never launch k_full_density_chunked (-1: by count)
-   int slab_fused = 0;             // the step in progress (step_begin .. step_end) is fused
-   void* slab_msgs[2] = {nullptr, nullptr};   // its message buffers
-   int slab_msg_capacity = 0;
-   int had_exchange = 0;           // pack/unpack/step_begin were used on this context: never prehash
-   int may_hold_dead = 0;          // sph_hip_slab_pack has marked entries dead since the last cell build
-   int early_exchange = 0;         // the last step packed its messages early (sph_hip_slab_step_begin)
-   struct SlabComm* comm = nullptr;     // native RCCL exchange (csrc/slab_rccl.h), or null
-   hipStream_t border_stream = nullptr; // stream the last step_begin put the border work on
-   hipEvent_t ev_density = nullptr; // early exchange: density done (main stream) -> border work may start
-   hipEvent_t ev_border = nullptr;  //                 border acceleration done (exchange stream) -> integrate may run
-   hipEvent_t ev_pace[2] = {nullptr, nullptr};  // recorded every PACE_STEPS steps (see pace_host)
-   long long steps_enqueued = 0;
-   int timing_level = 2;           // SPH_HIP_TIMING_*: which events sph_hip_step() records
-   int timing_stride = 1;          // ... on every timing_stride-th step only (sph_hip_set_timing_stride)
-   long long timing_seen = 0;      // timed steps since the stride was set
-   int slab_step_level = 0;        // level sph_hip_slab_step_begin chose for the step in progress
-   // LDS tile capacity of the two tiled kernels: chosen per launch among the largest tiles that
-   // still allow B workgroups per CU (levels, ascending), from the tile size recent steps needed
-   // (tile_feedback: pinned host word the density kernel stores into; 0 = nothing known yet)
-   int* tile_feedback = nullptr;   // TSTAT_COUNT ints, pinned host memory
-   int32_t* tile_stats = nullptr;  // TSTAT_* of the current step (device)
-   uint32_t* giveup_density = nullptr; // workgroups whose tile exceeds the density capacity
-   uint32_t* giveup_accel = nullptr;   // ... or the acceleration capacity
-   int tile_cap_forced = 0;        // SPH_HIP_TILE_CAP: fixed capacity for both kernels (tests)
-   int list_cap = 0;               // neighbours per particle the lists hold (even)
-   int list_cap_max = 0;           // how far the host may enlarge them (SPH_HIP_LIST_CAP pins both)
-   size_t list_blocks = 0;         // workgroup blocks the list allocation covers
-   int density_levels[TILE_CANDS] = {0}, n_density_levels = 0;
-   int accel_levels[TILE_CANDS] = {0}, n_accel_levels = 0;
-   int density_per_cu[TILE_CANDS] = {0}, accel_per_cu[TILE_CANDS] = {0};  // workgroups per CU at each level
-   TileCaps caps = {};             // candidate capacities + the two chosen for the current step
-   int cand_kept[TILE_CANDS] = {0}, n_cand_kept = 0;   // the candidate list tile_feedback's counts belong to
-
-   // REF-mode lists
-   int32_t* vox = nullptr; // 3 ints per particle
-   uint32_t* nb = nullptr;
-   float* nd = nullptr;
-
-   // reductions
-   double* epart = nullptr; // 2 * blocks partial sums, then [0],[1] totals
-   int eblocks = 0;
-   int energy_blocks = 0;   // partials written by the last integrate (0 = none yet)
-   int32_t* stats = nullptr; // sum(lo,hi), max, min
-
-   // error word of the slab exchange as last copied to the host (pinned; sph_hip_slab_poll_errors)
-   volatile int32_t* err_watch = nullptr;
-   hipEvent_t watch_event = nullptr;  // behind the last requested copy of the error word
-   int watch_pending = 0;
-
-   // asynchronous host mirror (sph_hip_download_async): its own device staging, copy stream and events
-   float* mirror_stage = nullptr;     // capacity * 11 floats + voxel counts
-   hipStream_t copy_stream = nullptr;
-   hipEvent_t ev_exported = nullptr;  // compute stream: the mirror staging is complete
-   hipEvent_t ev_copied = nullptr;    // copy stream: it has reached the host
-   int mirror_busy = 0;               // a copy has been started and not yet been seen complete
-
-   // staging for host <-> device in the reference's interleaved layouts
-   float* stage = nullptr; // capacity * 11 floats
 };
 
 // ---- arithmetic helpers -----------------------------------------------------------------

@@ -1,6 +1,6 @@
 """What a workgroup per CU is worth to each pair kernel: the 4M column stepped with the LDS tile
 capacity of ONE pass pinned to each capacity level (the other pass at its usual one), one process per
-setting, on one box.  Feeds density_thr / accel_thr in csrc/sph_hip.hip (pick_tile_caps).
+setting, on one box.  Feeds DENSITY_THR / ACCEL_THR in csrc/launch_policy.h.
     python tools/occupancy_prices.py            (SPH_HIP_ARITH=fast for the tolerance-mode kernels)"""
 import os
 import subprocess
