@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SPH_HIP_ABI_VERSION 6
+#define SPH_HIP_ABI_VERSION 7
 /* The ABI version the loaded library was built with (compare with SPH_HIP_ABI_VERSION of the
  * header the host was compiled against before calling anything else).  A library built with
  * profiling hooks that cut pieces out of the kernels (diagnostic builds: results are garbage by
@@ -269,6 +269,38 @@ int sph_hip_download_grid_counts(sph_hip_context* ctx, int32_t* counts);
 /* REF mode only: mNeighbors / mNeighborDistancesScaled, n*examine_count entries each
  * (reference src/sph.cpp:112-113). */
 int sph_hip_download_neighbor_lists(sph_hip_context* ctx, uint32_t* neighbors, float* distances);
+
+/* ---- field sampler ----------------------------------------------------------------------- */
+
+/* SPH interpolation of the CURRENT state (positions, masses, velocities; never the densities of
+ * the last step) at probe points, FULL and FULL_FAST contexts that hold the whole grid (identical
+ * results in both arithmetics).  For a probe x, over every live particle j:
+ *   member  d2 = (dx*dx + dy*dy) + dz*dz < h2 in fp32, dx = x.x - x_j.x etc. - the density
+ *           pass's test, but NO particle is excluded: a probe placed on a particle includes that
+ *           particle's own term (unlike computeDensity, reference src/sph.cpp:737);
+ *   term    t_j = m_j * (kernel1 * (hscaled2 - d*d)^3), d = sqrtf(d2) * sim_scale - the density
+ *           pass's arithmetic, including its range test on d where the scale is not unit;
+ *   density sum of t_j in fp32, in canonical order: ascending FULL cell id, then ascending index;
+ *   velocity (sum of t_j * v_j, per component, unfused, same order) / density if density > 0,
+ *           else 0 (Shepard-normalised);
+ *   count   the number of members.
+ * A non-finite or out-of-box probe needs no special case: its cell is the cell build's clamped
+ * one, and a NaN or infinite d2 is never a member - such a probe gives density 0, count 0 and
+ * velocity 0.
+ * Each call first brings the cell structure up to date (the build sph_hip_voxelize runs).  A call
+ * does not change the simulation: sph_hip_download returns the same bytes before and after it,
+ * and every later step is bit-identical to one without it.  Any output may be NULL (with all of
+ * them NULL the probes are still evaluated: timing); arrays are host memory; the call
+ * synchronises.  SPH_HIP_ERR_INVALID for a REF context, a slab context (sph_hip_create_slab with
+ * neighbours, or one that has exchanged), n < 0, dims <= 0, a non-finite origin, a non-finite or
+ * non-positive spacing, and a lattice of more than 2^31 - 1 points.  n == 0 does nothing. */
+/* n probes, xyz interleaved; density[n], velocity_xyz[3n], count[n] */
+int sph_hip_sample_points(sph_hip_context* ctx, int n, const float* xyz,
+                          float* density, float* velocity_xyz, int32_t* count);
+/* The lattice origin + (float)i * spacing per axis (fp32, unfused), i in [0, dims).
+ * Out index (k*dims[1] + j)*dims[0] + i, x fastest like the cell ids. */
+int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                           const int32_t dims[3], float* density, float* velocity_xyz, int32_t* count);
 
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *

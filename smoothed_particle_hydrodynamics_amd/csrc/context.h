@@ -17,6 +17,7 @@
 #include "full_kernels.h"
 #include "full_tiled.h"
 #include "ref_kernels.h"
+#include "sample_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
 
@@ -244,6 +245,12 @@ struct sph_hip_context {
 
    // staging for host <-> device in the reference's interleaved layouts
    DevBuf<float> stage; // capacity * 11 floats
+
+   // field sampler (sph_hip_sample_points / _lattice): probes and outputs of one chunk, grown on demand
+   DevBuf<float> sample_buf;
+   size_t sample_words = 0;
+   int sample_route = 0;           // SAMPLE_ROUTE_*: SPH_HIP_SAMPLE_UNTILED=1 / SPH_HIP_SAMPLE_TILED=1 (tests, A/B runs)
+   int sample_lds_set = 0;         // the tiled lattice kernels may take their dynamic LDS on this device
 };
 
 namespace {
@@ -293,6 +300,9 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    ctx->no_fused_integrate = getenv_flag("SPH_HIP_NO_FUSED_INTEGRATE");
    ctx->no_fused_slab = getenv_flag("SPH_HIP_NO_FUSED_SLAB");
    if (const char* v = getenv("SPH_HIP_CHUNKED")) ctx->chunked_giveups = v[0] == '1' ? 1 : 0;   // default: by count
+   ctx->sample_route = getenv_flag("SPH_HIP_SAMPLE_UNTILED") ? SAMPLE_ROUTE_UNTILED
+                       : getenv_flag("SPH_HIP_SAMPLE_TILED")  ? SAMPLE_ROUTE_TILED
+                                                              : SAMPLE_ROUTE_DEFAULT;
    ctx->device = device;
    ctx->capacity = capacity;
 

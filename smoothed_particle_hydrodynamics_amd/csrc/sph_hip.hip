@@ -34,6 +34,40 @@ __global__ void k_selftest_sqrt(unsigned long long* __restrict__ out)
    }
 }
 
+
+// ---- field sampler (sample_kernels.h; decisions: sample_policy.h) ---------------------------------
+
+// Sampling reads a whole-grid FULL-mode state; a slab holds part of the grid and ghosts besides.
+int sample_check(sph_hip_context* ctx, const char* who)
+{
+   if (ctx->mode != SPH_HIP_MODE_FULL) {
+      ctx->err = std::string(who) + ": FULL and FULL_FAST contexts only";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange) {
+      ctx->err = std::string(who) + ": slab contexts (with neighbours, or that have exchanged) cannot be sampled";
+      return SPH_HIP_ERR_INVALID;
+   }
+   return SPH_HIP_OK;
+}
+
+// the chunk scratch, grown on demand (the old one is released once the stream is idle)
+int sample_scratch(sph_hip_context* ctx, size_t words)
+{
+   if (words <= ctx->sample_words) return SPH_HIP_OK;
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   ctx->sample_buf.reset();
+   ctx->sample_words = 0;
+   SPH_TRY(dev_alloc(ctx->sample_buf, words));
+   ctx->sample_words = words;
+   return SPH_HIP_OK;
+}
+
+// Bring the cell structure up to date with the current positions: the build sph_hip_voxelize runs,
+// which consumes a pending prehash and moves the last sums with the particles, so that nothing a
+// caller can read or a later step computes changes.
+int sample_prepare(sph_hip_context* ctx) { return launch_cell_build(ctx, nullptr, nullptr, true); }
+
 } // namespace
 
 extern "C" {
@@ -910,6 +944,160 @@ int sph_hip_download_neighbor_lists(sph_hip_context* ctx, uint32_t* neighbors, f
       SPH_TRY(hipMemcpyAsync(distances, ctx->nd, sizeof(float) * m, hipMemcpyDeviceToHost,
                              ctx->stream));
    SPH_TRY(hipStreamSynchronize(ctx->stream));
+   return SPH_HIP_OK;
+}
+
+// ---- field sampler --------------------------------------------------------------------------------
+
+int sph_hip_sample_points(sph_hip_context* ctx, int n, const float* xyz, float* density, float* velocity_xyz,
+                          int32_t* count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (n < 0 || (n > 0 && !xyz)) {
+      ctx->err = "sph_hip_sample_points: negative count or null probe array";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if ((rc = sample_check(ctx, "sph_hip_sample_points"))) return rc;
+   if (n == 0) return SPH_HIP_OK;
+   if (ctx->n == 0) {
+      // nothing resident (the cell arrays may still describe an earlier upload)
+      if (density) memset(density, 0, sizeof(float) * (size_t)n);
+      if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * (size_t)n);
+      if (count) memset(count, 0, sizeof(int32_t) * (size_t)n);
+      return SPH_HIP_OK;
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS);
+   if ((rc = sample_scratch(ctx, (size_t)chunk * 8))) return rc;
+   float* sxyz = ctx->sample_buf;
+   float* srho = sxyz + 3 * (size_t)chunk;
+   float* svel = srho + (size_t)chunk;
+   int32_t* scnt = reinterpret_cast<int32_t*>(svel + 3 * (size_t)chunk);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   hipStream_t st = ctx->stream;
+   for (int p0 = 0; p0 < n; p0 += chunk) {
+      const int m = n - p0 < chunk ? n - p0 : chunk;
+      SPH_TRY(hipMemcpyAsync(sxyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+      bind_flags([&](auto U, auto V) {
+         hipLaunchKernelGGL((k_sample_points<U.value, V.value>), dim3(div_up(m, 256)), dim3(256), 0, st, sxyz, m,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid, k, srho, svel,
+                            scnt);
+      }, unit_scale(ctx->prm), velocity_xyz != nullptr);
+      SPH_TRY(hipGetLastError());
+      if (density) SPH_TRY(hipMemcpyAsync(density + p0, srho, sizeof(float) * m, hipMemcpyDeviceToHost, st));
+      if (velocity_xyz)
+         SPH_TRY(hipMemcpyAsync(velocity_xyz + 3 * (size_t)p0, svel, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
+      if (count) SPH_TRY(hipMemcpyAsync(count + p0, scnt, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+   }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3], const int32_t dims[3],
+                           float* density, float* velocity_xyz, int32_t* count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!origin || !spacing || !dims) {
+      ctx->err = "sph_hip_sample_lattice: null origin, spacing or dims";
+      return SPH_HIP_ERR_INVALID;
+   }
+   long long total = 1;
+   for (int a = 0; a < 3; a++) {
+      if (dims[a] <= 0 || !std::isfinite(origin[a]) || !std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) {
+         ctx->err = "sph_hip_sample_lattice: dims must be positive, the origin finite, the spacing finite and positive";
+         return SPH_HIP_ERR_INVALID;
+      }
+      total *= dims[a];
+      if (total > 0x7fffffffll) {
+         ctx->err = "sph_hip_sample_lattice: more than 2^31 - 1 lattice points";
+         return SPH_HIP_ERR_INVALID;
+      }
+   }
+   if ((rc = sample_check(ctx, "sph_hip_sample_lattice"))) return rc;
+   if (ctx->n == 0) {
+      if (density) memset(density, 0, sizeof(float) * (size_t)total);
+      if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * (size_t)total);
+      if (count) memset(count, 0, sizeof(int32_t) * (size_t)total);
+      return SPH_HIP_OK;
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   const double cells[3] = {spacing[0] * (double)ctx->grid.inv, spacing[1] * (double)ctx->grid.inv,
+                            spacing[2] * (double)ctx->grid.inv};
+   const SampleBrick brick = sample_brick(dims, cells);
+   const bool tiled = sample_use_tiled(brick, dims, cells, SAMPLE_TILE_CAP, ctx->sample_route);
+   if (tiled && !ctx->sample_lds_set) {
+      // (the attribute belongs to the function on the current device: set once per context)
+      for (int m = 0; m < 4; m++)
+         bind_flags([&](auto U, auto V) {
+            (void)hipFuncSetAttribute((const void*)(k_sample_lattice<U.value, V.value, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      SAMPLE_TILE_CAP * SAMPLE_TILE_BYTES_VELOCITY);
+         }, (m & 1) != 0, (m & 2) != 0);
+      (void)hipGetLastError();
+      ctx->sample_lds_set = 1;
+   }
+   const bool vel = velocity_xyz != nullptr;
+   const size_t lds = tiled ? (size_t)SAMPLE_TILE_CAP *
+                                  (vel ? SAMPLE_TILE_BYTES_VELOCITY : SAMPLE_TILE_BYTES_DENSITY) : 0;
+   const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
+   const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
+   if ((rc = sample_scratch(ctx, chunk_points * 5))) return rc;
+   float* srho = ctx->sample_buf;
+   float* svel = srho + chunk_points;
+   int32_t* scnt = reinterpret_cast<int32_t*>(svel + 3 * chunk_points);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const bool unit = unit_scale(ctx->prm);
+   hipStream_t st = ctx->stream;
+   SampleLattice L;
+   L.ox = origin[0];
+   L.oy = origin[1];
+   L.oz = origin[2];
+   L.sx = spacing[0];
+   L.sy = spacing[1];
+   L.sz = spacing[2];
+   L.bx = brick.bx;
+   L.by = brick.by;
+   L.bz = brick.bz;
+   // a chunk's outputs are a box of the caller's arrays: one copy per z-plane and array, or one for
+   // the lot when the chunk spans whole planes
+   auto copy_out = [&](void* dst, const void* src, size_t elem) -> hipError_t {
+      char* d = (char*)dst;
+      const char* s = (const char*)src;
+      const size_t plane = (size_t)dims[0] * dims[1];
+      if (L.ex == dims[0] && L.ey == dims[1])
+         return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem,
+                               hipMemcpyDeviceToHost, st);
+      for (int z = 0; z < L.ez; z++) {
+         const hipError_t e = hipMemcpy2DAsync(
+             d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
+             s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
+             hipMemcpyDeviceToHost, st);
+         if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
+   };
+   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += c.ez)
+      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += c.ey)
+         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += c.ex) {
+            L.ex = dims[0] - L.i0 < c.ex ? dims[0] - L.i0 : c.ex;
+            L.ey = dims[1] - L.j0 < c.ey ? dims[1] - L.j0 : c.ey;
+            L.ez = dims[2] - L.k0 < c.ez ? dims[2] - L.k0 : c.ez;
+            L.bricks_x = div_up(L.ex, L.bx);
+            L.bricks_y = div_up(L.ey, L.by);
+            const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
+            bind_flags([&](auto U, auto V, auto T) {
+               hipLaunchKernelGGL((k_sample_lattice<U.value, V.value, T.value>), dim3(bricks), dim3(SAMPLE_THREADS),
+                                  lds, st, L, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid,
+                                  k, SAMPLE_TILE_CAP, srho, svel, scnt);
+            }, unit, vel, tiled);
+            SPH_TRY(hipGetLastError());
+            if (density) SPH_TRY(copy_out(density, srho, sizeof(float)));
+            if (velocity_xyz) SPH_TRY(copy_out(velocity_xyz, svel, 3 * sizeof(float)));
+            if (count) SPH_TRY(copy_out(count, scnt, sizeof(int32_t)));
+         }
+   SPH_TRY(hipStreamSynchronize(st));
    return SPH_HIP_OK;
 }
 

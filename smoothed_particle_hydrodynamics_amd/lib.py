@@ -93,6 +93,9 @@ PROTOTYPES = {
     "sph_hip_download_voxels": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "sph_hip_download_grid_counts": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_download_neighbor_lists": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
+    "sph_hip_sample_points": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_sample_lattice": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3),
+                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -120,7 +123,7 @@ PROTOTYPES = {
     "sph_hip_abi_version": (C.c_int, []),
     "sph_hip_selftest_sqrt": (C.c_int, [C.c_int, _P(C.c_uint64), _P(C.c_uint32)]),
 }
-ABI_VERSION = 6   # SPH_HIP_ABI_VERSION of the include/sph_hip.h these prototypes mirror
+ABI_VERSION = 7   # SPH_HIP_ABI_VERSION of the include/sph_hip.h these prototypes mirror
 
 _LIB = None
 

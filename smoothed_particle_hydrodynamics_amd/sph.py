@@ -267,6 +267,41 @@ class SPH:
         self._check(self._lib.sph_hip_integrate(self._ctx), "sph_hip_integrate")
         self._mirror_fresh = False
 
+    # ---- field sampler (sph_hip_sample_points / sph_hip_sample_lattice) ---------------------------
+    def sampleFields(self, points, velocity=True):
+        """SPH interpolation of the current state at `points` ((n, 3) float32): (density[n],
+        velocity[n, 3] or None, count[n]) as numpy arrays.  The probe sums every particle within h,
+        its own included where a probe sits on one (include/sph_hip.h: field sampler); the
+        simulation is not changed by the call."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        rho = np.zeros(n, np.float32)
+        vel = np.zeros((n, 3), np.float32) if velocity else None
+        cnt = np.zeros(n, np.int32)
+        self._check(self._lib.sph_hip_sample_points(self._ctx, n, _ptr(pts), _ptr(rho), _ptr(vel), _ptr(cnt)),
+                    "sph_hip_sample_points")
+        return rho, vel, cnt
+
+    def sampleLattice(self, origin, spacing, shape, velocity=True):
+        """The same sums on the lattice origin + i * spacing (fp32, per axis), shape = (nx, ny, nz):
+        (density[nz, ny, nx], velocity[nz, ny, nx, 3] or None, count[nz, ny, nx])."""
+        o = (C.c_float * 3)(*[float(v) for v in origin])
+        s = (C.c_float * 3)(*[float(v) for v in spacing])
+        dims = [int(v) for v in shape]
+        if len(dims) != 3 or len(o) != 3 or len(s) != 3:
+            raise ValueError("origin, spacing and shape take three values each")
+        d = (C.c_int32 * 3)(*dims)
+        grid = (max(dims[2], 0), max(dims[1], 0), max(dims[0], 0))
+        total = grid[0] * grid[1] * grid[2]
+        if total >= 2 ** 31:
+            raise ValueError("a lattice of more than 2^31 - 1 points")
+        rho = np.zeros(grid, np.float32)
+        vel = np.zeros(grid + (3,), np.float32) if velocity else None
+        cnt = np.zeros(grid, np.int32)
+        self._check(self._lib.sph_hip_sample_lattice(self._ctx, C.byref(o), C.byref(s), C.byref(d), _ptr(rho),
+                                                     _ptr(vel), _ptr(cnt)), "sph_hip_sample_lattice")
+        return rho, vel, cnt
+
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
         """The six numbers of SPH::updateElapsed (reference src/sph.cpp:292-299), in ms."""
