@@ -62,8 +62,9 @@ __device__ __forceinline__ void integrate_particle(const PairConsts& k, float4& 
    const float ny0 = x.y + (vhy * pos_dt);
    const float nz0 = x.z + (vhz * pos_dt);
 
-   // (k.skip_point_mass: tolerance mode without a point mass - the term is +-0, see accel_end; d3 then
-   // only divides a potential energy of exactly zero)
+   // (k.skip_point_mass: tolerance mode without a point mass - the term is +-0 or NaN, see
+   // point_mass_nan; d3 then only divides a potential energy of exactly zero, or one of a particle
+   // whose new velocity is NaN and whose energy terms are not summed)
    float agx = 0.0f, agy = 0.0f, agz = 0.0f, d3 = 1.0f;
    if (!k.skip_point_mass) {
       float rsx = (nx0 - k.cx), rsy = (ny0 - k.cy), rsz = (nz0 - k.cz);
@@ -81,7 +82,16 @@ __device__ __forceinline__ void integrate_particle(const PairConsts& k, float4& 
       agy = gm * (rsy / d3);
       agz = gm * (rsz / d3);
    } else {
-      agx = agy = agz = (nx0 - nx0) + (ny0 - ny0) + (nz0 - nz0);   // 0, or NaN where the term is: see accel_end
+      float rsx = (nx0 - k.cx), rsy = (ny0 - k.cy), rsz = (nz0 - k.cz);
+      if (!UNIT_SCALE) {
+         rsx *= k.sim_scale;
+         rsy *= k.sim_scale;
+         rsz *= k.sim_scale;
+      }
+      const float nan_any = point_mass_nan(rsx, rsy, rsz);   // 0, or NaN where the term is
+      agx = (rsx - rsx) + nan_any;
+      agy = (rsy - rsy) + nan_any;
+      agz = (rsz - rsz) + nan_any;
    }
    if (k.apply_gravity) { // extension, as in accel_end
       agx += k.gx;

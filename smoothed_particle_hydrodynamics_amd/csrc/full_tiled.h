@@ -1540,7 +1540,12 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       // (... and the lane itself as a neighbour must yield a FINITE factor, so that its r = 0 makes the
       // term vanish whatever the factor is: then a lane past its count needs no select on m B - a
       // compare and two selects per pair were 12 of the pair's ~140 issue cycles)
-      const float self_c = (k.hscaled * k.hscaled) * (s.pi_div_rhoi2 * xyzc[self_tile].w);
+      // (... and r = 0 needs a finite position of its own: a lane at x = +-inf takes dx = inf - inf =
+      // NaN from itself, which would make all three components of its sum NaN where the list-walking
+      // routes, and the reference, leave the other two alone - its x - x, 0 or NaN, rides in self_c)
+      const float4 self = xyzc[self_tile];
+      const float self_c = (k.hscaled * k.hscaled) * (s.pi_div_rhoi2 * self.w) +
+                           ((self.x - self.x) + (self.y - self.y) + (self.z - self.z));
       const bool odd_lane = __any(!__builtin_isfinite(s.pi_div_rhoi2) || !__builtin_isfinite(self_c));
       TRIP(TripCounters trips; trips.wave(TRIP_A_WAVES - 16, true); trips.lane(TRIP_A_CNT_L - 16, (unsigned)cnt);
            trips.lane(TRIP_A_LANES_L - 16, live ? 1u : 0u); trips.lane(TRIP_A_NV_L - 16, (unsigned)(cnt - first_v));)

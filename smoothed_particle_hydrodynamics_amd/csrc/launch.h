@@ -71,7 +71,8 @@ PairConsts pair_consts(const sph_hip_params& p, bool fast)
    k.max_z = p.max_z;
    k.apply_gravity = p.apply_gravity;
    k.apply_walls = p.apply_walls;
-   k.skip_point_mass = fast && p.central_mass == 0.0f && p.softening > 0.0f && std::isfinite(p.grav_const) ? 1 : 0;
+   k.skip_point_mass = fast && p.central_mass == 0.0f && p.softening >= 1.0e-12f && std::isfinite(p.grav_const) ? 1 : 0;
+   // (the softening bound: pair_math.h point_mass_nan)
    return k;
 }
 

@@ -255,10 +255,25 @@ __device__ __forceinline__ int visc_keep(float visc_scale)
    return m < 1.0f ? 1 : (int)m;
 }
 
+// The point-mass term gm * (rs / d3) of a scene without a point mass (gm = -G * 0, G finite), with
+// rs = (r - c) * sim_scale, dot = |rs| and d3 = (dot + softening)^3 as in reference src/sph.cpp:897-915
+// and 974-989 - componentwise what it comes to without the square root and the three divisions:
+//   * some rs NaN: dot, d3 and so every component NaN;
+//   * else a component whose own rs is +-inf: inf / d3 = inf / inf, NaN; the others rs / inf = +-0;
+//   * else +-0: d3 > 0 and rs / d3 finite, because the host sets k.skip_point_mass only for a
+//     softening of at least 1e-12 (d3 >= softening^3 is then a normal number and |rs / d3| <=
+//     1 / softening^2 < FLT_MAX) - rs / d3 = 0 where dot or d3 overflow.
+// A non-finite central position or sim_scale enters through rs, as in the reference.  Returns the
+// part every component shares: NaN or 0; a component adds (rs - rs) for its own part, 0 or NaN.
+__device__ __forceinline__ float point_mass_nan(float rsx, float rsy, float rsz)
+{
+   return (__builtin_isnan(rsx) || __builtin_isnan(rsy) || __builtin_isnan(rsz)) ? __builtin_nanf("") : 0.0f;
+}
+
 // reference src/sph.cpp:888-933.  k.skip_point_mass (tolerance mode only, set by the host): a scene
-// without a point mass (the dam-break: central_mass = 0, so every term of the block is +-0) skips
-// the term's square root and three divisions behind a uniform branch; the exact mode evaluates it
-// always (x + -0 keeps a -0 that x + +0 does not).
+// without a point mass (the dam-break: central_mass = 0, so every term of the block is +-0 or NaN,
+// point_mass_nan) skips the term's square root and three divisions behind a uniform branch; the
+// exact mode evaluates it always (x + -0 keeps a -0 that x + +0 does not).
 template <bool UNIT_SCALE>
 __device__ __forceinline__ float4 accel_end(const PairConsts& k, const AccelState& s)
 {
@@ -282,13 +297,16 @@ __device__ __forceinline__ float4 accel_end(const PairConsts& k, const AccelStat
    ay += gm * (rsy / d3);
    az += gm * (rsz / d3);
    } else {
-      // (... +-0 for a particle whose position is finite.  One that is not - a particle the reference has
-      // lost to a NaN two steps ago, seeded random scene 594 of the round-4 soak - gets NaN from the term,
-      // in all three components: x - x is 0 or NaN exactly when the term is.)
-      const float lost = (s.rx - s.rx) + (s.ry - s.ry) + (s.rz - s.rz);
-      ax += lost;
-      ay += lost;
-      az += lost;
+      float rsx = (s.rx - k.cx), rsy = (s.ry - k.cy), rsz = (s.rz - k.cz);
+      if (!UNIT_SCALE) {
+         rsx *= k.sim_scale;
+         rsy *= k.sim_scale;
+         rsz *= k.sim_scale;
+      }
+      const float nan_any = point_mass_nan(rsx, rsy, rsz);
+      ax += (rsx - rsx) + nan_any;
+      ay += (rsy - rsy) + nan_any;
+      az += (rsz - rsz) + nan_any;
    }
    if (k.apply_gravity) { // extension: uniform gravity enters next to the point-mass term
       ax += k.gx;

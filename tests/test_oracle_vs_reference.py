@@ -6,7 +6,7 @@ exact numbers).  test_oracle_golden.py carries more pins of the same kind."""
 import numpy as np
 import pytest
 
-from helpers import live_mask, pin_sha, reference_pins
+from helpers import NONFINITE_SCENES, live_mask, pin_sha, reference_pins
 
 CONSTANT_NAMES = ["h", "h2", "hscaled", "hscaled2", "hscaled6", "hscaled9", "htimes2", "htimes2inv",
                   "kernel1", "kernel2", "kernel3", "softening", "rho0", "stiffness", "viscosity",
@@ -153,3 +153,57 @@ def test_full_mode_against_reference_pair_functions(oracle, scale):
     energies = oracle.integrate(p, opos, ovel, oacc, mass)
     assert pin_sha(opos) == ref["pos"] and pin_sha(ovel) == ref["vel"]
     assert list(energies) == ref["energy"]
+
+
+@pytest.mark.parametrize("case", NONFINITE_SCENES)
+def test_full_mode_nonfinite_point_mass_term_against_reference(oracle, case):
+    """A scene without a point mass (central_mass = 0, the dam-break) where a position or the central
+    position is not finite: the term -G * 0 * (rs / d3) is NaN in a component whose rs is infinite and
+    in every component once one rs is NaN, +-0 elsewhere - the oracle (the tolerance mode's checker)
+    has that from the reference, through density, acceleration and the integration's second kick."""
+    from helpers import nonfinite_scene
+    p, pos, vel, mass = nonfinite_scene(case, oracle.params_for_h)
+    n = mass.size
+    cap = 128
+    nb, nd, cnt, worst = oracle.full_build_lists(p, pos, cap)
+    assert worst <= cap
+
+    def run(R):
+        R.configure(p, n)
+        R.set_state(pos, vel, mass)
+        R.set_lists(cap, nb, nd, cnt)
+        R.compute_density()
+        R.compute_acceleration()
+        s = R.get_state()
+        out = {"rho": s["rho"], "acc": s["acc"]}
+        R.integrate()
+        s = R.get_state()
+        out.update(pos=s["pos"], vel=s["vel"], energy=R.energy())
+        return out
+
+    ref = reference_pins("full_nonfinite_point_mass_" + case, run)
+    ids, cs, ci = oracle.full_cells(p, pos)
+    orho, ocnt = oracle.full_density(p, pos, mass, cs, ci)
+    oacc = oracle.full_accel(p, pos, vel, mass, orho, cs, ci)
+    assert np.array_equal(ocnt, cnt)
+    assert pin_sha(orho) == ref["rho"]
+    assert pin_sha(oacc) == ref["acc"]
+    opos, ovel = pos.copy(), vel.copy()
+    energies = oracle.integrate(p, opos, ovel, oacc, mass)
+    assert pin_sha(opos) == ref["pos"] and pin_sha(ovel) == ref["vel"]
+    assert list(energies) == ref["energy"]
+    acc = oacc.reshape(-1, 3)
+    if case == "particles":
+        # the NaN patterns the pins hold, spelled out
+        assert np.isnan(acc[10, 0]) and np.isfinite(acc[10, 1:]).all()
+        assert np.isnan(acc[20, 1]) and np.isfinite(acc[20, [0, 2]]).all()
+        assert np.isnan(acc[30, 2]) and np.isfinite(acc[30, :2]).all()
+        assert np.isnan(acc[40]).all() and np.isnan(acc[50]).all()
+        others = np.setdiff1d(np.arange(n), [10, 20, 30, 40, 50])
+        assert np.isfinite(acc[others]).all()
+    elif case == "central_x_inf":
+        # rs_x = -inf: x is inf / inf, y and z are finite / inf = 0
+        assert np.isnan(acc[:, 0]).all() and np.isfinite(acc[:, 1:]).all()
+    else:
+        # rs_z = NaN: dot and d3 are NaN, and so is every component
+        assert np.isnan(acc).all()
