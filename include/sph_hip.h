@@ -107,7 +107,7 @@ typedef struct sph_hip_params {
    float central_mass;                /* mCentralMass                                   */
    float central_pos[3];              /* mCentralPos                                    */
    float softening;                   /* mSoftening                                     */
-   int32_t examine_count;             /* mExamineCount (32)                             */
+   int32_t examine_count;             /* mExamineCount (32); REF mode: >= SPH_HIP_MIN_EXAMINE_COUNT */
    /* FULL-mode grid (no reference counterpart): cell edge >= h */
    int32_t full_cells_x, full_cells_y, full_cells_z;
    float full_cell_inv;
@@ -132,7 +132,12 @@ typedef struct sph_hip_context sph_hip_context;
 int sph_hip_params_default(sph_hip_params* out, float h, int cells_x, int cells_y, int cells_z);
 
 /* Replaces the allocations in SPH::SPH() (reference src/sph.cpp:100-113): device storage for
- * up to `capacity` particles on HIP device `device`. */
+ * up to `capacity` particles on HIP device `device`.  A REF-mode context needs examine_count >=
+ * SPH_HIP_MIN_EXAMINE_COUNT (else SPH_HIP_ERR_INVALID, with a last_error text): the search
+ * (reference src/sph.cpp:598-679) stores up to 4 neighbours per chunk of 8 candidates and stops
+ * once more than examine_count - 8 are stored, so it stores at most max(4, examine_count - 4)
+ * entries - past the end of a list of fewer than 4.  The reference does not check this. */
+#define SPH_HIP_MIN_EXAMINE_COUNT 4
 int sph_hip_create(sph_hip_context** out, const sph_hip_params* params, int capacity, int mode,
                    int device);
 void sph_hip_destroy(sph_hip_context* ctx);
@@ -141,7 +146,12 @@ void sph_hip_destroy(sph_hip_context* ctx);
 const char* sph_hip_last_error(const sph_hip_context* ctx);
 
 /* Replaces the six GUI setters + the constructor constants (reference src/sph.cpp:1219-1289).
- * Takes effect at the start of the next phase call; grid shape and h may not change. */
+ * Takes effect at the start of the next phase call; grid shape, h and examine_count may not
+ * change.  Like the reference, which forms every pressure inside computeAcceleration
+ * (src/sph.cpp:785, 829-834), an acceleration phase uses the constants set when it is called for
+ * the neighbours' pressure terms too: a FULL-mode context forms those terms in its density pass
+ * and, when rho0, stiffness, kernel3 or the arithmetic have changed since, forms them again
+ * before the acceleration pass (sph_hip_step never changes constants in the middle of a step). */
 int sph_hip_set_params(sph_hip_context* ctx, const sph_hip_params* params);
 int sph_hip_get_params(const sph_hip_context* ctx, sph_hip_params* out);
 

@@ -179,6 +179,13 @@ struct sph_hip_context {
    DevBuf<uint32_t> nlist;              // neighbour lists density pass -> acceleration pass
    DevBuf<uint32_t> nlist_overflow;     // per workgroup: 1 = tile or a list did not fit
    int fast = 0;                   // tolerance-mode pair arithmetic (SPH_HIP_MODE_FULL_FAST / sph_hip_set_arithmetic)
+   // what velB / auxc were last formed with (launch_density, k_neighbor_terms): the acceleration pass
+   // of a phase call whose constants differ (a setter in between) forms them again first
+   struct {
+      int valid = 0;               // 0: none formed yet, or the particles have moved since (keep_sums build)
+      int fast = 0;
+      float rho0 = 0.0f, stiffness = 0.0f, kernel3 = 0.0f;
+   } terms;
    int uniform_mass = 0;           // every resident particle has bit-identical mass
    int use_tiled = 1;              // FULL mode: LDS-tiled kernels (0 = untiled everywhere)
    int prehashed = 0;              // the last integrate also did the next build's cell hash + counts
@@ -272,6 +279,14 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    if (!out || !params || capacity < 1 ||
        (mode != SPH_HIP_MODE_REF && mode != SPH_HIP_MODE_FULL && mode != SPH_HIP_MODE_FULL_FAST)) {
       g_create_error = "sph_hip_create: invalid argument";
+      return SPH_HIP_ERR_INVALID;
+   }
+   // REF mode: the search stores up to 4 neighbours per chunk and stops once more than
+   // examine_count - 8 are stored (ref_kernels.h), so a list of fewer than 4 entries overflows in
+   // its first chunk
+   if (mode == SPH_HIP_MODE_REF && params->examine_count < SPH_HIP_MIN_EXAMINE_COUNT) {
+      g_create_error = "sph_hip_create: examine_count must be at least " +
+                       std::to_string(SPH_HIP_MIN_EXAMINE_COUNT) + " in REF mode (the search's largest chunk)";
       return SPH_HIP_ERR_INVALID;
    }
    // FULL with the tolerance-mode pair arithmetic (SPH_HIP_ARITH=fast: experiments run the tools

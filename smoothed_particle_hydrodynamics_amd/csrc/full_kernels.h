@@ -87,6 +87,24 @@ __device__ __forceinline__ void density_untiled(int p, const float4* __restrict_
    ncount[p] = count;
 }
 
+// The j-only factors of the last density pass formed again from its rho, for constants set since
+// (sph_hip_set_params between sph_hip_compute_density and sph_hip_compute_acceleration: the
+// reference forms them inside computeAcceleration) - what density_untiled writes, without the sums.
+// Not part of sph_hip_step.
+template <bool FAST>
+__global__ void __launch_bounds__(256)
+k_neighbor_terms(const float4* __restrict__ posm, const float4* __restrict__ velp,
+                 const float* __restrict__ rho, const int32_t* __restrict__ meta, PairConsts k,
+                 float4* __restrict__ velB, float* __restrict__ auxc)
+{
+   const int p = meta[META_SUM_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   if (p >= meta[META_SUM_END]) return;
+   const float2 bc = FAST ? neighbor_terms_fast(k, rho[p], posm[p].w) : neighbor_terms(k, rho[p], posm[p].w);
+   const float4 v = velp[p];
+   velB[p] = make_float4(v.x, v.y, v.z, FAST ? bc.y : bc.x);
+   auxc[p] = FAST ? bc.x : bc.y;
+}
+
 template <bool UNIT_SCALE, bool FAST>
 __global__ void __launch_bounds__(256)
 k_full_density(const float4* __restrict__ posm, const uint32_t* __restrict__ cell_start,

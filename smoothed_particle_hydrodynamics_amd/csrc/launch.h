@@ -301,6 +301,7 @@ int launch_cell_build(sph_hip_context* ctx, void* clear_left = nullptr, void* cl
                          ctx->perm, ctx->cell_start, ctx->posm[cur], ctx->velp[cur], ctx->posm[nxt],
                          ctx->velp[nxt], (uint32_t*)nullptr, scratch_key, scratch_src, remap);
       if (remap) {
+         ctx->terms.valid = 0;   // velB / auxc stay where they were: formed again if an acceleration pass follows
          // a build that is not followed by the sums: their last results move with the particles
          // (temporaries in the staging buffer behind k_rank_big's scratch; the float4 part 16-byte aligned)
          float4* acc_t = reinterpret_cast<float4*>(ctx->stage.get() + ((2 * (size_t)ctx->capacity + 3) & ~(size_t)3));
@@ -432,6 +433,36 @@ void launch_accel_lists(sph_hip_context* ctx, bool unit, int blocks, const PairC
    }, unit, ctx->uniform_mass != 0 || ctx->fast != 0, ctx->caps.wide != 0, ctx->fast != 0);
 }
 
+// FULL mode: the constants the j-only factors in velB / auxc were formed with (density pass)
+void note_neighbor_terms(sph_hip_context* ctx, const PairConsts& k)
+{
+   ctx->terms.valid = 1;
+   ctx->terms.fast = ctx->fast;
+   ctx->terms.rho0 = k.rho0;
+   ctx->terms.stiffness = k.stiffness;
+   ctx->terms.kernel3 = k.kernel3;
+}
+
+// Before an acceleration pass: the reference forms p_j / rho_j^2 and rho_j^-1 m_j k3 inside
+// computeAcceleration, with the constants of that call.  A density pass formed them here; if rho0,
+// stiffness, kernel3 or the arithmetic (which decides the layout) have been set since, or the
+// particles were moved by a stand-alone cell build, they are formed again from the density pass's
+// rho.  Never within sph_hip_step: its density and acceleration passes share one set of constants.
+void refresh_neighbor_terms(sph_hip_context* ctx, const PairConsts& k)
+{
+   const bool same = ctx->terms.valid && ctx->terms.fast == ctx->fast &&
+                     memcmp(&ctx->terms.rho0, &k.rho0, sizeof(float)) == 0 &&
+                     memcmp(&ctx->terms.stiffness, &k.stiffness, sizeof(float)) == 0 &&
+                     memcmp(&ctx->terms.kernel3, &k.kernel3, sizeof(float)) == 0;
+   if (same) return;
+   bind_flags([&](auto F) {
+      hipLaunchKernelGGL((k_neighbor_terms<F.value>), dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream,
+                         ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->rho, ctx->meta, k, ctx->velB,
+                         ctx->auxc);
+   }, ctx->fast != 0);
+   note_neighbor_terms(ctx, k);
+}
+
 int launch_density(sph_hip_context* ctx)
 {
    const int n = ctx->n;
@@ -452,6 +483,7 @@ int launch_density(sph_hip_context* ctx)
                                ctx->grid, k, ctx->rho, ctx->velB, ctx->auxc, ctx->ncount);
          }, unit, ctx->fast != 0);
       }
+      note_neighbor_terms(ctx, k);
    }
    SPH_TRY(hipGetLastError());
    return SPH_HIP_OK;
@@ -471,6 +503,7 @@ int launch_accel(sph_hip_context* ctx, int part = 0, hipStream_t part_stream = n
                          ctx->velp[0], ctx->rho, ctx->nb, ctx->nd, ctx->ncount, n,
                          ctx->prm.examine_count, k, ctx->acc);
    } else {
+      refresh_neighbor_terms(ctx, k);
       const bool unit = unit_scale(ctx->prm);
       if (ctx->use_tiled) {
          // same tiling (and tile descriptors) as the density pass of this step

@@ -137,6 +137,22 @@ def test_slab_thinner_than_its_halos_is_refused(hiplib):
             assert "2 * SPH_HIP_SLAB_HALO" in msg
 
 
+def test_ref_examine_count_below_the_search_chunk_is_refused(hiplib):
+    """A REF context whose lists hold fewer entries than the search stores in one chunk (4) is refused
+    before any device is touched: the stop rule (count > examine_count - 8, reference
+    src/sph.cpp:679) would let the first chunk write past the list.  The header states the bound."""
+    from smoothed_particle_hydrodynamics_amd.lib import default_params
+    text = open(os.path.join(ROOT, "include", "sph_hip.h")).read()
+    assert int(re.search(r"#define\s+SPH_HIP_MIN_EXAMINE_COUNT\s+(\d+)", text).group(1)) == 4
+    for cap in (3, 0, -8):
+        p = default_params(0.1, (8, 8, 8))
+        p.examine_count = cap
+        ctx = C.c_void_p()
+        assert hiplib.sph_hip_create(C.byref(ctx), C.byref(p), 1024, 0, 0) == -1, cap
+        assert not ctx
+        assert "examine_count must be at least 4" in hiplib.sph_hip_last_error(None).decode()
+
+
 def test_missing_library_is_loud(tmp_path):
     from smoothed_particle_hydrodynamics_amd.lib import SphHipError, load_library
     with pytest.raises(SphHipError, match="no CPU fallback"):

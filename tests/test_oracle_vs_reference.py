@@ -6,6 +6,7 @@ exact numbers).  test_oracle_golden.py carries more pins of the same kind."""
 import numpy as np
 import pytest
 
+import param_cases
 from helpers import NONFINITE_SCENES, live_mask, pin_sha, reference_pins
 
 CONSTANT_NAMES = ["h", "h2", "hscaled", "hscaled2", "hscaled6", "hscaled9", "htimes2", "htimes2inv",
@@ -207,3 +208,95 @@ def test_full_mode_nonfinite_point_mass_term_against_reference(oracle, case):
     else:
         # rs_z = NaN: dot and d3 are NaN, and so is every component
         assert np.isnan(acc).all()
+
+
+def _param_case_id(case):
+    return case.name
+
+
+@pytest.mark.parametrize("case", param_cases.CASES, ids=_param_case_id)
+def test_ref_steps_on_constant_cases(oracle, case):
+    """REF mode on every case of tests/param_cases.py: two whole SPH::step() calls of the reference
+    (its list size through ref_set_examine_count) against two oracle steps.  With the walls on, the
+    reference's own handleBoundaryConditions (defined, never called by step()) is applied after
+    each step: what the oracle's integration does in place."""
+    p, pos, vel, mass = param_cases.scene(oracle.params_for_h, case)
+    n = mass.size
+
+    def run(R):
+        R.configure(p, n)
+        R.set_state(pos, vel, mass)
+        out = {}
+        for s in range(2):
+            old = R.get_state()["pos"]
+            R.step()
+            st = R.get_state()
+            if p.apply_walls:
+                v, q = R.boundary(old, st["vel"], p.time_step, st["pos"])
+                R.set_state(q, v)
+                st["pos"], st["vel"] = q, v
+            for k in ("pos", "vel", "rho", "acc", "ncount"):
+                out["%s%d" % (k, s)] = st[k]
+            out["energy%d" % s] = R.energy()
+        return out
+
+    ref = reference_pins("param_case_ref_" + case.name, run)
+    opos, ovel = pos.copy(), vel.copy()
+    for s in range(2):
+        out = oracle.step(p, opos, ovel, mass, mode="ref")
+        for k, a in (("pos", opos), ("vel", ovel), ("rho", out["rho"]), ("acc", out["acc"]),
+                     ("ncount", out["ncount"])):
+            assert pin_sha(a) == ref["%s%d" % (k, s)], "%s step %d: %s" % (case.name, s, k)
+        assert [out["ke"], out["pe"]] == ref["energy%d" % s], "%s step %d: energy" % (case.name, s)
+    assert out["ncount"].max() <= case.overrides.get("examine_count", 32)
+
+
+@pytest.mark.parametrize("case", param_cases.FULL_CASES, ids=_param_case_id)
+def test_full_mode_on_constant_cases(oracle, case):
+    """FULL mode on every case of tests/param_cases.py, two steps: the oracle's lists fed to the
+    reference's computeDensity / computeAcceleration, then its integrate (and, with the walls on, its
+    handleBoundaryConditions), against the oracle's list-free FULL step."""
+    p, pos, vel, mass = param_cases.scene(oracle.params_for_h, case)
+    n = mass.size
+    cap = 256
+    lists = []
+    states = [(pos.copy(), vel.copy())]
+    opos, ovel = pos.copy(), vel.copy()
+    outs = []
+    for s in range(2):
+        nb, nd, cnt, worst = oracle.full_build_lists(p, opos, cap)
+        assert worst <= cap
+        lists.append((nb, nd, cnt))
+        outs.append(oracle.step(p, opos, ovel, mass, mode="full"))
+        assert np.array_equal(outs[-1]["ncount"], cnt)
+        states.append((opos.copy(), ovel.copy()))
+
+    def run(R):
+        R.configure(p, n)
+        R.set_state(pos, vel, mass)
+        out = {}
+        for s in range(2):
+            old = R.get_state()["pos"]
+            R.set_lists(cap, *lists[s])
+            R.compute_density()
+            R.compute_acceleration()
+            st = R.get_state()
+            out["rho%d" % s], out["acc%d" % s] = st["rho"], st["acc"]
+            R.integrate()
+            st = R.get_state()
+            if p.apply_walls:
+                v, q = R.boundary(old, st["vel"], p.time_step, st["pos"])
+                R.set_state(q, v)
+                st["pos"], st["vel"] = q, v
+            out["pos%d" % s], out["vel%d" % s] = st["pos"], st["vel"]
+            out["energy%d" % s] = R.energy()
+        return out
+
+    ref = reference_pins("param_case_full_" + case.name, run)
+    for s in range(2):
+        what = "%s step %d: " % (case.name, s)
+        assert pin_sha(outs[s]["rho"]) == ref["rho%d" % s], what + "rho"
+        assert pin_sha(outs[s]["acc"]) == ref["acc%d" % s], what + "acc"
+        assert pin_sha(states[s + 1][0]) == ref["pos%d" % s], what + "pos"
+        assert pin_sha(states[s + 1][1]) == ref["vel%d" % s], what + "vel"
+        assert [outs[s]["ke"], outs[s]["pe"]] == ref["energy%d" % s], what + "energy"
