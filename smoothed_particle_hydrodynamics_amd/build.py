@@ -10,7 +10,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["sph_hip.hip"]
-HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "full_tiled.h",
+HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "full_tiled.h", "neighbor_lists.h",
            "ref_kernels.h", "common_kernels.h", "slab_kernels.h", "slab_rccl.h", "launch_policy.h",
            "context.h", "launch.h", "slab_comm.h", "sample_kernels.h", "sample_policy.h",
            os.path.join("..", "..", "include", "sph_hip.h")]

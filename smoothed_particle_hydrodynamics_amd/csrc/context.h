@@ -177,7 +177,7 @@ struct sph_hip_context {
    DevBuf<int32_t> ncount;
    DevBuf<TileDesc> tile_desc;          // per 256-particle workgroup: LDS tile layout
    DevBuf<uint32_t> nlist;              // neighbour lists density pass -> acceleration pass
-   DevBuf<uint32_t> nlist_overflow;     // per workgroup: 1 = tile or a list did not fit
+   DevBuf<uint32_t> nlist_overflow;     // per workgroup: LISTS_ALL / LISTS_NONE / LISTS_SOME (neighbor_lists.h)
    int fast = 0;                   // tolerance-mode pair arithmetic (SPH_HIP_MODE_FULL_FAST / sph_hip_set_arithmetic)
    // what velB / auxc were last formed with (launch_density, k_neighbor_terms): the acceleration pass
    // of a phase call whose constants differ (a setter in between) forms them again first

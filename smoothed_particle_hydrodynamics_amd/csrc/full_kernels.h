@@ -138,10 +138,7 @@ __device__ __forceinline__ void accel_untiled(int p, const float4* __restrict__ 
    accel_begin(k, s, pi, velB[p], rho[p]);
    // FAST: the viscous sum visits the last visc_keep() neighbours only (ncount from the density pass)
    int first_v = 0, j = 0;
-   if (FAST) {
-      const int cnt = ncount[p], keep = visc_keep(s.visc_scale);
-      first_v = keep < cnt ? cnt - keep : 0;
-   }
+   if (FAST) first_v = visc_first(ncount[p], s.visc_scale);
 #pragma unroll 1
    for (int row = 0; row < 9; row++) {
       const uint32_t b = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]

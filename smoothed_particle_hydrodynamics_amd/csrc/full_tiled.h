@@ -21,11 +21,14 @@
 //
 // Workgroups whose tile would not fit (very dense regions) are flagged and run the untiled
 // code of full_kernels.h inline — same results, slower, no extra launch.
+// The neighbour lists the density pass leaves for the acceleration pass - their format, the append,
+// the per-workgroup flag - are neighbor_lists.h's.
 #pragma once
 
 #include "launch_policy.h"
 #include "common_kernels.h"
 #include "full_kernels.h"
+#include "neighbor_lists.h"
 #include "slab_kernels.h"
 
 // SPH_ABLATE=N cuts a piece out of a kernel so that tools/ablate.py can price it: such a build
@@ -100,143 +103,17 @@ __device__ unsigned int g_phase[2][PHASE_WGS][8];   // [kernel][workgroup][phase
 
 // The tile lives in dynamic LDS, its capacity chosen by the host per launch (launch_policy.h:
 // TILE_PAD, TILE_CAP_MAX, TILE_CAP_MAX_WIDE).
-#ifndef TILE_BATCH
-#define TILE_BATCH 8
-#endif
-// (TILE_BATCH: 16-byte loads a thread keeps in flight while filling the tile)
+constexpr int TILE_BATCH = 8;   // 16-byte loads a thread keeps in flight while filling the tile
 #define DENSITY_TILE_BYTES 12
 #define ACCEL_TILE_BYTES 16
 // launch bounds = the most workgroups per CU the register budget should allow
-#ifndef DENSITY_BLOCKS
-#define DENSITY_BLOCKS (6 * 256 / TILE_THREADS)
-#endif
-#ifndef ACCEL_BLOCKS
-#define ACCEL_BLOCKS (TILE_THREADS == 256 ? 5 : 2)
-#endif
-// Neighbour lists handed from the density pass to the acceleration pass, 16-bit entries, per
-// workgroup a block of list_rows(list_cap) * TILE_THREADS 32-bit words laid out in BLOCKS OF EIGHT
-// ENTRIES: entries 8b .. 8b+7 of lane t are the 16 bytes at b * LIST_BLOCK_BYTES + 16 t.  A consumer
-// fetches a trip's eight entries with one 16-byte load per lane (a wave: 1 KB contiguous); the
-// producer fills a 16-byte slot with eight consecutive 2-byte stores of ONE lane, so a 128-byte
-// line is complete after eight lanes have taken eight pops each and leaves the L2 whole.  (Until
-// round 4 entry j sat in half (j & 1) of word (j >> 1) * TILE_THREADS + t: a line was shared by 32
-// lanes x 2 entries and stayed open until the slowest of them got there - in a compressed scene,
-// 150 entries per particle and three workgroups per CU, the open lines outgrew the L2 several
-// times over and the density pass WROTE 9 GB for 1.3 GB of entries: profiles/r4_notes.md.)
-// Only blocks in use are ever touched.  list_cap - the neighbours per particle the lists hold - is a
-// launch argument: a context starts with NLIST_CAP and the host enlarges it (up to NLIST_CAP_MAX,
-// memory permitting) when the density pass reports particles that went without a list.
-#ifndef NLIST_CAP
-#define NLIST_CAP 254
-#endif
-#define NLIST_CAP_MAX 1022
-#define LIST_BLOCK_ENTRIES 8
-#define LIST_BLOCK_BYTES (16 * TILE_THREADS)
-// rows of TILE_THREADS words a workgroup's list block takes: whole blocks for entries 0 .. list_cap
-__host__ __device__ __forceinline__ constexpr int list_rows(int list_cap)
-{
-   return 4 * ((list_cap + LIST_BLOCK_ENTRIES) / LIST_BLOCK_ENTRIES);
-}
-// byte offset of entry j of the lane whose slots start at lane_off (= 16 * lane) in the block
-__device__ __forceinline__ uint32_t list_entry_off(uint32_t j, uint32_t lane_off)
-{
-   return (j >> 3) * (uint32_t)LIST_BLOCK_BYTES + lane_off + (j & 7u) * 2u;
-}
-// The append's running position.  pos holds block and slot of the next entry with the lane field
-// (bits 4 .. 4 + log2(TILE_THREADS)) ALL ONES: pos += 2 then carries from the slot field straight
-// into the block field when a 16-byte slot is full (and leaves the lane field zero: or it back).
-// The address puts the lane in: one v_bfi.  Three instructions per entry, none of them a shift.
-#define LIST_LANE_FIELD ((uint32_t)(LIST_BLOCK_BYTES - 16))
-__device__ __forceinline__ uint32_t list_pos_of(uint32_t j)
-{
-   return ((j >> 3) * (uint32_t)LIST_BLOCK_BYTES + (j & 7u) * 2u) | LIST_LANE_FIELD;
-}
-__device__ __forceinline__ uint32_t list_pos_off(uint32_t pos, uint32_t lane_off)
-{
-   return (LIST_LANE_FIELD & lane_off) | (~LIST_LANE_FIELD & pos);      // v_bfi_b32
-}
-__device__ __forceinline__ uint32_t list_pos_next(uint32_t pos) { return (pos + 2u) | LIST_LANE_FIELD; }
-__device__ __forceinline__ uint32_t list_entry_load(const char* __restrict__ lists, uint32_t j, uint32_t lane_off)
-{
-   return *reinterpret_cast<const uint16_t*>(lists + list_entry_off(j, lane_off));
-}
-// the eight entries of block b of that lane
-__device__ __forceinline__ uint4 list_block_load(const char* __restrict__ lists, int b, uint32_t lane_off)
-{
-   return *reinterpret_cast<const uint4*>(lists + (uint32_t)b * (uint32_t)LIST_BLOCK_BYTES + lane_off);
-}
-__device__ __forceinline__ void list_block_entries(const uint4& blk, uint32_t (&entry)[8])
-{
-   entry[0] = blk.x & 0xffffu; entry[1] = blk.x >> 16;
-   entry[2] = blk.y & 0xffffu; entry[3] = blk.y >> 16;
-   entry[4] = blk.z & 0xffffu; entry[5] = blk.z >> 16;
-   entry[6] = blk.w & 0xffffu; entry[7] = blk.w >> 16;
-}
-// Zeroes the entries between a list's end and the end of its last block (0 is a valid tile index):
-// the bit-exact acceleration loop gathers by every entry of a fetched block before it looks at the
-// count, and what an earlier step left there need not be an index of this step's tile.
-__device__ __forceinline__ void list_pad(char* __restrict__ lists, uint32_t lane_off, int count, int list_cap)
-{
-   if (count >= list_cap + 1) return;
-   uint32_t c = (uint32_t)count;
-   if (c & 1u) { *reinterpret_cast<uint16_t*>(lists + list_entry_off(c, lane_off)) = (uint16_t)0; c += 1u; }
-   if (c & 2u) { *reinterpret_cast<uint32_t*>(lists + list_entry_off(c, lane_off)) = 0u; c += 2u; }
-   if (c & 4u) { *reinterpret_cast<uint2*>(lists + list_entry_off(c, lane_off)) = make_uint2(0u, 0u); }
-}
-// first list word of a particle that has no list (more neighbours than list_cap): no valid
-// entry has segment id 15
-#define NLIST_NO_LIST 0xffffffffu
-static_assert(NLIST_CAP <= NLIST_CAP_MAX, "initial list capacity");
-// list entries fetched per trip of the SUM loops (measured best on MI355X: 8 / 8; the density
-// pass ran best with 6 until the end of round 2, now 8 or 10 are 5-10 us ahead of it at 4M)
-#ifndef DENSITY_UNROLL
-#define DENSITY_UNROLL 8
-#endif
-#ifndef APPEND_POPS
-#define APPEND_POPS 4     // accepted candidates appended per trip of the append loop
-#endif
-// The tiled density pass appends through LDS: a lane collects the eight entries of its current list
-// block in a 16-byte slot of its own and writes the block with ONE 16-byte store when it is full (and
-// the last, partial one once at the end).  The texture addresser was busy 80 % of that pass with the
-// 2-byte stores of the append - one per accepted neighbour, each to a 16-byte slot of its own, 13 L2
-// requests per wave-instruction - and every other load of the CU queued behind them: with seven stores in
-// eight left out (a probe, lists wrong) a workgroup's life went from 55 to 45 us, its prologue from 13 to
-// 9 us (tools/phase_clock.py, tools/pmc_latency.sh, profiles/r4_notes.md 4c).
-#ifndef APPEND_STAGED
-#define APPEND_STAGED 1
-#endif
-#ifndef ACCEL_UNROLL
-#define ACCEL_UNROLL 8
-#endif
-#ifndef VISC_UNROLL
-#define VISC_UNROLL 4     // neighbours per trip of the tolerance-mode viscous sum (the list's last few)
-#endif
-// A 16-bit list entry is a tile index plus what it takes to get back from it to the neighbour's
-// sorted position (tile index - D[segment]).  Narrow (tiles up to 4064 entries): segment id << 12 |
-// 12-bit index.  Wide (scenes several times denser, tiles up to 16352 entries, chosen per step by
-// the host): plane dz + 1 << 14 | 14-bit index; the row inside the plane follows from the index
-// and the descriptor's segment starts B - two more LDS reads and compares per neighbour, which is
-// why it is not the only format.
-template <bool WIDE>
-struct ListEntry {
-   static constexpr int TBITS = WIDE ? 14 : 12;
-   static constexpr uint32_t TMASK = (1u << TBITS) - 1u;
-   __device__ static __forceinline__ uint32_t tag(int segment)
-   {
-      return (uint32_t)(WIDE ? segment / 3 : segment) << TBITS;
-   }
-   __device__ static __forceinline__ int tile(uint32_t e) { return (int)(e & TMASK); }
-   // D of the entry's segment.  Segments of a plane that share storage have equal D, and an
-   // empty segment starts where the next begins, so comparing with the starts finds a valid one.
-   template <class Desc>
-   __device__ static __forceinline__ int shift(const Desc& d, uint32_t e)
-   {
-      if (!WIDE) return d.D[e >> TBITS];
-      const int z = (int)(e >> TBITS), t = (int)(e & TMASK);
-      const int k = 3 * z + (t >= d.B[3 * z + 1] ? 1 : 0) + (t >= d.B[3 * z + 2] ? 1 : 0);
-      return d.D[k];
-   }
-};
+constexpr int DENSITY_BLOCKS = 6 * 256 / TILE_THREADS;
+constexpr int ACCEL_BLOCKS = TILE_THREADS == 256 ? 5 : 2;
+// A trip of the list-driven SUM and pressure loops is one block of the lists (LIST_BLOCK_ENTRIES:
+// measured best on MI355X; the density pass ran best with 6 until the end of round 2, now 8 or 10
+// are 5-10 us ahead of it at 4M).
+constexpr int APPEND_POPS = 4;   // accepted candidates appended per trip of the append loop
+constexpr int VISC_UNROLL = 4;   // neighbours per trip of the tolerance-mode viscous sum (the list's last few)
 
 typedef float __attribute__((ext_vector_type(2))) f32x2;
 typedef float __attribute__((ext_vector_type(4))) f32x4;
@@ -246,11 +123,6 @@ __device__ __forceinline__ f32x4 lds_read4(const float* base, int i)
 {
    return *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(base + i, 16));
 }
-
-static_assert(DENSITY_UNROLL == LIST_BLOCK_ENTRIES && ACCEL_UNROLL == LIST_BLOCK_ENTRIES, "a trip of the list-driven loops is one block of the lists");
-static_assert(TILE_CAP_MAX + TILE_PAD <= (1 << ListEntry<false>::TBITS) &&
-                 TILE_CAP_MAX_WIDE + TILE_PAD <= (1 << ListEntry<true>::TBITS),
-              "tile index must fit the list entry");
 
 // Per-workgroup tile layout, computed by k_tile_desc before the sums run.
 struct TileDesc {
@@ -576,10 +448,9 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
    if (sd.total > tile_cap) {
       // tile does not fit: on the give-up lists, computed by the first workgroups of both passes
       // (or, with its lists, by k_full_density_chunked, which then has set the flag itself)
-      if (inline_giveups && tid == 0) nlist_overflow[wg] = 1u;
+      if (inline_giveups && tid == 0) nlist_overflow[wg] = LISTS_NONE;
       return;
    }
-#if APPEND_STAGED
    // The three arrays are packed to the tile's own size; what the launch's capacity leaves free behind
    // them holds the append's staging slots (16 bytes per lane).  A tile that leaves less than that - one
    // workgroup in a hundred at the benchmark's density - appends with 2-byte stores as before round 4.
@@ -591,9 +462,8 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
       L.y = L.x + packed;
       L.z = L.y + packed;
       stage_lane = reinterpret_cast<char*>(L.z + packed) + 16 * tid;
-      *reinterpret_cast<uint4*>(stage_lane) = make_uint4(0u, 0u, 0u, 0u);
+      list_stage_clear(stage_lane);
    }
-#endif
    RowRanges r;
 #pragma unroll
    for (int kk = 0; kk < 9; kk++) r.s[kk] = r.e[kk] = 0;
@@ -609,18 +479,15 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
    PHASE_MARK(1);   // tile
    const int self_t = p + sd.D[4];
    const f32x2 px = {pi.x, pi.x}, py = {pi.y, pi.y}, pz = {pi.z, pi.z};
-   // uniform base of the workgroup's list block; lanes address it with 32-bit offsets
-   uint32_t* list_block = nlist + (size_t)wg * (size_t)(list_rows(list_cap) * TILE_THREADS);
 
    const float h2_screen = k.h2_screen;
    TRIP(TripCounters trips; trips.wave(TRIP_D_WAVES, true); trips.lane(TRIP_D_LANES_L, live ? 1u : 0u);)
    int count = 0;
-   // TEST stores every accepted neighbour with one 2-byte store (no pairing of entries in registers:
-   // the append loop runs to the largest popcount among the wave's lanes for every chunk, so what
-   // counts is instructions per trip); pos = where this lane's next entry goes (list_pos_of).
-   char* const lists = reinterpret_cast<char*>(list_block);
-   const uint32_t lane_off = 16u * (uint32_t)tid;
-   uint32_t pos = list_pos_of(0u);
+   // TEST appends every accepted neighbour on its own (no pairing of entries in registers: the append
+   // loop runs to the largest popcount among the wave's lanes for every chunk, so what counts is
+   // instructions per trip)
+   ListWriter lw(nlist, wg, list_cap, tid, stage_lane);
+   uint32_t pos = list_pos_of(0u);   // where the lane's next entry goes
    // TEST + append over the nine rows, compiled twice: for a workgroup that stages its appends in LDS
    // (nearly all) and for one whose tile leaves no room (a branch on that in every pop cost 10 us at 4M)
    auto test_and_append = [&](auto staged_c) {
@@ -678,61 +545,22 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
                   if (mask != 0u) {
                      const uint32_t bit = (uint32_t)__builtin_ctz(mask);
                      mask &= mask - 1u;
-#if APPEND_STAGED
-                     const uint32_t in_block = pos & 14u;   // the entry's two bytes inside its 16-byte block
-                     if constexpr (STAGED) {
-                        *reinterpret_cast<uint16_t*>(stage_lane + in_block) = (uint16_t)(ebase + bit);
-                        if (in_block == 14u)                // the block is complete: one 16-byte store
-                           *reinterpret_cast<uint4*>(lists + list_pos_off(pos & ~14u, lane_off)) =
-                              *reinterpret_cast<const uint4*>(stage_lane);
-                     } else {
-                        *reinterpret_cast<uint16_t*>(lists + list_pos_off(pos, lane_off)) = (uint16_t)(ebase + bit);
-                     }
-#else
-                     *reinterpret_cast<uint16_t*>(lists + list_pos_off(pos, lane_off)) = (uint16_t)(ebase + bit);
-#endif
-                     pos = list_pos_next(pos);
+                     lw.append<STAGED>(pos, ebase + bit);
                   }
                }
             }
          }
       }
    };
-#if APPEND_STAGED
    if (staged) test_and_append(std::true_type());
    else test_and_append(std::false_type());
-#else
-   test_and_append(std::false_type());
-#endif
    PHASE_MARK(2);   // TEST + append
-#if APPEND_STAGED
-   // The last block, partly filled (or block 0 of a lane without neighbours): the slot as it is - what
-   // lies behind the list's end are entries of the lane's previous block or the zeros the slot started
-   // with, valid indices of this tile either way, which is all list_pad's zeros are there for.
-   if (!staged)
-      list_pad(lists, lane_off, count, list_cap);
-   else if (count <= list_cap && ((count & 7) != 0 || count == 0))
-      *reinterpret_cast<uint4*>(lists + list_pos_off(pos & ~14u, lane_off)) = *reinterpret_cast<const uint4*>(stage_lane);
-#else
-   // (the rest of the list's last block: zeros)
-   list_pad(lists, lane_off, count, list_cap);
-#endif
    // A particle with more neighbours than its list holds (a scene many times denser than the
    // benchmark's) goes without a list: its lane walks its candidate ranges in the tile one by one
    // here - canonical order, small code - and again in the acceleration pass, which recognises it
    // by the marker in the list's first word; the other lanes of the workgroup keep their lists.
-   const bool overflowed = count > list_cap;
-   if (overflowed) {
-      list_overflow = 1;
-      *reinterpret_cast<uint32_t*>(lists + lane_off) = NLIST_NO_LIST;
-   }
-   if (__any(overflowed)) {
-      // reported to the host (through the acceleration pass), which then enlarges the lists
-      const int without = __popcll(__ballot(overflowed));
-      if ((tid & (SPH_WAVE - 1)) == 0) atomicAdd(&tile_stats[TSTAT_NO_LIST], without);
-   }
-   __syncthreads();
-   if (tid == 0) nlist_overflow[wg] = list_overflow ? 2u : 0u;
+   const bool overflowed = lw.finish(pos, count, list_cap, staged, list_overflow);
+   lists_publish(overflowed, list_overflow, tile_stats, nlist_overflow, wg);
    float density = 0.0f;
    if (__any(overflowed) && overflowed) {
       count = 0;
@@ -777,15 +605,15 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
    TRIP(trips.lane(TRIP_D_LISTED_L, (unsigned)listed);)
    // (the next trip's block travels while this trip's entries are summed; the compaction below only
    // ever writes behind the current trip's read position, never into the block already fetched)
-   uint4 sum_blk = list_block_load(lists, 0, lane_off);
-   for (int j0 = 0; __any(j0 < listed); j0 += DENSITY_UNROLL) {
+   uint4 sum_blk = lw.block(0);
+   for (int j0 = 0; __any(j0 < listed); j0 += LIST_BLOCK_ENTRIES) {
       TRIP(trips.wave(TRIP_D_SUMTRIPS_W, true);
-           for (int u = 0; u < DENSITY_UNROLL; u++) trips.wave(TRIP_D_SUMSLOTS_W, __any(j0 + u < listed));)
+           for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) trips.wave(TRIP_D_SUMSLOTS_W, __any(j0 + u < listed));)
 #if !(defined(SPH_ABLATE) && (SPH_ABLATE == 1 || SPH_ABLATE == 15))
-      uint32_t entry[DENSITY_UNROLL];
+      uint32_t entry[LIST_BLOCK_ENTRIES];
       // (the trip's eight entries: one 16-byte load; a lane past its last block takes that one again)
       list_block_entries(sum_blk, entry);
-      sum_blk = list_block_load(lists, min((j0 >> 3) + 1, lastb), lane_off);
+      sum_blk = lw.block(min((j0 >> 3) + 1, lastb));
       if constexpr (WIDE) {
          // Scenes several times denser than the benchmark's (wide entries = tiles beyond 4064
          // positions = at most four workgroups per CU): few waves share a SIMD, so the latency of a
@@ -793,10 +621,10 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
          // trip's other neighbours or not at all.  The eight entries as ONE basic block: all reads
          // first, the roots together, the terms added in list order (a neighbour past the count or
          // failing the reference's test adds +0.0f); the registers are there at this occupancy.
-         float d2[DENSITY_UNROLL], mj[DENSITY_UNROLL];
-         bool ok[DENSITY_UNROLL];
+         float d2[LIST_BLOCK_ENTRIES], mj[LIST_BLOCK_ENTRIES];
+         bool ok[LIST_BLOCK_ENTRIES];
 #pragma unroll
-         for (int u = 0; u < DENSITY_UNROLL; u++) {
+         for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
             const bool valid = j0 + u < listed;
             const int t = valid ? ListEntry<WIDE>::tile(entry[u]) : 0;
             mj[u] = pi.w;
@@ -805,23 +633,22 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
             d2[u] = dist2(pi.x, pi.y, pi.z, L.x[t], L.y[t], L.z[t], dx, dy, dz);
             ok[u] = valid && d2[u] < k.h2;      // the reference's own test, on the reference's own value
          }
-         float dd[DENSITY_UNROLL];
+         float dd[LIST_BLOCK_ENTRIES];
 #pragma unroll
-         for (int u = 0; u < DENSITY_UNROLL; u++) dd[u] = ok[u] ? d2[u] : 0.0f;
+         for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) dd[u] = ok[u] ? d2[u] : 0.0f;
          sqrt_rn_batch(dd);
 #pragma unroll
-         for (int u = 0; u < DENSITY_UNROLL; u++) {
+         for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
             float d = dd[u];
             if (!UNIT_SCALE) d *= k.sim_scale;
             const float term = density_term<UNIT_SCALE>(k, mj[u], d);
             density += ok[u] ? term : 0.0f;
-            if (ok[u] && kept != j0 + u)
-               *reinterpret_cast<uint16_t*>(lists + list_entry_off((uint32_t)kept, lane_off)) = (uint16_t)entry[u];
+            if (ok[u] && kept != j0 + u) lw.keep(kept, entry[u]);
             kept += ok[u] ? 1 : 0;
          }
       } else {
 #pragma unroll
-      for (int u = 0; u < DENSITY_UNROLL; u++) {
+      for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
          if (j0 + u < listed) {
             const int t = ListEntry<WIDE>::tile(entry[u]);
             float mj = pi.w;
@@ -834,7 +661,7 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
                   if (!UNIT_SCALE) d *= k.sim_scale;
                   density_accumulate<UNIT_SCALE>(k, mj, d, density);
                }
-               if (kept != j0 + u) *reinterpret_cast<uint16_t*>(lists + list_entry_off((uint32_t)kept, lane_off)) = (uint16_t)entry[u];
+               if (kept != j0 + u) lw.keep(kept, entry[u]);
                kept++;
             }
          }
@@ -846,7 +673,7 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
    }
    if (!overflowed && kept != count) {
       count = kept;
-      list_pad(lists, lane_off, count, list_cap);
+      lw.pad(count, list_cap);
    }
    TRIP(trips.flush(0, 1u << TRIP_D_TEST8_L | 1u << TRIP_D_SLOTS_L | 1u << TRIP_D_POPS_L | 1u << TRIP_D_LISTED_L |
                        1u << TRIP_D_LANES_L);)
@@ -919,7 +746,7 @@ k_full_density_chunked(const float4* __restrict__ posm, const float4* __restrict
       if (sd.total + TILE_PAD > (1 << ListEntry<WIDE>::TBITS)) {
          // its virtual tile cannot be indexed by a list entry: the untiled walk, no lists
          if (live) density_untiled<UNIT_SCALE, FAST>(p, posm, cell_start, velp, g, k, rho_out, velB_out, auxc_out, ncount);
-         if (tid == 0) nlist_overflow[wg] = 1u;
+         if (tid == 0) nlist_overflow[wg] = LISTS_NONE;
          continue;
       }
       float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -938,13 +765,11 @@ k_full_density_chunked(const float4* __restrict__ posm, const float4* __restrict
       const int c_first = (int)cell_of(g, pa.x, pa.y, pa.z, cxa, cya, cza);
       const int c_last = (int)cell_of(g, pb.x, pb.y, pb.z, cxb, cyb, czb);
       const f32x2 px = {pi.x, pi.x}, py = {pi.y, pi.y}, pz = {pi.z, pi.z};
-      uint32_t* list_block = nlist + (size_t)wg * (size_t)(list_rows(list_cap) * TILE_THREADS);
-      char* const lists = reinterpret_cast<char*>(list_block);
-      const uint32_t lane_off = 16u * (uint32_t)tid;
-      uint32_t pos = list_pos_of(0u);   // the append position (list_pos_of(entries this lane's list holds))
+      ListWriter lw(nlist, wg, list_cap, tid, stage_lane);
+      uint32_t pos = list_pos_of(0u);
       int count = 0;
       float density = 0.0f;
-      if (staged) *reinterpret_cast<uint4*>(stage_lane) = make_uint4(0u, 0u, 0u, 0u);
+      if (staged) list_stage_clear(stage_lane);
 #pragma unroll 1
       for (int kk = 0; kk < 9; kk++) {
          const int off = ((kk / 3 - 1) * g.ny + (kk % 3 - 1)) * g.nx;
@@ -1027,16 +852,8 @@ k_full_density_chunked(const float4* __restrict__ posm, const float4* __restrict
                            mask = 0u;
                         } else {
                            count++;
-                           const uint32_t in_block = pos & 14u;
-                           if (staged) {
-                              *reinterpret_cast<uint16_t*>(stage_lane + in_block) = (uint16_t)(ebase + bit);
-                              if (in_block == 14u)
-                                 *reinterpret_cast<uint4*>(lists + list_pos_off(pos & ~14u, lane_off)) =
-                                    *reinterpret_cast<const uint4*>(stage_lane);
-                           } else {
-                              *reinterpret_cast<uint16_t*>(lists + list_pos_off(pos, lane_off)) = (uint16_t)(ebase + bit);
-                           }
-                           pos = list_pos_next(pos);
+                           if (staged) lw.append<true>(pos, ebase + bit);
+                           else lw.append<false>(pos, ebase + bit);
                         }
                      }
                   }
@@ -1044,21 +861,8 @@ k_full_density_chunked(const float4* __restrict__ posm, const float4* __restrict
             }
          }
       }
-      if (!staged)
-         list_pad(lists, lane_off, count, list_cap);
-      else if (count <= list_cap && ((count & 7) != 0 || count == 0))
-         *reinterpret_cast<uint4*>(lists + list_pos_off(pos & ~14u, lane_off)) = *reinterpret_cast<const uint4*>(stage_lane);
-      const bool overflowed = count > list_cap;
-      if (overflowed) {
-         list_overflow = 1;
-         *reinterpret_cast<uint32_t*>(lists + lane_off) = NLIST_NO_LIST;
-      }
-      if (__any(overflowed)) {
-         const int without = __popcll(__ballot(overflowed));
-         if ((tid & (SPH_WAVE - 1)) == 0) atomicAdd(&tile_stats[TSTAT_NO_LIST], without);
-      }
-      __syncthreads();
-      if (tid == 0) nlist_overflow[wg] = list_overflow ? 2u : 0u;
+      const bool overflowed = lw.finish(pos, count, list_cap, staged, list_overflow);
+      lists_publish(overflowed, list_overflow, tile_stats, nlist_overflow, wg);
       if (live) {
          if (overflowed) {
             // more neighbours than the list holds: this lane alone walks its candidates through L1/L2
@@ -1226,7 +1030,7 @@ __device__ __forceinline__ void fused_integrate(const FusedStep& fs, const PairC
 // workgroup's tile descriptor (in LDS: the entries' segment -> sorted position shift).
 template <bool UNIT_SCALE, bool UNIFORM_MASS, bool WIDE, bool FAST>
 __device__ __forceinline__ float4
-accel_from_lists(int p, int cnt, const char* __restrict__ lists, uint32_t lane_off, const TileDesc& d,
+accel_from_lists(int p, int cnt, const ListReader& lr, const TileDesc& d,
                  const float4* __restrict__ posm, const float4* __restrict__ velB,
                  const float* __restrict__ rho, const float* __restrict__ auxc, const PairConsts& k)
 {
@@ -1235,10 +1039,7 @@ accel_from_lists(int p, int cnt, const char* __restrict__ lists, uint32_t lane_o
    accel_begin(k, s, pi, velB[p], rho[p]);
    const bool in_range = accel_operands_in_range(k);
    int first_v = 0;
-   if (FAST) {
-      const int keep = visc_keep(s.visc_scale);
-      first_v = keep < cnt ? cnt - keep : 0;
-   }
+   if (FAST) first_v = visc_first(cnt, s.visc_scale);
    if constexpr (FAST) {
       // Tolerance mode (the arithmetic the compressed dam is benchmarked in, where a tenth of the workgroups
       // come here): the pressure sum takes a list block of eight entries per trip - ONE 16-byte load, the
@@ -1247,11 +1048,11 @@ accel_from_lists(int p, int cnt, const char* __restrict__ lists, uint32_t lane_o
       // accel_end: same bits).  Four entries per trip, a 2-byte load each and {v, C} gathered for all of
       // them, made a particle with 170 neighbours wait for 85 dependent round trips.
       const int lastb = cnt > 0 ? (cnt - 1) >> 3 : 0;
-      uint4 blk = list_block_load(lists, 0, lane_off);
+      uint4 blk = lr.block(0);
       for (int j0 = 0; j0 < cnt; j0 += 8) {
          uint32_t entry[8];
          list_block_entries(blk, entry);
-         blk = list_block_load(lists, min((j0 >> 3) + 1, lastb), lane_off);
+         blk = lr.block(min((j0 >> 3) + 1, lastb));
          float4 pj[8];
          float cj[8];
 #pragma unroll
@@ -1275,7 +1076,7 @@ accel_from_lists(int p, int cnt, const char* __restrict__ lists, uint32_t lane_o
          float4 pj[VISC_UNROLL], vj[VISC_UNROLL];
 #pragma unroll
          for (int u = 0; u < VISC_UNROLL; u++) {
-            const uint32_t e = list_entry_load(lists, (uint32_t)min(j0 + u, cnt - 1), lane_off);
+            const uint32_t e = lr.entry((uint32_t)min(j0 + u, cnt - 1));
             const int q = ListEntry<WIDE>::tile(e) - ListEntry<WIDE>::shift(d, e);
             pj[u] = posm[q];
             vj[u] = velB[q];
@@ -1300,7 +1101,7 @@ accel_from_lists(int p, int cnt, const char* __restrict__ lists, uint32_t lane_o
 #pragma unroll
       for (int u = 0; u < U; u++) {
          const int j = min(j0 + u, cnt - 1);
-         const uint32_t e = list_entry_load(lists, (uint32_t)j, lane_off);
+         const uint32_t e = lr.entry((uint32_t)j);
          const int q = ListEntry<WIDE>::tile(e) - ListEntry<WIDE>::shift(d, e);
          pj[u] = posm[q];
          cj[u] = auxc[q];
@@ -1366,9 +1167,9 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
    // the pass is launched in two parts (early exchange), for those of the other part
    const bool own = mapped >= 0 && !(p0 >= end || p0 + TILE_THREADS <= ob || p0 >= oe) &&
                     accel_part_has(part, p0, meta);
-   // 1: tile did not fit the density pass (on the give-up list), 2: some particle of the
-   // workgroup has no list (more neighbours than list_cap)
-   const uint32_t gave_up = own ? nlist_overflow[wg] : 1u;
+   // the workgroup's lists (neighbor_lists.h: LISTS_NONE = its tile did not fit the density pass, on
+   // the give-up list; LISTS_SOME = some particle has more neighbours than list_cap)
+   const uint32_t gave_up = own ? nlist_overflow[wg] : LISTS_NONE;
    // (requested together with the flag it would otherwise wait for - one round trip less in front
    // of the tile loads; kept in a register while a give-up workgroup uses L.desc)
    int desc_word = 0;
@@ -1380,20 +1181,18 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       const int gp = g0 + tid;
       const bool mine = gp < end && gp >= ob && gp < oe && accel_part_has(part, g0, meta);
       const int gwg = (int)giveup[blockIdx.x];
-      const uint32_t glists = nlist_overflow[gwg];   // 1: its tile did not fit the density pass either (no lists)
-      if (glists != 1u) {
+      const uint32_t glists = nlist_overflow[gwg];   // LISTS_NONE: its tile did not fit the density pass either
+      if (glists != LISTS_NONE) {
          // the lists are there: walk them, operands from global memory (accel_from_lists)
          tile_desc_load(desc, gwg, L.desc);
          if (mine) {
             const int gcnt = ncount[gp];
-            const char* glists_base = reinterpret_cast<const char*>(
-               nlist + (size_t)gwg * (size_t)(list_rows(list_cap) * TILE_THREADS));
-            const uint32_t goff = 16u * (uint32_t)tid;
-            if (glists == 2u && gcnt > 0 && *reinterpret_cast<const uint32_t*>(glists_base + goff) == NLIST_NO_LIST)
+            const ListReader glr(nlist, gwg, list_cap, tid);
+            if (glists == LISTS_SOME && gcnt > 0 && glr.no_list())
                accel_untiled<UNIT_SCALE, FAST>(gp, posm, velB, rho, auxc, cell_start, g, k, acc, ncount);
             else
-               acc[gp] = accel_from_lists<UNIT_SCALE, UNIFORM_MASS, WIDE, FAST>(gp, gcnt, glists_base, goff, L.desc, posm,
-                                                                                velB, rho, auxc, k);
+               acc[gp] = accel_from_lists<UNIT_SCALE, UNIFORM_MASS, WIDE, FAST>(gp, gcnt, glr, L.desc, posm, velB,
+                                                                                rho, auxc, k);
          }
          __syncthreads();   // L.desc is loaded again below, for this workgroup's own tile
       } else if (mine) {
@@ -1411,7 +1210,7 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          fused_integrate<UNIT_SCALE>(fs, k, g, gp, mine, gx, ga, (int)giveup[blockIdx.x]);
       }
    }
-   if (gave_up == 1u) return;
+   if (gave_up == LISTS_NONE) return;
    if (tid < (int)(sizeof(TileDesc) / sizeof(int))) reinterpret_cast<int*>(&L.desc)[tid] = desc_word;
    __syncthreads();
    PHASE_MARK(16);   // ranges, flags, descriptor
@@ -1439,8 +1238,7 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       buf[r] = make_float4(0.f, 0.f, 0.f, 0.f);
       cbuf[r] = 0.f;
    }
-   const int total_staged = 0;
-#define total total_staged
+   const int filled = 0;
 #else
 #pragma unroll
    for (int r = 0; r < BATCH; r++) {
@@ -1451,6 +1249,7 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       buf[r] = posm[idx - d];
       cbuf[r] = auxc[idx - d];
    }
+   const int filled = total;   // tile entries to store
 #endif
 
    // Lanes keep their own particle.  (Rounds 1-2 dealt the workgroup's particles to the lanes in
@@ -1474,21 +1273,20 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
 
    // the lane's first list words travel with the tile (requested before the count is known: what
    // a lane with fewer entries reads in the rows of its block is never used)
-   const char* lists = reinterpret_cast<const char*>(nlist + (size_t)wg * (size_t)(list_rows(list_cap) * TILE_THREADS));
-   const uint32_t lane_off = 16u * (uint32_t)col;
-   uint32_t entry[ACCEL_UNROLL];
-   uint4 next_blk = list_block_load(lists, 0, lane_off);      // (block 0 of every lane exists)
+   const ListReader lr(nlist, wg, list_cap, col);
+   uint32_t entry[LIST_BLOCK_ENTRIES];
+   uint4 next_blk = lr.block(0);      // (block 0 of every lane exists)
 
    // the tile: first batch from the registers, then whatever is left
 #pragma unroll
    for (int r = 0; r < BATCH; r++) {
       const int idx = tid + r * TILE_THREADS;
-      if (idx < total) xyzc[idx] = make_float4(buf[r].x, buf[r].y, buf[r].z, cbuf[r]);
+      if (idx < filled) xyzc[idx] = make_float4(buf[r].x, buf[r].y, buf[r].z, cbuf[r]);
    }
-   for (int base = BATCH * TILE_THREADS; base < total; base += BATCH * TILE_THREADS) {
+   for (int base = BATCH * TILE_THREADS; base < filled; base += BATCH * TILE_THREADS) {
 #pragma unroll
       for (int r = 0; r < BATCH; r++) {
-         const int idx = min(base + tid + r * TILE_THREADS, total - 1);
+         const int idx = min(base + tid + r * TILE_THREADS, filled - 1);
          int d = D[0];
 #pragma unroll
          for (int kk = 1; kk < 9; kk++) d = (idx >= B[kk]) ? D[kk] : d;
@@ -1498,13 +1296,10 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
 #pragma unroll
       for (int r = 0; r < BATCH; r++) {
          const int idx = base + tid + r * TILE_THREADS;
-         if (idx < total) xyzc[idx] = make_float4(buf[r].x, buf[r].y, buf[r].z, cbuf[r]);
+         if (idx < filled) xyzc[idx] = make_float4(buf[r].x, buf[r].y, buf[r].z, cbuf[r]);
       }
    }
    __syncthreads();
-#if defined(SPH_ABLATE) && SPH_ABLATE == 23
-#undef total
-#endif
 
    PHASE_MARK(17);   // tile, own loads, first list block
    AccelState s;
@@ -1514,14 +1309,13 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
    // a particle without a list (marker in its first word; only in workgroups flagged 2): its lane
    // skips the list loop and walks its candidate ranges in the tile afterwards
    bool no_list = false;
-   if (gave_up == 2u && cnt > 0) no_list = next_blk.x == NLIST_NO_LIST;
+   // (the marker tested on the block already loaded: ListReader::no_list() loads it again, and a
+   // helper taking the word changed this kernel's code)
+   if (gave_up == LISTS_SOME && cnt > 0) no_list = next_blk.x == NLIST_NO_LIST;
    // FAST: only the last visc_keep() neighbours take part in the viscous sum - and only they are
    // gathered ({v, C}; what every pair needs, m B, is in the tile)
    int first_v = 0;
-   if (FAST) {
-      const int keep = visc_keep(s.visc_scale);
-      first_v = keep < cnt ? cnt - keep : 0;
-   }
+   if (FAST) first_v = visc_first(cnt, s.visc_scale);
    if (no_list) cnt = 0;
 #if defined(SPH_ABLATE) && (SPH_ABLATE == 21 || SPH_ABLATE == 23)
    cnt = 0;   // timing only: prologue and epilogue
@@ -1549,16 +1343,16 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       const bool odd_lane = __any(!__builtin_isfinite(s.pi_div_rhoi2) || !__builtin_isfinite(self_c));
       TRIP(TripCounters trips; trips.wave(TRIP_A_WAVES - 16, true); trips.lane(TRIP_A_CNT_L - 16, (unsigned)cnt);
            trips.lane(TRIP_A_LANES_L - 16, live ? 1u : 0u); trips.lane(TRIP_A_NV_L - 16, (unsigned)(cnt - first_v));)
-      for (int j0 = 0; __any(j0 < cnt); j0 += ACCEL_UNROLL) {
+      for (int j0 = 0; __any(j0 < cnt); j0 += LIST_BLOCK_ENTRIES) {
          TRIP(trips.wave(TRIP_A_PTRIPS_W - 16, true);)
          list_block_entries(next_blk, entry);
-         next_blk = list_block_load(lists, min((j0 >> 3) + 1, lastb), lane_off);
+         next_blk = lr.block(min((j0 >> 3) + 1, lastb));
          // (the trip's roots taken together - sqrt_rn_batch - and no branch on j0 + u < cnt: a lane
          // past its count takes ITSELF as the neighbour with m B = 0 - r = 0 and a factor of zero:
          // the sum does not move - so that the eight pairs of a trip are one basic block)
-         float dx[ACCEL_UNROLL], dy[ACCEL_UNROLL], dz[ACCEL_UNROLL], dd[ACCEL_UNROLL], bm[ACCEL_UNROLL];
+         float dx[LIST_BLOCK_ENTRIES], dy[LIST_BLOCK_ENTRIES], dz[LIST_BLOCK_ENTRIES], dd[LIST_BLOCK_ENTRIES], bm[LIST_BLOCK_ENTRIES];
 #pragma unroll
-         for (int u = 0; u < ACCEL_UNROLL; u++) {
+         for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
             const bool valid = j0 + u < cnt;
             const float4 pj = xyzc[valid ? ListEntry<WIDE>::tile(entry[u]) : self_tile];
             dd[u] = dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx[u], dy[u], dz[u]);
@@ -1566,18 +1360,18 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          }
 #if defined(SPH_ABLATE) && SPH_ABLATE == 22
 #pragma unroll
-         for (int u = 0; u < ACCEL_UNROLL; u++) s.pgx += dd[u] + bm[u];   // timing only: no pair arithmetic
+         for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) s.pgx += dd[u] + bm[u];   // timing only: no pair arithmetic
 #else
          sqrt_rn_batch(dd);
          if (!odd_lane) {
 #pragma unroll
-            for (int u = 0; u < ACCEL_UNROLL; u++) {
+            for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
                if (!UNIT_SCALE) dd[u] *= k.sim_scale;
                accel_pair_fast_pressure<UNIT_SCALE>(k, s, dx[u], dy[u], dz[u], dd[u], bm[u]);
             }
          } else {
 #pragma unroll
-            for (int u = 0; u < ACCEL_UNROLL; u++) {
+            for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
                if (!UNIT_SCALE) dd[u] *= k.sim_scale;
                if (j0 + u < cnt) accel_pair_fast_pressure<UNIT_SCALE>(k, s, dx[u], dy[u], dz[u], dd[u], bm[u]);
             }
@@ -1596,7 +1390,7 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
 #pragma unroll
          for (int u = 0; u < VISC_UNROLL; u++) {
             const int j = min(first_v + m0 + u, cnt > 0 ? cnt - 1 : 0);
-            const uint32_t e = list_entry_load(lists, (uint32_t)j, lane_off);
+            const uint32_t e = lr.entry((uint32_t)j);
             tj[u] = ListEntry<WIDE>::tile(e);
             vj[u] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (m0 + u < nv) vj[u] = velB[tj[u] - ListEntry<WIDE>::shift(L.desc, e)];
@@ -1613,16 +1407,16 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          }
       }
    } else {
-   // ACCEL_UNROLL neighbours per trip: their {v,B} gathers are issued back to back before the
+   // LIST_BLOCK_ENTRIES neighbours per trip: their {v,B} gathers are issued back to back before the
    // first pair's arithmetic, and the list entries of the NEXT trip are requested before it too,
    // so neither of a neighbour's two dependent memory round trips is waited for in isolation.
    // Lanes past their count re-read their last entry (valid address, result unused).
-   for (int j0 = 0; __any(j0 < cnt); j0 += ACCEL_UNROLL) {
-      float4 vj[ACCEL_UNROLL];
-      float mj[ACCEL_UNROLL];
+   for (int j0 = 0; __any(j0 < cnt); j0 += LIST_BLOCK_ENTRIES) {
+      float4 vj[LIST_BLOCK_ENTRIES];
+      float mj[LIST_BLOCK_ENTRIES];
       list_block_entries(next_blk, entry);
 #pragma unroll
-      for (int u = 0; u < ACCEL_UNROLL; u++) {
+      for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
          mj[u] = pi.w;
          const int q = ListEntry<WIDE>::tile(entry[u]) - ListEntry<WIDE>::shift(L.desc, entry[u]);
          const int qq = cnt > 0 ? q : p0;  // lanes without neighbours hold no valid entry
@@ -1634,9 +1428,9 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          if (!UNIFORM_MASS) mj[u] = posm[qq].w;
       }
       // the next trip's list entries travel while this trip's pairs are computed
-      next_blk = list_block_load(lists, min((j0 >> 3) + 1, lastb), lane_off);
+      next_blk = lr.block(min((j0 >> 3) + 1, lastb));
 #pragma unroll
-      for (int u = 0; u < ACCEL_UNROLL; u++) {
+      for (int u = 0; u < LIST_BLOCK_ENTRIES; u++) {
          if (j0 + u < cnt) {
             const float4 pj = xyzc[ListEntry<WIDE>::tile(entry[u])];
             float dx, dy, dz;
@@ -1653,7 +1447,7 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       }
    }
    }
-   if (gave_up == 2u && __any(no_list) && no_list) {
+   if (gave_up == LISTS_SOME && __any(no_list) && no_list) {
       // canonical order: the 9 rows ascending, positions ascending inside a row
       RowRanges rr;
       int cx, cy, cz;

@@ -255,6 +255,14 @@ __device__ __forceinline__ int visc_keep(float visc_scale)
    return m < 1.0f ? 1 : (int)m;
 }
 
+// FAST: the first of a particle's cnt neighbours (in canonical order) that take part in the viscous
+// sum - only the last visc_keep() do
+__device__ __forceinline__ int visc_first(int cnt, float visc_scale)
+{
+   const int keep = visc_keep(visc_scale);
+   return keep < cnt ? cnt - keep : 0;
+}
+
 // The point-mass term gm * (rs / d3) of a scene without a point mass (gm = -G * 0, G finite), with
 // rs = (r - c) * sim_scale, dot = |rs| and d3 = (dot + softening)^3 as in reference src/sph.cpp:897-915
 // and 974-989 - componentwise what it comes to without the square root and the three divisions:

@@ -9,7 +9,7 @@ Three measured inputs, no model of the code:
      the per-chunk bookkeeping.
   2. The opcode MIX of each phase: the shipped ISA compiled with -gline-tables-only (same code, plus
      .loc directives), every VALU instruction attributed to the phase whose source lines it came from
-     (helpers inlined from sph_device.h / pair_math.h inherit the phase of the code around them;
+     (helpers inlined from sph_device.h / pair_math.h / neighbor_lists.h inherit the phase of the code around them;
      code that the 4M column never runs - untiled give-up bodies, the walk of a particle without a
      list, sqrtf's slow path - is left out of the mix; TEST + append are compiled twice, for workgroups
      that stage their appends in LDS and for the one in a hundred that cannot: both copies share
@@ -92,9 +92,9 @@ def source_spans():
     # ---- acceleration kernel
     a0 = find(ft, "k_full_accel_lists(const float4* __restrict__ posm")
     g0 = find(ft, "if ((int)blockIdx.x < tile_stats[TSTAT_GIVEUP_ACCEL]) {", a0)
-    g1 = find(ft, "if (gave_up == 1u) return;", a0)
+    g1 = find(ft, "if (gave_up == LISTS_NONE) return;", a0)
     p0 = find(ft, "if constexpr (FAST) {", a0)
-    p1 = find(ft, "if (gave_up == 2u && __any(no_list) && no_list) {", a0)
+    p1 = find(ft, "if (gave_up == LISTS_SOME && __any(no_list) && no_list) {", a0)
     e0 = find(ft, "if (FAST) accel_fast_finish(k, s);", p1)
     spans["a_pro"].append(("full_tiled.h", a0, g0 - 1))
     spans["a_rare"].append(("full_tiled.h", g0, g1 - 1))
@@ -109,7 +109,7 @@ def source_spans():
     return spans
 
 
-HELPERS = ("sph_device.h", "pair_math.h", "common_kernels.h", "slab_kernels.h", "cell_build.h")
+HELPERS = ("sph_device.h", "pair_math.h", "common_kernels.h", "slab_kernels.h", "cell_build.h", "neighbor_lists.h")
 
 
 def attribute(asm, kernel, prefix, spans):
@@ -146,7 +146,7 @@ def attribute(asm, kernel, prefix, spans):
                 cur = ph
             elif fname not in HELPERS and not fname.startswith(("amd_", "__clang")) and fname != "sph_hip.hip":
                 pass
-            # helpers (sph_device.h, pair_math.h, the HIP headers) inherit the phase around them; a
+            # helpers (sph_device.h, pair_math.h, neighbor_lists.h, the HIP headers) inherit the phase around them; a
             # slow path inside a helper is recognised by its opcodes below
             continue
         if s.startswith("v_"):
