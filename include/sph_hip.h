@@ -312,6 +312,59 @@ int sph_hip_sample_points(sph_hip_context* ctx, int n, const float* xyz,
 int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
                            const int32_t dims[3], float* density, float* velocity_xyz, int32_t* count);
 
+/* ---- iso-surface extractor ---------------------------------------------------------------- *
+ *
+ * An indexed triangle mesh of the fluid's surface {f > iso} over the density lattice f that
+ * sph_hip_sample_lattice(ctx, origin, spacing, dims, ...) would return at that moment (hence the
+ * same mesh in FULL and FULL_FAST).  All arithmetic is fp32, unfused, in the order written.
+ *   inside     a lattice point is inside when f > iso (strictly); NaN is outside.
+ *   cells      the cube with lower corner (i, j, k), i < nx-1, j < ny-1, k < nz-1; its corner
+ *              c = x + 2y + 4z is lattice point (i+x, j+y, k+z).  It splits into six tetrahedra
+ *              {0, a, a|b, 7}, (a, b) in the order (1,2), (1,4), (2,1), (2,4), (4,1), (4,2).
+ *   edges      every tetrahedron edge is one of the seven positive-direction edges of a lattice
+ *              point p, in the order +x, +y, +z, +x+y, +x+z, +y+z, +x+y+z; an edge exists only
+ *              where its far end is on the lattice.  An edge with exactly one inside endpoint
+ *              carries one vertex.  Vertex ids are ranks in canonical order: first by p's lattice
+ *              index (k*ny + j)*nx + i, then by the edge's place in that list.
+ *   position   a = p (the owning end), b = the far end: t = (iso - f_a) / (f_b - f_a), then
+ *              t = fminf(fmaxf(t, 0), 1) (IEEE: NaN becomes 0); per component
+ *              x = x_a + t * (x_b - x_a), lattice coordinates origin + (float)i * spacing.
+ *   normal     the lattice gradient at a and at b, per axis of spacing s: central
+ *              (f[+1] - f[-1]) / (2 * s) inside, (f[+1] - f) / s on the lower face, (f - f[-1]) / s
+ *              on the upper face, 0 along an axis of one point; g = g_a + t * (g_b - g_a) per
+ *              component; len = sqrtf((gx*gx + gy*gy) + gz*gz); the normal is -(g / len) per
+ *              component when len is finite and > 0, else 0 (it points toward lower density).
+ *   velocity   v = v_a + t * (v_b - v_a) per component, of the sampler's Shepard velocity.
+ *   triangles  in canonical cube order, then tetrahedron order.  A tetrahedron with its four
+ *              corners all inside or all outside emits none; one corner apart from the other three:
+ *              one triangle of the three edges at that corner; two and two: the quad of the four
+ *              crossing edges, cycle (q0, q1, q2, q3) with consecutive edges sharing a corner, as
+ *              (q0, q1, q2), (q0, q2, q3).  Every cycle starts at its smallest vertex id and is
+ *              oriented so that, with its vertices at the edge midpoints (t = 0.5),
+ *              (v1 - v0) x (v2 - v0) points from the inside corners toward the outside ones -
+ *              combinatorial: degenerate positions (t of 0 or 1) cannot flip it.
+ *   guarantee  when no point on the lattice's outer faces is inside, the mesh is closed and
+ *              consistently oriented: every undirected edge is used by exactly two triangles, once
+ *              in each direction.  (The sampler gives zeros outside the box: a lattice reaching
+ *              past it yields a closed surface.)  Vertices on edges that no cube uses (a lattice of
+ *              one point along x or y) are counted and emitted all the same.
+ * The mesh is kept in the context until the next extraction or sph_hip_destroy; steps do not
+ * touch it.  Both calls synchronise; neither changes the simulation (extraction first runs the
+ * cell build sph_hip_voxelize runs, as the sampler does).
+ * sph_hip_extract_surface: SPH_HIP_ERR_INVALID for everything sph_hip_sample_lattice refuses, for
+ * an iso that is not finite or not > 0, and for unknown flag bits; SPH_HIP_ERR_CAPACITY when V or T
+ * would exceed 2^31 - 1 or the mesh cannot be allocated.  Either way no mesh is kept.
+ * sph_hip_download_surface: SPH_HIP_ERR_INVALID when no mesh is kept, or when an output is asked
+ * for that the extraction's flags did not compute. */
+#define SPH_HIP_SURFACE_NORMALS  1
+#define SPH_HIP_SURFACE_VELOCITY 2
+/* meshes the lattice, keeps the mesh in the context; counts[0] = vertices, counts[1] = triangles */
+int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                            const int32_t dims[3], float iso, int flags, int32_t counts[2]);
+/* copies the kept mesh out: vertices_xyz[3V], normals_xyz[3V], velocity_xyz[3V], triangles[3T]; any may be NULL */
+int sph_hip_download_surface(sph_hip_context* ctx, float* vertices_xyz, float* normals_xyz,
+                             float* velocity_xyz, int32_t* triangles);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -18,6 +18,7 @@
 #include "full_tiled.h"
 #include "ref_kernels.h"
 #include "sample_kernels.h"
+#include "surface_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
 
@@ -258,6 +259,21 @@ struct sph_hip_context {
    size_t sample_words = 0;
    int sample_route = 0;           // SAMPLE_ROUTE_*: SPH_HIP_SAMPLE_UNTILED=1 / SPH_HIP_SAMPLE_TILED=1 (tests, A/B runs)
    int sample_lds_set = 0;         // the tiled lattice kernels may take their dynamic LDS on this device
+
+   // iso-surface extractor (sph_hip_extract_surface): one slab's scratch, the running totals per
+   // slab, and the kept mesh (grown on demand, kept until the next extraction or destroy)
+   DevBuf<unsigned char> surf_scratch;
+   size_t surf_scratch_bytes = 0;
+   DevBuf<unsigned long long> surf_totals;   // 4 per slab boundary (k_surf_scan)
+   size_t surf_totals_len = 0;
+   PinnedBuf<unsigned long long> surf_totals_host;   // 4
+   DevBuf<float> surf_vtx, surf_nrm, surf_vel;
+   DevBuf<int32_t> surf_tri;
+   long long surf_vtx_cap = 0, surf_nrm_cap = 0, surf_vel_cap = 0, surf_tri_cap = 0;
+   long long surf_nv = 0, surf_nt = 0;
+   int surf_flags = 0;
+   int surf_kept = 0;
+   int surf_planes_forced = 0;   // SPH_HIP_SURFACE_PLANES=n (tests): planes per slab
 };
 
 namespace {
@@ -318,6 +334,7 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    ctx->sample_route = getenv_flag("SPH_HIP_SAMPLE_UNTILED") ? SAMPLE_ROUTE_UNTILED
                        : getenv_flag("SPH_HIP_SAMPLE_TILED")  ? SAMPLE_ROUTE_TILED
                                                               : SAMPLE_ROUTE_DEFAULT;
+   if (const char* v = getenv("SPH_HIP_SURFACE_PLANES")) ctx->surf_planes_forced = atoi(v) > 0 ? atoi(v) : 0;
    ctx->device = device;
    ctx->capacity = capacity;
 

@@ -68,6 +68,52 @@ int sample_scratch(sph_hip_context* ctx, size_t words)
 // caller can read or a later step computes changes.
 int sample_prepare(sph_hip_context* ctx) { return launch_cell_build(ctx, nullptr, nullptr, true); }
 
+
+// ---- iso-surface extractor (surface_kernels.h; decisions: surface_policy.h) ------------------------
+
+// Grow a mesh array to hold `need` elements, keeping its first `keep` (the stream is idle).
+template <class T>
+int surf_grow(sph_hip_context* ctx, DevBuf<T>& buf, long long& cap, long long need, long long keep)
+{
+   if (need <= cap) return SPH_HIP_OK;
+   long long n = cap + cap / 2;
+   if (n < need) n = need;
+   if (n < 4096) n = 4096;
+   DevBuf<T> fresh;
+   if (dev_alloc(fresh, (size_t)n) != hipSuccess) {
+      (void)hipGetLastError();
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   if (keep > 0) SPH_TRY(hipMemcpy(fresh.get(), buf.get(), sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice));
+   buf = std::move(fresh);
+   cap = n;
+   return SPH_HIP_OK;
+}
+
+// the slab scratch and the totals array, grown on demand
+int surf_scratch_alloc(sph_hip_context* ctx, size_t bytes, size_t totals)
+{
+   if (bytes > ctx->surf_scratch_bytes) {
+      SPH_TRY(hipStreamSynchronize(ctx->stream));
+      ctx->surf_scratch.reset();
+      ctx->surf_scratch_bytes = 0;
+      if (dev_alloc(ctx->surf_scratch, bytes) != hipSuccess) {
+         (void)hipGetLastError();
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      ctx->surf_scratch_bytes = bytes;
+   }
+   if (totals > ctx->surf_totals_len) {
+      SPH_TRY(hipStreamSynchronize(ctx->stream));
+      ctx->surf_totals.reset();
+      ctx->surf_totals_len = 0;
+      SPH_TRY(dev_alloc(ctx->surf_totals, totals));
+      ctx->surf_totals_len = totals;
+   }
+   if (!ctx->surf_totals_host) SPH_TRY(pinned_alloc(ctx->surf_totals_host, 4));
+   return SPH_HIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1097,6 +1143,212 @@ int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const fl
             if (velocity_xyz) SPH_TRY(copy_out(velocity_xyz, svel, 3 * sizeof(float)));
             if (count) SPH_TRY(copy_out(count, scnt, sizeof(int32_t)));
          }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// ---- iso-surface extractor ------------------------------------------------------------------------
+
+int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const float spacing[3], const int32_t dims[3],
+                            float iso, int flags, int32_t counts[2])
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   // the old mesh goes first: a refused or failed extraction keeps nothing
+   ctx->surf_kept = 0;
+   ctx->surf_nv = ctx->surf_nt = 0;
+   if (!origin || !spacing || !dims) {
+      ctx->err = "sph_hip_extract_surface: null origin, spacing or dims";
+      return SPH_HIP_ERR_INVALID;
+   }
+   long long total = 1;
+   for (int a = 0; a < 3; a++) {
+      if (dims[a] <= 0 || !std::isfinite(origin[a]) || !std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) {
+         ctx->err = "sph_hip_extract_surface: dims must be positive, the origin finite, the spacing finite and positive";
+         return SPH_HIP_ERR_INVALID;
+      }
+      total *= dims[a];
+      if (total > 0x7fffffffll) {
+         ctx->err = "sph_hip_extract_surface: more than 2^31 - 1 lattice points";
+         return SPH_HIP_ERR_INVALID;
+      }
+   }
+   if (!std::isfinite(iso) || !(iso > 0.0f)) {
+      ctx->err = "sph_hip_extract_surface: iso must be finite and positive";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (flags & ~(SPH_HIP_SURFACE_NORMALS | SPH_HIP_SURFACE_VELOCITY)) {
+      ctx->err = "sph_hip_extract_surface: unknown flag bits";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if ((rc = sample_check(ctx, "sph_hip_extract_surface"))) return rc;
+   ctx->surf_flags = flags;
+   const bool normals = (flags & SPH_HIP_SURFACE_NORMALS) != 0, vel = (flags & SPH_HIP_SURFACE_VELOCITY) != 0;
+   if (ctx->n == 0) {
+      // nothing resident: the density is 0 everywhere, nothing is inside (iso > 0)
+      ctx->surf_kept = 1;
+      if (counts) counts[0] = counts[1] = 0;
+      return SPH_HIP_OK;
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+
+   const int nx = dims[0], ny = dims[1], nz = dims[2];
+   const int P = surf_planes(dims, vel, ctx->surf_planes_forced);
+   const SurfScratch sz = surf_scratch(dims, P, vel);
+   if (sz.classified > SURF_MAX_SLAB_POINTS) {
+      ctx->err = "sph_hip_extract_surface: lattice planes too large to mesh";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   const int nslabs = div_up(nz, P);
+   if ((rc = surf_scratch_alloc(ctx, (size_t)sz.bytes, 4 * (size_t)(nslabs + 1)))) {
+      if (rc == SPH_HIP_ERR_CAPACITY) ctx->err = "sph_hip_extract_surface: cannot allocate the slab scratch";
+      return rc;
+   }
+   // scratch layout (surface_policy.h: surf_scratch)
+   unsigned char* p = ctx->surf_scratch;
+   auto carve = [&](long long bytes) {
+      unsigned char* q = p;
+      p += surf_round256(bytes);
+      return q;
+   };
+   float* srho = reinterpret_cast<float*>(carve(sz.sampled * 4));
+   int32_t* scnt = reinterpret_cast<int32_t*>(carve(sz.sampled * 4));
+   float* svel = vel ? reinterpret_cast<float*>(carve(sz.sampled * 12)) : nullptr;
+   uint8_t* codes = carve(sz.classified);
+   int32_t* vbase = reinterpret_cast<int32_t*>(carve(sz.classified * 4));
+   int2* active = reinterpret_cast<int2*>(carve(sz.own * 8));
+   uint32_t* bsum_pack = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
+   uint32_t* bsum_vown = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
+   uint32_t* boff_v = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
+   uint32_t* boff_t = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
+   uint32_t* boff_a = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
+   unsigned long long* totals = ctx->surf_totals;
+   unsigned long long* host = ctx->surf_totals_host;
+
+   const double cells[3] = {spacing[0] * (double)ctx->grid.inv, spacing[1] * (double)ctx->grid.inv,
+                            spacing[2] * (double)ctx->grid.inv};
+   const SampleBrick brick = sample_brick(dims, cells);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const bool unit = unit_scale(ctx->prm);
+   hipStream_t st = ctx->stream;
+   SPH_TRY(hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), st));
+
+   SurfSlab S;
+   S.nx = nx;
+   S.ny = ny;
+   S.nz = nz;
+   S.plane = nx * ny;
+   S.ox = origin[0];
+   S.oy = origin[1];
+   S.oz = origin[2];
+   S.sx = spacing[0];
+   S.sy = spacing[1];
+   S.sz = spacing[2];
+   S.iso = iso;
+   SampleLattice L;
+   L.ox = origin[0];
+   L.oy = origin[1];
+   L.oz = origin[2];
+   L.sx = spacing[0];
+   L.sy = spacing[1];
+   L.sz = spacing[2];
+   L.bx = brick.bx;
+   L.by = brick.by;
+   L.bz = brick.bz;
+   L.i0 = L.j0 = 0;
+   L.ex = nx;
+   L.ey = ny;
+   L.bricks_x = div_up(nx, L.bx);
+   L.bricks_y = div_up(ny, L.by);
+   long long nv = 0, nt = 0;   // vertices and triangles before the slab
+   for (int s = 0; s < nslabs; s++) {
+      S.k0 = s * P;
+      S.own = nz - S.k0 < P ? nz - S.k0 : P;
+      S.cls = nz - S.k0 < P + 1 ? nz - S.k0 : P + 1;
+      S.ks0 = S.k0 - SURF_HALO_BELOW < 0 ? 0 : S.k0 - SURF_HALO_BELOW;
+      const int ks1 = S.k0 + P + SURF_HALO_ABOVE < nz ? S.k0 + P + SURF_HALO_ABOVE : nz;
+      // 1. density (+ velocity) of the slab's planes and halo: the sampler's kernel and bits
+      L.k0 = S.ks0;
+      L.ez = ks1 - S.ks0;
+      const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
+      bind_flags([&](auto U, auto V) {
+         hipLaunchKernelGGL((k_sample_lattice<U.value, V.value, false>), dim3(bricks), dim3(SAMPLE_THREADS), 0, st, L,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid, k, SAMPLE_TILE_CAP,
+                            srho, svel, scnt);
+      }, unit, vel);
+      SPH_TRY(hipGetLastError());
+      // 2. classify, 3. scan
+      const int pts = S.cls * S.plane;
+      const int nb = div_up(pts, SURF_THREADS);
+      hipLaunchKernelGGL(k_surf_classify, dim3(nb), dim3(SURF_THREADS), 0, st, S, srho, codes, bsum_pack, bsum_vown);
+      SPH_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_surf_scan, dim3(1), dim3(SURF_THREADS), 0, st, nb, bsum_pack, bsum_vown, boff_v, boff_t,
+                         boff_a, totals + 4 * (size_t)s, totals + 4 * (size_t)(s + 1));
+      SPH_TRY(hipGetLastError());
+      // the slab's totals: the mesh arrays must hold them before anything is emitted
+      SPH_TRY(hipMemcpyAsync(host, totals + 4 * (size_t)(s + 1), 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             st));
+      SPH_TRY(hipStreamSynchronize(st));
+      const long long nv_next = (long long)host[0], nt_next = (long long)host[1];
+      const int nactive = (int)host[2];
+      if (nv + (long long)host[3] > 0x7fffffffll || nt_next > 0x7fffffffll) {
+         ctx->err = "sph_hip_extract_surface: more than 2^31 - 1 vertices or triangles";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      rc = surf_grow(ctx, ctx->surf_vtx, ctx->surf_vtx_cap, 3 * nv_next, 3 * nv);
+      if (!rc && normals) rc = surf_grow(ctx, ctx->surf_nrm, ctx->surf_nrm_cap, 3 * nv_next, 3 * nv);
+      if (!rc && vel) rc = surf_grow(ctx, ctx->surf_vel, ctx->surf_vel_cap, 3 * nv_next, 3 * nv);
+      if (!rc) rc = surf_grow(ctx, ctx->surf_tri, ctx->surf_tri_cap, 3 * nt_next, 3 * nt);
+      if (rc) {
+         if (rc == SPH_HIP_ERR_CAPACITY) ctx->err = "sph_hip_extract_surface: cannot allocate the mesh";
+         return rc;
+      }
+      // 4. vertex bases, active cubes, vertices, 5. triangles
+      bind_flags([&](auto N, auto V) {
+         hipLaunchKernelGGL((k_surf_vertices<N.value, V.value>), dim3(nb), dim3(SURF_THREADS), 0, st, S, srho, svel,
+                            codes, boff_v, boff_t, boff_a, totals + 4 * (size_t)s, vbase, active, ctx->surf_vtx.get(),
+                            ctx->surf_nrm.get(), ctx->surf_vel.get());
+      }, normals, vel);
+      SPH_TRY(hipGetLastError());
+      if (nactive > 0) {
+         hipLaunchKernelGGL(k_surf_triangles, dim3(div_up(nactive, SURF_THREADS)), dim3(SURF_THREADS), 0, st, S, codes,
+                            vbase, active, nactive, ctx->surf_tri.get());
+         SPH_TRY(hipGetLastError());
+      }
+      nv = nv_next;
+      nt = nt_next;
+   }
+   SPH_TRY(hipStreamSynchronize(st));
+   ctx->surf_nv = nv;
+   ctx->surf_nt = nt;
+   ctx->surf_kept = 1;
+   if (counts) {
+      counts[0] = (int32_t)nv;
+      counts[1] = (int32_t)nt;
+   }
+   return SPH_HIP_OK;
+}
+
+int sph_hip_download_surface(sph_hip_context* ctx, float* vertices_xyz, float* normals_xyz, float* velocity_xyz,
+                             int32_t* triangles)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!ctx->surf_kept) {
+      ctx->err = "sph_hip_download_surface: no mesh is kept (extract one first)";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if ((normals_xyz && !(ctx->surf_flags & SPH_HIP_SURFACE_NORMALS)) ||
+       (velocity_xyz && !(ctx->surf_flags & SPH_HIP_SURFACE_VELOCITY))) {
+      ctx->err = "sph_hip_download_surface: the extraction did not compute normals / velocity";
+      return SPH_HIP_ERR_INVALID;
+   }
+   hipStream_t st = ctx->stream;
+   const size_t v3 = 3 * (size_t)ctx->surf_nv, t3 = 3 * (size_t)ctx->surf_nt;
+   if (vertices_xyz && v3) SPH_TRY(hipMemcpyAsync(vertices_xyz, ctx->surf_vtx.get(), sizeof(float) * v3, hipMemcpyDeviceToHost, st));
+   if (normals_xyz && v3) SPH_TRY(hipMemcpyAsync(normals_xyz, ctx->surf_nrm.get(), sizeof(float) * v3, hipMemcpyDeviceToHost, st));
+   if (velocity_xyz && v3) SPH_TRY(hipMemcpyAsync(velocity_xyz, ctx->surf_vel.get(), sizeof(float) * v3, hipMemcpyDeviceToHost, st));
+   if (triangles && t3) SPH_TRY(hipMemcpyAsync(triangles, ctx->surf_tri.get(), sizeof(int32_t) * t3, hipMemcpyDeviceToHost, st));
    SPH_TRY(hipStreamSynchronize(st));
    return SPH_HIP_OK;
 }

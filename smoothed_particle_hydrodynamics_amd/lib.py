@@ -96,6 +96,9 @@ PROTOTYPES = {
     "sph_hip_sample_points": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_sample_lattice": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3),
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_extract_surface": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3), C.c_float,
+                                          C.c_int, _P(C.c_int32 * 2)]),
+    "sph_hip_download_surface": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

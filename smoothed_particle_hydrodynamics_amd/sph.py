@@ -6,13 +6,14 @@ src/sph.h:20-139) so that code and tests written against the reference read the 
 src/particle.h:7-20: one object for all particles, xyz interleaved).  All computation
 happens in libsph_hip.so on the GPU; this file only moves arrays and parameters.
 """
+import collections
 import ctypes as C
 
 import numpy as np
 
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, SphHipError, SphParams, default_params, load_library
 
-__all__ = ["SPH", "Particle", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
+__all__ = ["SPH", "Particle", "SurfaceMesh", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
 
 class Particle:
@@ -26,6 +27,13 @@ class Particle:
         self.mVelocity = np.zeros(3 * n, np.float32)
         self.mAcceleration = np.zeros(3 * n, np.float32)
         self.mNeighborCount = np.zeros(n, np.int32)
+
+
+SURFACE_NORMALS, SURFACE_VELOCITY = 1, 2   # SPH_HIP_SURFACE_* (include/sph_hip.h)
+
+# sph_hip_extract_surface's mesh: vertices (V, 3) float32, triangles (T, 3) int32, normals and
+# velocity (V, 3) float32 or None where not asked for
+SurfaceMesh = collections.namedtuple("SurfaceMesh", ["vertices", "triangles", "normals", "velocity"])
 
 
 def _ptr(a):
@@ -302,6 +310,28 @@ class SPH:
                                                      _ptr(vel), _ptr(cnt)), "sph_hip_sample_lattice")
         return rho, vel, cnt
 
+    def extractSurface(self, origin, spacing, shape, iso, normals=True, velocity=False):
+        """The surface {density > iso} of the lattice sampleLattice(origin, spacing, shape) would
+        give, meshed on the device (include/sph_hip.h: iso-surface extractor): a SurfaceMesh of
+        numpy arrays.  The mesh stays in the context until the next extraction."""
+        o = (C.c_float * 3)(*[float(v) for v in origin])
+        s = (C.c_float * 3)(*[float(v) for v in spacing])
+        dims = [int(v) for v in shape]
+        if len(dims) != 3 or len(o) != 3 or len(s) != 3:
+            raise ValueError("origin, spacing and shape take three values each")
+        flags = (SURFACE_NORMALS if normals else 0) | (SURFACE_VELOCITY if velocity else 0)
+        counts = (C.c_int32 * 2)()
+        self._check(self._lib.sph_hip_extract_surface(self._ctx, C.byref(o), C.byref(s), C.byref((C.c_int32 * 3)(*dims)),
+                                                      float(iso), flags, C.byref(counts)), "sph_hip_extract_surface")
+        nv, nt = counts[0], counts[1]
+        vtx = np.zeros((nv, 3), np.float32)
+        tri = np.zeros((nt, 3), np.int32)
+        nrm = np.zeros((nv, 3), np.float32) if normals else None
+        vel = np.zeros((nv, 3), np.float32) if velocity else None
+        self._check(self._lib.sph_hip_download_surface(self._ctx, _ptr(vtx), _ptr(nrm), _ptr(vel), _ptr(tri)),
+                    "sph_hip_download_surface")
+        return SurfaceMesh(vtx, tri, nrm, vel)
+
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
         """The six numbers of SPH::updateElapsed (reference src/sph.cpp:292-299), in ms."""
@@ -371,3 +401,29 @@ class SPH:
         self._check(self._lib.sph_hip_download_neighbor_lists(self._ctx, _ptr(nb), _ptr(nd)),
                     "sph_hip_download_neighbor_lists")
         return nb, nd
+
+
+def write_ply(path, mesh):
+    """Write a SurfaceMesh (or any object with .vertices, .triangles and an optional .normals) as
+    binary little-endian PLY: x y z [nx ny nz] float per vertex, a uchar-counted int list per face."""
+    v = np.ascontiguousarray(mesh.vertices, np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(mesh.triangles, np.int32).reshape(-1, 3)
+    n = getattr(mesh, "normals", None)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if n is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    vert = np.empty(len(v), dtype=fields)
+    vert["x"], vert["y"], vert["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if n is not None:
+        n = np.asarray(n, np.float32).reshape(-1, 3)
+        vert["nx"], vert["ny"], vert["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    face = np.empty(len(t), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+    face["n"] = 3
+    face["i"] = t
+    head = ["ply", "format binary_little_endian 1.0", "element vertex %d" % len(v)]
+    head += ["property float %s" % name for name, _ in fields]
+    head += ["element face %d" % len(t), "property list uchar int vertex_indices", "end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(head) + "\n").encode("ascii"))
+        f.write(vert.tobytes())
+        f.write(face.tobytes())
