@@ -365,6 +365,73 @@ int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const f
 int sph_hip_download_surface(sph_hip_context* ctx, float* vertices_xyz, float* normals_xyz,
                              float* velocity_xyz, int32_t* triangles);
 
+/* ---- renderer ----------------------------------------------------------------------------- *
+ *
+ * A ray-marched image of the fluid's surface {f > iso}, where f(p) is the density
+ * sph_hip_sample_points would return at p at that moment (hence the same image in FULL and
+ * FULL_FAST, and one that agrees with the sampler and the extractor).  All arithmetic is fp32,
+ * unfused, in the order written; fminf / fmaxf follow C99 (a NaN operand yields the other one).
+ *   pixel ray  pixel (px, py) of a W x H image, row 0 at the top:
+ *              a = (float)(2*px + 1 - W) / (float)W, b = (float)(H - 2*py - 1) / (float)H;
+ *              d_c = (forward_c + a * right_c) + b * up_c per component;
+ *              len = sqrtf((dx*dx + dy*dy) + dz*dz); the direction is d_c / len per component.
+ *              A pixel whose len is 0 or not finite misses.
+ *   box        per axis: inv = 1.0f / d, t0 = (lo - eye) * inv, t1 = (hi - eye) * inv,
+ *              near = fminf(t0, t1), far = fmaxf(t0, t1);
+ *              tnear = fmaxf(fmaxf(fmaxf(near_x, near_y), near_z), 0.0f),
+ *              tfar = fminf(fminf(far_x, far_y), far_z).  The ray misses unless tnear <= tfar.
+ *   march      t_k = tnear + (float)k * step, p_k = eye + t_k * d per component, for k = 0, 1, ...
+ *              while t_k <= tfar and k < max_samples.  The first k with f(p_k) > iso (strictly;
+ *              NaN is outside) is first_inside; if no sample is inside, the ray misses.
+ *   refine     k = 0: t_hit = tnear.  Otherwise ta = t_(k-1), tb = t_k, and `refine` times:
+ *              tm = 0.5f * (ta + tb); tb = tm if f(eye + tm * d) > iso, else ta = tm.
+ *              t_hit = tb; p_hit = eye + t_hit * d per component.
+ *   normal     g_a = (f(p_hit + e_a) - f(p_hit - e_a)) / (2.0f * grad_step) per axis, where
+ *              p_hit + e_a moves coordinate a alone by grad_step;
+ *              len = sqrtf((gx*gx + gy*gy) + gz*gz); the normal is -(g / len) per component
+ *              when len is finite and > 0, else 0 (it points toward lower density).
+ *   shade      l = light / sqrtf((lx*lx + ly*ly) + lz*lz) per component;
+ *              ndl = (nx*lx + ny*ly) + nz*lz; w = ambient + diffuse * fmaxf(ndl, 0.0f);
+ *              channel c = (uint8_t)(fminf(fmaxf(albedo_c * w, 0.0f), 1.0f) * 255.0f + 0.5f);
+ *              alpha 255.  A miss is `background`.
+ *   outputs    one entry per pixel, row-major (index py * W + px), host memory, each may be NULL
+ *              (with all of them NULL the frame is still computed: timing):
+ *              rgba[4], depth (t_hit; +inf on a miss), normal_xyz[3] (0 on a miss),
+ *              velocity_xyz[3] (the sampler's Shepard velocity at p_hit with
+ *              SPH_HIP_RENDER_VELOCITY; 0 on a miss, and everywhere without the flag),
+ *              first_inside (k; -1 on a miss).
+ * Each call first brings the cell structure up to date (the build sph_hip_voxelize runs) and
+ * synchronises before it returns; it does not change the simulation (sph_hip_download returns the
+ * same bytes before and after it, and every later step is bit-identical to one without it).
+ * SPH_HIP_ERR_INVALID, with a last_error text, for a REF or slab context (as the sampler), null
+ * camera or params, width or height outside [1, 16384], a non-finite camera or params field, a
+ * step or grad_step that is not > 0, an iso that is not > 0, refine outside [0, 30],
+ * box_lo >= box_hi on an axis, a zero light vector, max_samples outside [1, 2^24], and unknown
+ * flag bits. */
+typedef struct sph_hip_camera {          /* field order is ABI */
+   float eye[3];
+   float forward[3];   /* toward the image centre, any length */
+   float right[3];     /* image-plane half-width at unit forward distance */
+   float up[3];        /* image-plane half-height at unit forward distance */
+} sph_hip_camera;
+
+typedef struct sph_hip_render_params {   /* field order is ABI */
+   float box_lo[3], box_hi[3];   /* the volume that is marched */
+   float step;                   /* march step, world units */
+   float iso;                    /* surface level */
+   int32_t refine;               /* bisection iterations */
+   float grad_step;              /* offset of the central differences */
+   float light[3];               /* direction toward the light */
+   float albedo[3], ambient, diffuse;
+   uint8_t background[4];        /* RGBA of a pixel whose ray misses */
+   int32_t max_samples;          /* march samples per ray at most */
+} sph_hip_render_params;
+
+#define SPH_HIP_RENDER_VELOCITY 1
+int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                   int width, int height, int flags, uint8_t* rgba, float* depth,
+                   float* normal_xyz, float* velocity_xyz, int32_t* first_inside);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -19,6 +19,7 @@
 #include "ref_kernels.h"
 #include "sample_kernels.h"
 #include "surface_kernels.h"
+#include "render_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
 
@@ -274,6 +275,14 @@ struct sph_hip_context {
    int surf_flags = 0;
    int surf_kept = 0;
    int surf_planes_forced = 0;   // SPH_HIP_SURFACE_PLANES=n (tests): planes per slab
+
+   // renderer (sph_hip_render): one row chunk's scratch and the occupancy map (a byte per FULL cell),
+   // grown on demand
+   DevBuf<unsigned char> render_scratch;
+   size_t render_scratch_bytes = 0;
+   DevBuf<unsigned char> render_occ;
+   size_t render_occ_len = 0;
+   int render_noskip = 0;   // SPH_HIP_RENDER_NOSKIP=1 (tests, A/B runs): every sample walks
 };
 
 namespace {
@@ -335,6 +344,7 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
                        : getenv_flag("SPH_HIP_SAMPLE_TILED")  ? SAMPLE_ROUTE_TILED
                                                               : SAMPLE_ROUTE_DEFAULT;
    if (const char* v = getenv("SPH_HIP_SURFACE_PLANES")) ctx->surf_planes_forced = atoi(v) > 0 ? atoi(v) : 0;
+   ctx->render_noskip = getenv_flag("SPH_HIP_RENDER_NOSKIP");
    ctx->device = device;
    ctx->capacity = capacity;
 

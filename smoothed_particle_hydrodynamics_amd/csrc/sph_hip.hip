@@ -1353,6 +1353,116 @@ int sph_hip_download_surface(sph_hip_context* ctx, float* vertices_xyz, float* n
    return SPH_HIP_OK;
 }
 
+// ---- renderer -------------------------------------------------------------------------------------
+
+int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp, int width,
+                   int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
+                   int32_t* first_inside)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if ((rc = sample_check(ctx, "sph_hip_render"))) return rc;
+   if (const char* why = render_check(cam, rp, width, height, flags)) {
+      ctx->err = std::string("sph_hip_render: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   const size_t pixels = (size_t)width * height;
+   const bool vel = (flags & SPH_HIP_RENDER_VELOCITY) != 0;
+   if (velocity_xyz && !vel) memset(velocity_xyz, 0, sizeof(float) * 3 * pixels);
+   if (ctx->n == 0) {
+      // nothing resident (the cell arrays may still describe an earlier upload): every ray misses
+      for (size_t i = 0; i < pixels; i++) {
+         if (rgba) memcpy(rgba + 4 * i, rp->background, 4);
+         if (depth) depth[i] = INFINITY;
+         if (first_inside) first_inside[i] = -1;
+      }
+      if (normal_xyz) memset(normal_xyz, 0, sizeof(float) * 3 * pixels);
+      if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * pixels);
+      return SPH_HIP_OK;
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   hipStream_t st = ctx->stream;
+   const CellGrid& g = ctx->grid;
+   const bool skip = !ctx->render_noskip;
+   if (skip) {
+      if ((size_t)g.ncells > ctx->render_occ_len) {
+         SPH_TRY(hipStreamSynchronize(st));
+         ctx->render_occ.reset();
+         ctx->render_occ_len = 0;
+         SPH_TRY(dev_alloc(ctx->render_occ, (size_t)g.ncells));
+         ctx->render_occ_len = (size_t)g.ncells;
+      }
+      hipLaunchKernelGGL(k_render_occupancy, dim3(div_up(g.ncells, RENDER_THREADS)), dim3(RENDER_THREADS), 0, st,
+                         ctx->cell_start, g, ctx->render_occ.get());
+      SPH_TRY(hipGetLastError());
+   }
+   // scratch of one row chunk (render_policy.h)
+   const int rows = render_chunk_rows(width, height);
+   const size_t bytes = (size_t)render_scratch_bytes(width, rows);
+   if (bytes > ctx->render_scratch_bytes) {
+      SPH_TRY(hipStreamSynchronize(st));
+      ctx->render_scratch.reset();
+      ctx->render_scratch_bytes = 0;
+      if (dev_alloc(ctx->render_scratch, bytes) != hipSuccess) {
+         (void)hipGetLastError();
+         ctx->err = "sph_hip_render: cannot allocate the chunk scratch";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      ctx->render_scratch_bytes = bytes;
+   }
+   const long long cp = (long long)width * rows;
+   unsigned char* base = ctx->render_scratch.get();
+   size_t off = 0;
+   auto carve = [&](long long n) {
+      unsigned char* q = base + off;
+      off += (size_t)render_round256(n);
+      return q;
+   };
+   uint32_t* s_rgba = reinterpret_cast<uint32_t*>(carve(cp * 4));
+   float* s_depth = reinterpret_cast<float*>(carve(cp * 4));
+   float* s_nrm = reinterpret_cast<float*>(carve(cp * 12));
+   float* s_vel = reinterpret_cast<float*>(carve(cp * 12));
+   int32_t* s_first = reinterpret_cast<int32_t*>(carve(cp * 4));
+   int32_t* s_hits = reinterpret_cast<int32_t*>(carve(cp * 4));
+   uint32_t* s_count = reinterpret_cast<uint32_t*>(carve(256));
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const bool unit = unit_scale(ctx->prm);
+   const unsigned char* occ = skip ? ctx->render_occ.get() : nullptr;
+   RenderFrame F;
+   F.cam = *cam;
+   F.rp = *rp;
+   F.width = width;
+   F.height = height;
+   F.tiles_x = div_up(width, RENDER_TILE);
+   for (F.row0 = 0; F.row0 < height; F.row0 += rows) {
+      F.rows = height - F.row0 < rows ? height - F.row0 : rows;
+      const int chunk = width * F.rows;
+      const int tiles = F.tiles_x * div_up(F.rows, RENDER_TILE);
+      SPH_TRY(hipMemsetAsync(s_count, 0, sizeof(uint32_t), st));
+      bind_flags([&](auto U, auto S) {
+         hipLaunchKernelGGL((k_render_march<U.value, S.value>), dim3(div_up(tiles, RENDER_THREADS / SPH_WAVE)),
+                            dim3(RENDER_THREADS), 0, st, F, ctx->posm[ctx->cur], ctx->cell_start, g, k, occ, s_rgba,
+                            s_depth, s_nrm, s_vel, s_first, s_hits, s_count);
+      }, unit, skip);
+      SPH_TRY(hipGetLastError());
+      bind_flags([&](auto U, auto S, auto V) {
+         hipLaunchKernelGGL((k_render_shade<U.value, S.value, V.value>), dim3(div_up(chunk, RENDER_THREADS)),
+                            dim3(RENDER_THREADS), 0, st, F, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start,
+                            g, k, occ, s_hits, s_count, s_first, s_rgba, s_depth, s_nrm, s_vel);
+      }, unit, skip, vel);
+      SPH_TRY(hipGetLastError());
+      const size_t o = (size_t)F.row0 * width;
+      if (rgba) SPH_TRY(hipMemcpyAsync(rgba + 4 * o, s_rgba, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
+      if (depth) SPH_TRY(hipMemcpyAsync(depth + o, s_depth, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
+      if (normal_xyz) SPH_TRY(hipMemcpyAsync(normal_xyz + 3 * o, s_nrm, (size_t)chunk * 12, hipMemcpyDeviceToHost, st));
+      if (velocity_xyz && vel)
+         SPH_TRY(hipMemcpyAsync(velocity_xyz + 3 * o, s_vel, (size_t)chunk * 12, hipMemcpyDeviceToHost, st));
+      if (first_inside) SPH_TRY(hipMemcpyAsync(first_inside + o, s_first, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
+   }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
 void* sph_hip_stream(sph_hip_context* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
 
 } // extern "C"

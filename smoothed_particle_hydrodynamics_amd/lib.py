@@ -54,6 +54,24 @@ class SphParams(C.Structure):
         return out
 
 
+class SphCamera(C.Structure):
+    """Mirror of sph_hip_camera (include/sph_hip.h: renderer)."""
+
+    _fields_ = [("eye", C.c_float * 3), ("forward", C.c_float * 3), ("right", C.c_float * 3),
+                ("up", C.c_float * 3)]
+
+
+class SphRenderParams(C.Structure):
+    """Mirror of sph_hip_render_params (include/sph_hip.h: renderer)."""
+
+    _fields_ = [
+        ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3),
+        ("step", C.c_float), ("iso", C.c_float), ("refine", C.c_int32), ("grad_step", C.c_float),
+        ("light", C.c_float * 3), ("albedo", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float),
+        ("background", C.c_uint8 * 4), ("max_samples", C.c_int32),
+    ]
+
+
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -99,6 +117,8 @@ PROTOTYPES = {
     "sph_hip_extract_surface": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3), C.c_float,
                                           C.c_int, _P(C.c_int32 * 2)]),
     "sph_hip_download_surface": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_render": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -8,12 +8,15 @@ happens in libsph_hip.so on the GPU; this file only moves arrays and parameters.
 """
 import collections
 import ctypes as C
+import math
+import struct
+import zlib
 
 import numpy as np
 
-from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, SphHipError, SphParams, default_params, load_library
+from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, SphCamera, SphHipError, SphParams, SphRenderParams, default_params, load_library
 
-__all__ = ["SPH", "Particle", "SurfaceMesh", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
+__all__ = ["SPH", "Particle", "SurfaceMesh", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
 
 class Particle:
@@ -34,6 +37,47 @@ SURFACE_NORMALS, SURFACE_VELOCITY = 1, 2   # SPH_HIP_SURFACE_* (include/sph_hip.
 # sph_hip_extract_surface's mesh: vertices (V, 3) float32, triangles (T, 3) int32, normals and
 # velocity (V, 3) float32 or None where not asked for
 SurfaceMesh = collections.namedtuple("SurfaceMesh", ["vertices", "triangles", "normals", "velocity"])
+
+
+RENDER_VELOCITY = 1   # SPH_HIP_RENDER_VELOCITY (include/sph_hip.h)
+
+# sph_hip_render's frame: rgba (H, W, 4) uint8, depth (H, W) float32, normal (H, W, 3) float32,
+# velocity (H, W, 3) float32 or None where not asked for, first_inside (H, W) int32
+RenderResult = collections.namedtuple("RenderResult", ["rgba", "depth", "normal", "velocity", "first_inside"])
+
+
+class Camera:
+    """sph_hip_camera: the eye and three fp32 vectors (include/sph_hip.h: renderer).  Pixel (px, py)
+    looks along forward + a * right + b * up, a and b in (-1, 1) across the image."""
+
+    def __init__(self, eye, forward, right, up):
+        self.eye, self.forward, self.right, self.up = (np.array(v, np.float32).reshape(3)
+                                                       for v in (eye, forward, right, up))
+
+    @classmethod
+    def look_at(cls, eye, target, up, fov_y_deg, width, height):
+        """A pinhole camera at `eye` looking at `target`, `up` giving the image's vertical, with a
+        vertical field of view of fov_y_deg and square pixels: computed in float64, then rounded to
+        the four fp32 vectors (unit forward; right and up scaled to the image plane's half extents)."""
+        e = np.asarray(eye, np.float64).reshape(3)
+        f = np.asarray(target, np.float64).reshape(3) - e
+        if not np.linalg.norm(f) > 0:
+            raise ValueError("eye and target coincide")
+        f = f / np.linalg.norm(f)
+        r = np.cross(f, np.asarray(up, np.float64).reshape(3))
+        if not np.linalg.norm(r) > 0:
+            raise ValueError("up is parallel to the view direction")
+        r = r / np.linalg.norm(r)
+        u = np.cross(r, f)
+        half_h = math.tan(math.radians(float(fov_y_deg)) / 2.0)
+        half_w = half_h * float(width) / float(height)
+        return cls(e, f, r * half_w, u * half_h)
+
+    def as_struct(self):
+        c = SphCamera()
+        for name in ("eye", "forward", "right", "up"):
+            getattr(c, name)[:] = [float(v) for v in getattr(self, name)]
+        return c
 
 
 def _ptr(a):
@@ -332,6 +376,54 @@ class SPH:
                     "sph_hip_download_surface")
         return SurfaceMesh(vtx, tri, nrm, vel)
 
+    # ---- renderer (sph_hip_render) ------------------------------------------------------------------
+    def renderParams(self, iso, step=None, refine=8, grad_step=None, box=None, light=(0.4, 0.8, 0.45),
+                     albedo=(0.25, 0.55, 0.9), ambient=0.2, diffuse=0.8, background=(0, 0, 0, 255),
+                     max_samples=1 << 16):
+        """The sph_hip_render_params of render(...)'s arguments, defaults filled in."""
+        f = np.float32
+        h = f(self._params.h)
+        if box is None:
+            top = np.array(self.getParticleBounds(), f)
+            box = (np.full(3, f(0.0) - h, f), (top + h).astype(f))
+        rp = SphRenderParams()
+        rp.box_lo[:] = [float(v) for v in np.asarray(box[0], f).reshape(3)]
+        rp.box_hi[:] = [float(v) for v in np.asarray(box[1], f).reshape(3)]
+        rp.step = float(f(0.5) * h) if step is None else float(step)
+        rp.iso = float(iso)
+        rp.refine = int(refine)
+        rp.grad_step = float(f(0.5) * h) if grad_step is None else float(grad_step)
+        rp.light[:] = [float(v) for v in light]
+        rp.albedo[:] = [float(v) for v in albedo]
+        rp.ambient = float(ambient)
+        rp.diffuse = float(diffuse)
+        rp.background[:] = [int(v) for v in background]
+        rp.max_samples = int(max_samples)
+        return rp
+
+    def render(self, camera, width, height, iso, step=None, refine=8, grad_step=None, box=None,
+               light=(0.4, 0.8, 0.45), albedo=(0.25, 0.55, 0.9), ambient=0.2, diffuse=0.8,
+               background=(0, 0, 0, 255), velocity=False, max_samples=1 << 16):
+        """Ray-march the surface {density > iso} of the current state into a width x height image on
+        the device (include/sph_hip.h: renderer): a RenderResult of numpy arrays.  step and
+        grad_step default to h / 2, the box to the particle bounds [0, max] grown by h on every
+        side; the simulation is not changed by the call."""
+        rp = self.renderParams(iso, step, refine, grad_step, box, light, albedo, ambient, diffuse, background,
+                               max_samples)
+        W, H = int(width), int(height)
+        if W < 1 or H < 1:
+            raise ValueError("width and height must be positive")
+        rgba = np.zeros((H, W, 4), np.uint8)
+        depth = np.zeros((H, W), np.float32)
+        normal = np.zeros((H, W, 3), np.float32)
+        vel = np.zeros((H, W, 3), np.float32) if velocity else None
+        first = np.zeros((H, W), np.int32)
+        cam = camera.as_struct()
+        self._check(self._lib.sph_hip_render(self._ctx, C.byref(cam), C.byref(rp), W, H,
+                                             RENDER_VELOCITY if velocity else 0, _ptr(rgba), _ptr(depth),
+                                             _ptr(normal), _ptr(vel), _ptr(first)), "sph_hip_render")
+        return RenderResult(rgba, depth, normal, vel, first)
+
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
         """The six numbers of SPH::updateElapsed (reference src/sph.cpp:292-299), in ms."""
@@ -427,3 +519,22 @@ def write_ply(path, mesh):
         f.write(("\n".join(head) + "\n").encode("ascii"))
         f.write(vert.tobytes())
         f.write(face.tobytes())
+
+
+def write_png(path, rgba):
+    """Write an (H, W, 4) uint8 RGBA image as an 8-bit RGBA PNG (zlib and struct only; every row
+    with filter 0)."""
+    img = np.ascontiguousarray(rgba, np.uint8)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError("rgba must be (H, W, 4) uint8")
+    H, W = img.shape[0], img.shape[1]
+    raw = np.concatenate([np.zeros((H, 1), np.uint8), img.reshape(H, W * 4)], 1).tobytes()
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 6, 0, 0, 0)))
+        f.write(chunk(b"IDAT", zlib.compress(raw, 6)))
+        f.write(chunk(b"IEND", b""))
