@@ -432,6 +432,47 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
                    int width, int height, int flags, uint8_t* rgba, float* depth,
                    float* normal_xyz, float* velocity_xyz, int32_t* first_inside);
 
+/* ---- static obstacles --------------------------------------------------------------------- *
+ *
+ * Analytic solids inside the domain: spheres, axis-aligned boxes and axis-aligned capped
+ * cylinders, in position units (those of mPosition and max_x/y/z).  No counterpart in the
+ * reference's step: the response generalises SPH::applyBoundary (src/sph.cpp:1124-1148), which the
+ * reference applies to the six walls only.  Inside integrate, after the drift, the kick and the wall
+ * handling (apply_walls), every obstacle in list order tests the particle's new position strictly
+ * (on the surface is outside) and, when it is inside, reflects the particle where the line from its
+ * old position along its new velocity enters the obstacle and moves it on for the rest of the step
+ * scaled by mDamping (the time left is clamped at 0), or, when that line gives no valid entry,
+ * moves it to the nearest surface point and reflects an inward velocity component only.  The
+ * operation-by-operation contract is in csrc/obstacle_policy.h.  The KE term of sph_hip_get_energy
+ * uses the final velocity.  Obstacles carry no density or pressure (the walls do not either); they
+ * do not move.
+ *   sphere    center, radius.
+ *   box       lo, hi.
+ *   cylinder  axis (0 x, 1 y, 2 z), center (its axis component is ignored), radius, and its caps at
+ *             lo[axis], hi[axis].
+ * sph_hip_set_obstacles replaces the whole list (n = 0 clears it), ordered on the context's stream:
+ * steps enqueued before the call keep the old list; `list` may be reused as soon as it returns.  It
+ * is refused with SPH_HIP_ERR_INVALID, and the previous list kept, for an unknown kind, a field that
+ * is not finite (unused fields included), a radius that is not > 0, lo >= hi on a used axis, a
+ * cylinder axis outside 0..2, n < 0, n > SPH_HIP_MAX_OBSTACLES, a null list with n > 0, and on a slab
+ * between sph_hip_slab_step_begin and sph_hip_slab_step_end.  Valid in REF, FULL and FULL_FAST and on
+ * slab contexts; without obstacles every step is bit-identical to one on a context that never had any.
+ * sph_hip_get_obstacles copies up to `capacity` entries to `out` (NULL with capacity 0) and returns
+ * how many the context holds (or a negative status). */
+#define SPH_HIP_OBSTACLE_SPHERE   0
+#define SPH_HIP_OBSTACLE_BOX      1
+#define SPH_HIP_OBSTACLE_CYLINDER 2
+#define SPH_HIP_MAX_OBSTACLES     64
+typedef struct sph_hip_obstacle {   /* field order is ABI: 48 bytes */
+   int32_t kind;                    /* SPH_HIP_OBSTACLE_* */
+   int32_t axis;                    /* cylinder only */
+   float center[3];                 /* sphere, cylinder */
+   float radius;                    /* sphere, cylinder */
+   float lo[3], hi[3];              /* box; cylinder: its caps on `axis` */
+} sph_hip_obstacle;
+int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, int n);
+int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -283,6 +283,16 @@ struct sph_hip_context {
    DevBuf<unsigned char> render_occ;
    size_t render_occ_len = 0;
    int render_noskip = 0;   // SPH_HIP_RENDER_NOSKIP=1 (tests, A/B runs): every sample walks
+
+   // static obstacles (sph_hip_set_obstacles): the list the next enqueued steps use, its device copy,
+   // and the pinned staging of that copy (reused only after the event behind the last copy)
+   sph_hip_obstacle obst_host[SPH_HIP_MAX_OBSTACLES];
+   int n_obst = 0;
+   DevBuf<sph_hip_obstacle> obst_dev;
+   PinnedBuf<sph_hip_obstacle> obst_stage;
+   Event ev_obst_copied;
+   int obst_copy_pending = 0;
+   int slab_step_open = 0;         // between sph_hip_slab_step_begin and _end (the list must not change)
 };
 
 namespace {
@@ -472,6 +482,9 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    for (int i = 0; i < 4; i++) ctx->err_watch[i] = 0;
    CREATE_TRY(event_create(ctx->watch_event));
    CREATE_TRY(dev_alloc(ctx->stage, cap * 12));
+   CREATE_TRY(dev_alloc(ctx->obst_dev, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(pinned_alloc(ctx->obst_stage, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(event_create(ctx->ev_obst_copied));
    CREATE_TRY(hipStreamSynchronize(ctx->stream));
 #undef CREATE_TRY
    *out = ctx.release();

@@ -520,7 +520,8 @@ int launch_accel(sph_hip_context* ctx, int part = 0, hipStream_t part_stream = n
    return SPH_HIP_OK;
 }
 
-// with_hash: the kernel also does the first step of the next cell build (see k_integrate)
+// with_hash: the kernel also does the first step of the next cell build (see k_integrate);
+// with static obstacles, k_integrate_obst
 int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
 {
    const int n = ctx->n;
@@ -528,9 +529,14 @@ int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const int blocks = div_up(n, RED_THREADS);
    bind_flags([&](auto U, auto H) {
-      hipLaunchKernelGGL((k_integrate<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
-                         ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
-                         ctx->grid, ctx->key, ctx->slot, ctx->cell_count);
+      if (ctx->n_obst > 0)
+         hipLaunchKernelGGL((k_integrate_obst<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst);
+      else
+         hipLaunchKernelGGL((k_integrate<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count);
    }, unit_scale(ctx->prm), with_hash);
    ctx->energy_blocks = blocks;  // totals are formed on demand (sph_hip_get_energy)
    ctx->prehashed = with_hash ? 1 : 0;
@@ -623,7 +629,7 @@ int step_impl(sph_hip_context* ctx, bool timed)
    // hashes and counts for the next cell build - and the tiled acceleration pass does both itself
    const bool hash_too = ctx->mode == SPH_HIP_MODE_FULL && !ctx->had_exchange && ctx->plane_lo == 0 &&
                          ctx->plane_hi == ctx->grid.nz_global && !ctx->no_prehash;
-   const bool fused = hash_too && ctx->use_tiled && ctx->n > 0 && !ctx->no_fused_integrate;
+   const bool fused = fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst);
    if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;
    if (fused) fused_step_done(ctx, 1);

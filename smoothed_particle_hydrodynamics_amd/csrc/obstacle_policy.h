@@ -1,0 +1,276 @@
+// Static analytic obstacles (include/sph_hip.h: sph_hip_set_obstacles): the argument checks and the
+// per-particle collision response, one inline function for the device (k_integrate_obst,
+// k_slab_pack_early_obst: common_kernels.h, slab_kernels.h) and for g++ (tests/test_obstacles_cpu.py,
+// against the numpy restatement tests/obstacle_emulation.py).
+// Pure C++17 without HIP; the translation units that use it are compiled with -ffp-contract=off.
+//
+// The contract, operation by operation.  All arithmetic is fp32, unfused, in the order written
+// ("a + b + c" is (a + b) + c); sqrtf and "/" are correctly rounded.  Obstacle i of the list sees the
+// v, q the obstacle before it left; p is never updated.
+//   inputs     p: the particle's position before the step; v, q: its velocity and position after
+//              the drift, the kick and the wall handling (apply_walls); dt = time_step; damping.
+//   inside     (strict) sphere: d = q - center, (dx*dx + dy*dy) + dz*dz < r*r.
+//              box: lo[a] < q[a] < hi[a] on every axis a.
+//              cylinder (axis a, u = (a+1)%3, w = (a+2)%3): lo[a] < q[a] < hi[a] and
+//              du*du + dw*dw < r*r with d = q - center.
+//              A particle that is not inside is left untouched, bit for bit.
+//   entry      along the line p + v*s:
+//              box: for every axis with v[a] != 0, t_a = ((v[a] > 0 ? lo[a] : hi[a]) - p[a]) / v[a]
+//              and x_a = ((v[a] > 0 ? hi[a] : lo[a]) - p[a]) / v[a]; an axis with v[a] == 0 misses
+//              unless lo[a] < p[a] < hi[a].  t = the largest t_a (ties: the lowest axis),
+//              t_exit = the smallest x_a; n = -sign(v[a]) e_a of the axis that gave t.
+//              sphere: d0 = p - center, A = (vx*vx + vy*vy) + vz*vz, B = (d0x*vx + d0y*vy) + d0z*vz,
+//              C = ((d0x*d0x + d0y*d0y) + d0z*d0z) - r*r, D = B*B - A*C; the line misses unless
+//              D > 0; s = sqrtf(D), t = (-B - s) / A, t_exit = (-B + s) / A;
+//              n = (inter - center) / r per component.
+//              cylinder: cap slab as the box on axis a (tc0, tc1; v[a] == 0: -inf, +inf when
+//              lo[a] < p[a] < hi[a], else a miss); circle in (u, w): A = vu*vu + vw*vw,
+//              B = d0u*vu + d0w*vw, C = (d0u*d0u + d0w*d0w) - r*r, D = B*B - A*C, a miss unless
+//              D > 0, tr0 = (-B - s) / A, tr1 = (-B + s) / A with s = sqrtf(D) (A == 0: -inf, +inf
+//              when d0u*d0u + d0w*d0w < r*r, else a miss).  t = the later of tc0 and tr0, the cap
+//              on a tie; t_exit = the smaller of tc1 and tr1.  n: the cap's -sign(v[a]) e_a, or the
+//              side's (inter_u - center_u) / r, (inter_w - center_w) / r with n_a = 0.
+//              The entry is valid only when p is not inside, v != 0, the line meets the obstacle
+//              and 0 <= t < t_exit.
+//   response   (a valid entry: SPH::applyBoundary, reference src/sph.cpp:1124-1148, as coded)
+//              inter = p + v*t; dot = (v0*n0 + v1*n1) + v2*n2; refl = v - (n*dot)*2;
+//              remaining = dt - t if dt - t > 0, else 0 (the wall lets it go negative);
+//              v = refl; q = inter + refl*(remaining*damping), per component.
+//   fallback   (no valid entry) q moves to the nearest surface point, n is the outward normal there:
+//              sphere: d = q - center, len = sqrtf((dx*dx + dy*dy) + dz*dz), n = d / len per
+//              component (len == 0: n = +x), q = center + n*r.
+//              box: the face with the smallest distance q[a] - lo[a] (n = -e_a, q[a] = lo[a]) or
+//              hi[a] - q[a] (n = +e_a, q[a] = hi[a]); ties: the lowest axis, lo before hi.
+//              cylinder: candidates in the order lo cap (q[a] - lo[a]), hi cap (hi[a] - q[a]), side
+//              (r - len, len = sqrtf(du*du + dw*dw)); the first smallest wins.  A cap sets q[a] to
+//              its plane; the side sets q_u = center_u + n_u*r, q_w = center_w + n_w*r with
+//              n = (du / len, dw / len) (len == 0: n = e_u).
+//              dot = (v0*n0 + v1*n1) + v2*n2, m = dot if dot < 0 else 0, v = v - n*(m*2) per
+//              component: only an inward component is reflected, without damping.
+// The result is not strictly inside the obstacle except by the rounding of the last formula applied
+// (the sphere's and the side's q are rounded once per component from an exact surface point).
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/sph_hip.h"
+
+#ifdef __HIPCC__
+#define OBST_HD __host__ __device__
+#else
+#define OBST_HD
+#endif
+
+// Why a list is refused, or nullptr.  Every float field of every entry must be finite, the unused
+// ones included.
+inline const char* obstacle_check(const sph_hip_obstacle* list, int n)
+{
+   if (n < 0 || n > SPH_HIP_MAX_OBSTACLES) return "the obstacle count must be in [0, 64]";
+   if (n > 0 && !list) return "null obstacle list";
+   for (int i = 0; i < n; i++) {
+      const sph_hip_obstacle& o = list[i];
+      if (o.kind != SPH_HIP_OBSTACLE_SPHERE && o.kind != SPH_HIP_OBSTACLE_BOX && o.kind != SPH_HIP_OBSTACLE_CYLINDER)
+         return "unknown obstacle kind";
+      bool finite = isfinite(o.radius);
+      for (int a = 0; a < 3; a++) finite = finite && isfinite(o.center[a]) && isfinite(o.lo[a]) && isfinite(o.hi[a]);
+      if (!finite) return "obstacle fields must be finite";
+      if (o.kind == SPH_HIP_OBSTACLE_SPHERE) {
+         if (!(o.radius > 0.0f)) return "a sphere's radius must be > 0";
+      } else if (o.kind == SPH_HIP_OBSTACLE_BOX) {
+         for (int a = 0; a < 3; a++)
+            if (!(o.lo[a] < o.hi[a])) return "a box needs lo < hi on every axis";
+      } else {
+         if (o.axis < 0 || o.axis > 2) return "a cylinder's axis must be 0, 1 or 2";
+         if (!(o.radius > 0.0f)) return "a cylinder's radius must be > 0";
+         if (!(o.lo[o.axis] < o.hi[o.axis])) return "a cylinder needs lo < hi on its axis";
+      }
+   }
+   return nullptr;
+}
+
+OBST_HD inline bool obstacle_inside(const sph_hip_obstacle& o, const float x[3])
+{
+   if (o.kind == SPH_HIP_OBSTACLE_SPHERE) {
+      const float dx = x[0] - o.center[0], dy = x[1] - o.center[1], dz = x[2] - o.center[2];
+      return dx * dx + dy * dy + dz * dz < o.radius * o.radius;
+   }
+   if (o.kind == SPH_HIP_OBSTACLE_BOX)
+      return o.lo[0] < x[0] && x[0] < o.hi[0] && o.lo[1] < x[1] && x[1] < o.hi[1] && o.lo[2] < x[2] &&
+             x[2] < o.hi[2];
+   const int a = o.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+   const float du = x[u] - o.center[u], dw = x[w] - o.center[w];
+   return o.lo[a] < x[a] && x[a] < o.hi[a] && du * du + dw * dw < o.radius * o.radius;
+}
+
+// Slab of one axis for the line p + v*s: entry t0 and exit t1 (false: the line misses it).
+OBST_HD inline bool obstacle_slab(float p, float v, float lo, float hi, float& t0, float& t1)
+{
+   if (v != 0.0f) {
+      t0 = ((v > 0.0f ? lo : hi) - p) / v;
+      t1 = ((v > 0.0f ? hi : lo) - p) / v;
+      return true;
+   }
+   t0 = -INFINITY;
+   t1 = INFINITY;
+   return lo < p && p < hi;
+}
+
+// The response of one obstacle (see the contract above).
+OBST_HD inline void obstacle_respond(const sph_hip_obstacle& o, const float p[3], float v[3], float q[3],
+                                     float dt, float damping)
+{
+   if (!obstacle_inside(o, q)) return;
+   const float r = o.radius;
+   float n[3] = {0.0f, 0.0f, 0.0f};
+   float t = 0.0f, t_exit = 0.0f;
+   bool hit = !obstacle_inside(o, p) && (v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f);
+   int kind_n = -1;   // entry normal: axis 0..2 (slab), 3 (sphere), 4 (cylinder side)
+   if (hit) {
+      if (o.kind == SPH_HIP_OBSTACLE_BOX) {
+         t = -INFINITY;
+         t_exit = INFINITY;
+         for (int a = 0; a < 3 && hit; a++) {
+            float t0, t1;
+            if (!obstacle_slab(p[a], v[a], o.lo[a], o.hi[a], t0, t1)) hit = false;
+            if (v[a] != 0.0f && t0 > t) {
+               t = t0;
+               kind_n = a;
+            }
+            if (t1 < t_exit) t_exit = t1;
+         }
+      } else if (o.kind == SPH_HIP_OBSTACLE_SPHERE) {
+         const float d0x = p[0] - o.center[0], d0y = p[1] - o.center[1], d0z = p[2] - o.center[2];
+         const float A = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+         const float B = d0x * v[0] + d0y * v[1] + d0z * v[2];
+         const float C = (d0x * d0x + d0y * d0y + d0z * d0z) - r * r;
+         const float D = B * B - A * C;
+         if (D > 0.0f) {
+            const float s = sqrtf(D);
+            t = (-B - s) / A;
+            t_exit = (-B + s) / A;
+            kind_n = 3;
+         } else {
+            hit = false;
+         }
+      } else {
+         const int a = o.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+         float tc0, tc1, tr0 = -INFINITY, tr1 = INFINITY;
+         hit = obstacle_slab(p[a], v[a], o.lo[a], o.hi[a], tc0, tc1);
+         const float d0u = p[u] - o.center[u], d0w = p[w] - o.center[w];
+         const float A = v[u] * v[u] + v[w] * v[w];
+         const float C = (d0u * d0u + d0w * d0w) - r * r;
+         if (A > 0.0f) {
+            const float B = d0u * v[u] + d0w * v[w];
+            const float D = B * B - A * C;
+            if (D > 0.0f) {
+               const float s = sqrtf(D);
+               tr0 = (-B - s) / A;
+               tr1 = (-B + s) / A;
+            } else {
+               hit = false;
+            }
+         } else if (!(d0u * d0u + d0w * d0w < r * r)) {
+            hit = false;
+         }
+         if (tc0 >= tr0) {
+            t = tc0;
+            kind_n = a;
+         } else {
+            t = tr0;
+            kind_n = 4;
+         }
+         t_exit = tc1 < tr1 ? tc1 : tr1;
+      }
+      hit = hit && t >= 0.0f && t < t_exit;
+   }
+   if (hit) {
+      float inter[3], refl[3];
+      for (int c = 0; c < 3; c++) inter[c] = p[c] + v[c] * t;
+      if (kind_n < 3) {
+         n[kind_n] = v[kind_n] > 0.0f ? -1.0f : 1.0f;
+      } else if (kind_n == 3) {
+         for (int c = 0; c < 3; c++) n[c] = (inter[c] - o.center[c]) / r;
+      } else {
+         const int a = o.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+         n[u] = (inter[u] - o.center[u]) / r;
+         n[w] = (inter[w] - o.center[w]) / r;
+         n[a] = 0.0f;
+      }
+      const float dot = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
+      for (int c = 0; c < 3; c++) refl[c] = v[c] - ((n[c] * dot) * 2.0f);
+      const float rem = dt - t;
+      const float remaining = rem > 0.0f ? rem : 0.0f;
+      for (int c = 0; c < 3; c++) {
+         v[c] = refl[c];
+         q[c] = inter[c] + refl[c] * (remaining * damping);
+      }
+      return;
+   }
+   // fallback: nearest surface point
+   if (o.kind == SPH_HIP_OBSTACLE_SPHERE) {
+      const float dx = q[0] - o.center[0], dy = q[1] - o.center[1], dz = q[2] - o.center[2];
+      const float len = sqrtf(dx * dx + dy * dy + dz * dz);
+      if (len > 0.0f) {
+         n[0] = dx / len;
+         n[1] = dy / len;
+         n[2] = dz / len;
+      } else {
+         n[0] = 1.0f;
+      }
+      for (int c = 0; c < 3; c++) q[c] = o.center[c] + n[c] * r;
+   } else if (o.kind == SPH_HIP_OBSTACLE_BOX) {
+      float best = INFINITY;
+      int face = 0;
+      for (int a = 0; a < 3; a++) {
+         const float dlo = q[a] - o.lo[a], dhi = o.hi[a] - q[a];
+         if (dlo < best) {
+            best = dlo;
+            face = 2 * a;
+         }
+         if (dhi < best) {
+            best = dhi;
+            face = 2 * a + 1;
+         }
+      }
+      const int a = face >> 1;
+      if (face & 1) {
+         q[a] = o.hi[a];
+         n[a] = 1.0f;
+      } else {
+         q[a] = o.lo[a];
+         n[a] = -1.0f;
+      }
+   } else {
+      const int a = o.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+      const float du = q[u] - o.center[u], dw = q[w] - o.center[w];
+      const float len = sqrtf(du * du + dw * dw);
+      const float dlo = q[a] - o.lo[a], dhi = o.hi[a] - q[a], dside = r - len;
+      if (dlo <= dhi && dlo <= dside) {
+         q[a] = o.lo[a];
+         n[a] = -1.0f;
+      } else if (dhi <= dside) {
+         q[a] = o.hi[a];
+         n[a] = 1.0f;
+      } else {
+         if (len > 0.0f) {
+            n[u] = du / len;
+            n[w] = dw / len;
+         } else {
+            n[u] = 1.0f;
+         }
+         q[u] = o.center[u] + n[u] * r;
+         q[w] = o.center[w] + n[w] * r;
+      }
+   }
+   const float dot = v[0] * n[0] + v[1] * n[1] + v[2] * n[2];
+   const float m = dot < 0.0f ? dot : 0.0f;
+   for (int c = 0; c < 3; c++) v[c] = v[c] - n[c] * (m * 2.0f);
+}
+
+// Every obstacle of a list, in order.
+OBST_HD inline void obstacles_respond(const sph_hip_obstacle* list, int n, const float p[3], float v[3], float q[3],
+                                      float dt, float damping)
+{
+   for (int i = 0; i < n; i++) obstacle_respond(list[i], p, v, q, dt, damping);
+}

@@ -89,8 +89,10 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
    }
    // The two parts of the acceleration launch do the rest of the step themselves (FusedStep):
    // integrate into the other pair of state buffers, hash for the next build, and - the border
-   // part - the messages.  SPH_HIP_NO_FUSED_SLAB=1 keeps k_slab_pack_early + k_integrate.
-   ctx->slab_fused = ctx->no_fused_slab ? 0 : 1;
+   // part - the messages.  SPH_HIP_NO_FUSED_SLAB=1, or static obstacles, keep k_slab_pack_early +
+   // k_integrate (their _obst forms).
+   ctx->slab_fused = fuse_slab_step(ctx->no_fused_slab != 0, ctx->n_obst) ? 1 : 0;
+   ctx->slab_step_open = 1;
    ctx->slab_msgs[0] = left_device;
    ctx->slab_msgs[1] = right_device;
    ctx->slab_msg_capacity = capacity_records;
@@ -100,9 +102,15 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
       const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
       const SlabZone zone = slab_zone(ctx);
       bind_flags([&](auto U) {
-         hipLaunchKernelGGL(k_slab_pack_early<U.value>, dim3(SLAB_PACK_BLOCKS), dim3(256), 0, side,
-                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->grid,
-                            zone, (SlabMsg*)left_device, (SlabMsg*)right_device, capacity_records);
+         if (ctx->n_obst > 0)
+            hipLaunchKernelGGL(k_slab_pack_early_obst<U.value>, dim3(SLAB_PACK_BLOCKS), dim3(256), 0, side,
+                               ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->grid,
+                               zone, (SlabMsg*)left_device, (SlabMsg*)right_device, capacity_records,
+                               ctx->obst_dev, ctx->n_obst);
+         else
+            hipLaunchKernelGGL(k_slab_pack_early<U.value>, dim3(SLAB_PACK_BLOCKS), dim3(256), 0, side,
+                               ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->grid,
+                               zone, (SlabMsg*)left_device, (SlabMsg*)right_device, capacity_records);
       }, unit_scale(ctx->prm));
       SPH_TRY(hipGetLastError());
    }
@@ -119,6 +127,7 @@ int slab_step_end(sph_hip_context* ctx)
       return SPH_HIP_ERR_INVALID;
    }
    hipStream_t st = ctx->stream;
+   ctx->slab_step_open = 0;
    const StepEvents se = step_events(ctx, ctx->slab_step_level);
    const bool fused = ctx->slab_fused && ctx->n > 0;
    const SlabFused sf = {ctx->slab_msgs[0], ctx->slab_msgs[1], ctx->slab_msg_capacity};

@@ -159,6 +159,68 @@ k_slab_pack_early(const float4* __restrict__ posm, const float4* __restrict__ ve
    }
 }
 
+// The same with static obstacles (its own copy of the body, so that k_slab_pack_early's code stays as
+// tuned): the records carry what k_integrate_obst will write for the particle, so that ghosts agree
+// with their owners bit for bit.
+template <bool UNIT_SCALE>
+__global__ void __launch_bounds__(256)
+k_slab_pack_early_obst(const float4* __restrict__ posm, const float4* __restrict__ velp,
+                       const float4* __restrict__ acc, int32_t* __restrict__ meta, PairConsts k,
+                       CellGrid g, SlabZone zone, SlabMsg* __restrict__ left,
+                       SlabMsg* __restrict__ right, int capacity,
+                       const sph_hip_obstacle* __restrict__ obst, int n_obst)
+{
+   const ObstacleHook after = {obst, n_obst, k.dt, k.damping};
+   const int ob = meta[META_OWN_BEGIN], oe = meta[META_OWN_END];
+   const int lo_end = min(meta[META_BND_LO_END], oe);
+   const int hi_begin = min(max(meta[META_BND_HI_BEGIN], lo_end), oe);
+   const int n_left = lo_end - ob, n_right = oe - hi_begin;
+   // (whole waves stay in the loop together: msg_reserve is a wave-wide operation)
+   for (int q0 = blockIdx.x * blockDim.x; q0 < n_left + n_right; q0 += gridDim.x * blockDim.x) {
+      const int q = q0 + threadIdx.x;
+      bool to_left = false, to_right = false;
+      float4 x = make_float4(0.f, 0.f, 0.f, 0.f), v = x;
+      if (q < n_left + n_right) {
+         const int p = q < n_left ? ob + q : hi_begin + (q - n_left);
+         x = posm[p];
+         v = velp[p];
+         if (__float_as_uint(v.w) != SPH_DEAD_ID) {
+            double ke, pe;
+            integrate_particle<UNIT_SCALE>(k, x, v, acc[p], ke, pe, after);
+            const int plane = cell_coord(x.z, g.inv, g.nz_global);
+            to_left = zone.have_left && plane < zone.lo + zone.halo;
+            to_right = zone.have_right && plane >= zone.hi - zone.halo;
+         }
+      }
+      if (zone.have_left) {
+         const int s = msg_reserve(&left->header[0], to_left);
+         if (to_left) {
+            if (s < capacity) {
+               left->rec[2 * s] = x;
+               left->rec[2 * s + 1] = v;
+            } else {
+               atomicOr(&meta[META_ERRORS], 2);
+            }
+         }
+      }
+      if (zone.have_right) {
+         const int s = msg_reserve(&right->header[0], to_right);
+         if (to_right) {
+            if (s < capacity) {
+               right->rec[2 * s] = x;
+               right->rec[2 * s + 1] = v;
+            } else {
+               atomicOr(&meta[META_ERRORS], 2);
+            }
+         }
+      }
+   }
+   if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (left) left->header[1] = capacity;
+      if (right) right->header[1] = capacity;
+   }
+}
+
 // Cell build of a slab whose last step was integrated and hashed by its acceleration pass
 // (FusedStep): key, slot and the cells' counts of the owned entries of the previous sorted order
 // [OWN_BEGIN, OWN_END) are already there.  What is left: that order's other entries - last step's

@@ -796,6 +796,48 @@ int sph_hip_integrate(sph_hip_context* ctx)
    return launch_integrate(ctx);
 }
 
+// ---- static obstacles (obstacle_policy.h; routes: launch_policy.h fuse_integrate / fuse_slab_step) ----
+
+int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, int n)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = obstacle_check(list, n)) {
+      ctx->err = std::string("sph_hip_set_obstacles: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (ctx->slab_step_open) {
+      ctx->err = "sph_hip_set_obstacles: not between sph_hip_slab_step_begin and sph_hip_slab_step_end";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (n > 0) {
+      // the staging is pinned host memory the previous call's copy may still be reading: wait for
+      // that copy (not for the steps queued before it), then copy behind everything enqueued so far
+      if (ctx->obst_copy_pending) SPH_TRY(hipEventSynchronize(ctx->ev_obst_copied));
+      ctx->obst_copy_pending = 0;
+      memcpy(ctx->obst_stage.get(), list, sizeof(sph_hip_obstacle) * (size_t)n);
+      SPH_TRY(hipMemcpyAsync(ctx->obst_dev, ctx->obst_stage.get(), sizeof(sph_hip_obstacle) * (size_t)n,
+                             hipMemcpyHostToDevice, ctx->stream));
+      SPH_TRY(hipEventRecord(ctx->ev_obst_copied, ctx->stream));
+      ctx->obst_copy_pending = 1;
+      memcpy(ctx->obst_host, list, sizeof(sph_hip_obstacle) * (size_t)n);
+   }
+   ctx->n_obst = n;   // the steps enqueued from here on take the routes of this count
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity)
+{
+   if (!ctx) return SPH_HIP_ERR_INVALID;
+   if (capacity < 0 || (capacity > 0 && !out)) {
+      ctx->err = "sph_hip_get_obstacles: capacity must be >= 0, out non-null when it is > 0";
+      return SPH_HIP_ERR_INVALID;
+   }
+   const int k = capacity < ctx->n_obst ? capacity : ctx->n_obst;
+   if (k > 0) memcpy(out, ctx->obst_host, sizeof(sph_hip_obstacle) * (size_t)k);
+   return ctx->n_obst;
+}
+
 int sph_hip_synchronize(sph_hip_context* ctx)
 {
    int rc = check_ctx(ctx);

@@ -72,6 +72,8 @@ class SphRenderParams(C.Structure):
     ]
 
 
+from .obstacles import SphObstacle  # noqa: E402  (mirror of sph_hip_obstacle)
+
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 _ctx = C.c_void_p
@@ -119,6 +121,8 @@ PROTOTYPES = {
     "sph_hip_download_surface": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_render": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_set_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
+    "sph_hip_get_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -1,0 +1,144 @@
+"""Static analytic obstacles (include/sph_hip.h: sph_hip_set_obstacles).
+
+`Sphere`, `Box` and `Cylinder` describe the solids a context's particles collide with; `as_struct()`
+gives the C ABI's sph_hip_obstacle, `signed_distance(points)` the numpy distance to the surface
+(negative inside), for placing obstacles and checking results.  The collision response itself is
+csrc/obstacle_policy.h and runs on the GPU.
+"""
+import ctypes as C
+
+import numpy as np
+
+SPHERE, BOX, CYLINDER = 0, 1, 2   # SPH_HIP_OBSTACLE_* (include/sph_hip.h)
+MAX_OBSTACLES = 64                # SPH_HIP_MAX_OBSTACLES
+
+
+class SphObstacle(C.Structure):
+    """Mirror of sph_hip_obstacle (include/sph_hip.h): 48 bytes, field order is ABI."""
+
+    _fields_ = [("kind", C.c_int32), ("axis", C.c_int32), ("center", C.c_float * 3), ("radius", C.c_float),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+def _vec3(v):
+    return np.array(v, np.float32).reshape(3)
+
+
+def _points(points):
+    return np.asarray(points, np.float64).reshape(-1, 3)
+
+
+class Sphere:
+    kind = SPHERE
+
+    def __init__(self, center, radius):
+        self.center, self.radius = _vec3(center), np.float32(radius)
+
+    def as_struct(self):
+        s = SphObstacle()
+        s.kind = SPHERE
+        s.center[:] = [float(v) for v in self.center]
+        s.radius = float(self.radius)
+        return s
+
+    def signed_distance(self, points):
+        d = _points(points) - self.center.astype(np.float64)
+        return np.sqrt((d * d).sum(1)) - float(self.radius)
+
+    def __repr__(self):
+        return "Sphere(%s, %g)" % (list(self.center), self.radius)
+
+
+class Box:
+    """Axis-aligned box [lo, hi]."""
+
+    kind = BOX
+
+    def __init__(self, lo, hi):
+        self.lo, self.hi = _vec3(lo), _vec3(hi)
+
+    def as_struct(self):
+        s = SphObstacle()
+        s.kind = BOX
+        s.lo[:] = [float(v) for v in self.lo]
+        s.hi[:] = [float(v) for v in self.hi]
+        return s
+
+    def signed_distance(self, points):
+        p = _points(points)
+        lo, hi = self.lo.astype(np.float64), self.hi.astype(np.float64)
+        q = np.maximum(lo - p, p - hi)                       # per axis: > 0 outside that slab
+        outside = np.sqrt((np.maximum(q, 0.0) ** 2).sum(1))
+        inside = np.minimum(q.max(1), 0.0)
+        return outside + inside
+
+    def __repr__(self):
+        return "Box(%s, %s)" % (list(self.lo), list(self.hi))
+
+
+class Cylinder:
+    """Capped cylinder along `axis` (0 x, 1 y, 2 z): radius about `center` (whose axis component is
+    ignored), caps at lo and hi on the axis."""
+
+    kind = CYLINDER
+
+    def __init__(self, axis, center, radius, lo, hi):
+        if int(axis) not in (0, 1, 2):
+            raise ValueError("axis must be 0, 1 or 2")
+        self.axis = int(axis)
+        self.center, self.radius = _vec3(center), np.float32(radius)
+        self.lo, self.hi = np.float32(lo), np.float32(hi)
+
+    def as_struct(self):
+        s = SphObstacle()
+        s.kind = CYLINDER
+        s.axis = self.axis
+        s.center[:] = [float(v) for v in self.center]
+        s.radius = float(self.radius)
+        s.lo[self.axis] = float(self.lo)
+        s.hi[self.axis] = float(self.hi)
+        return s
+
+    def signed_distance(self, points):
+        p = _points(points)
+        a = self.axis
+        u, w = (a + 1) % 3, (a + 2) % 3
+        c = self.center.astype(np.float64)
+        radial = np.hypot(p[:, u] - c[u], p[:, w] - c[w]) - float(self.radius)
+        cap = np.maximum(float(self.lo) - p[:, a], p[:, a] - float(self.hi))
+        q = np.stack([radial, cap], 1)
+        outside = np.sqrt((np.maximum(q, 0.0) ** 2).sum(1))
+        inside = np.minimum(q.max(1), 0.0)
+        return outside + inside
+
+    def __repr__(self):
+        return "Cylinder(%d, %s, %g, %g, %g)" % (self.axis, list(self.center), self.radius, self.lo, self.hi)
+
+
+def from_struct(s):
+    """The Sphere / Box / Cylinder an sph_hip_obstacle describes."""
+    if s.kind == SPHERE:
+        return Sphere(list(s.center), s.radius)
+    if s.kind == BOX:
+        return Box(list(s.lo), list(s.hi))
+    if s.kind == CYLINDER:
+        return Cylinder(s.axis, list(s.center), s.radius, s.lo[s.axis], s.hi[s.axis])
+    raise ValueError("unknown obstacle kind %d" % s.kind)
+
+
+def as_array(obstacles):
+    """A ctypes array of sph_hip_obstacle for a list of obstacles (or of structs)."""
+    obstacles = list(obstacles)
+    arr = (SphObstacle * max(1, len(obstacles)))()
+    for i, o in enumerate(obstacles):
+        arr[i] = o if isinstance(o, SphObstacle) else o.as_struct()
+    return arr, len(obstacles)
+
+
+def inside_any(points, obstacles):
+    """Boolean mask of the points strictly inside any of the obstacles (float64 distances)."""
+    p = _points(points)
+    mask = np.zeros(p.shape[0], bool)
+    for o in obstacles:
+        mask |= o.signed_distance(p) < 0.0
+    return mask

@@ -313,9 +313,21 @@ class HipSlab:
         self._check(self._lib.sph_hip_set_arithmetic(self._ctx, int(arithmetic)), "sph_hip_set_arithmetic")
         self._settings["arithmetic"] = int(arithmetic)
 
+    def set_obstacles(self, obstacles):
+        """Static obstacles (sph_hip_set_obstacles): the same list on every slab of a run."""
+        from . import obstacles as O
+        obstacles = list(obstacles)
+        arr, n = O.as_array(obstacles)
+        self._check(self._lib.sph_hip_set_obstacles(self._ctx, arr, n), "sph_hip_set_obstacles")
+        self._settings["obstacles"] = obstacles
+
+    def get_obstacles(self):
+        from .sph import _get_obstacles
+        return _get_obstacles(self._lib, self._ctx, self._check)
+
     def settings(self):
-        """What set_timing / set_timing_stride / set_arithmetic were last given: a slab that
-        replaces this one (DistSlabStepper.rebalance) is set up alike."""
+        """What set_timing / set_timing_stride / set_arithmetic / set_obstacles were last given: a
+        slab that replaces this one (DistSlabStepper.rebalance) is set up alike."""
         return dict(self._settings)
 
     def apply_settings(self, settings):
@@ -325,6 +337,8 @@ class HipSlab:
             self.set_timing(settings["timing"])
         if "timing_stride" in settings:
             self.set_timing_stride(settings["timing_stride"])
+        if "obstacles" in settings:
+            self.set_obstacles(settings["obstacles"])
 
     def poll_send_counts(self):
         """Records in the two messages, without draining the stream: returns what the copy

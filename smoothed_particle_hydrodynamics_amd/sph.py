@@ -14,6 +14,7 @@ import zlib
 
 import numpy as np
 
+from . import obstacles as _obstacles
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, SphCamera, SphHipError, SphParams, SphRenderParams, default_params, load_library
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
@@ -82,6 +83,14 @@ class Camera:
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _get_obstacles(lib, ctx, check):
+    arr = (_obstacles.SphObstacle * _obstacles.MAX_OBSTACLES)()
+    n = lib.sph_hip_get_obstacles(ctx, arr, _obstacles.MAX_OBSTACLES)
+    if n < 0:
+        check(n, "sph_hip_get_obstacles")
+    return [_obstacles.from_struct(arr[i]) for i in range(n)]
 
 
 class SPH:
@@ -251,6 +260,17 @@ class SPH:
         lim = np.float32(self._params.cfl_limit)
         self._params.cfl_limit2 = float(lim * lim)
         self._push()
+
+    # ---- static obstacles (sph_hip_set_obstacles) ----------------------------------------------
+    def setObstacles(self, obstacles):
+        """Replace the static obstacles (obstacles.Sphere / Box / Cylinder, at most 64; an empty list
+        clears them).  Steps already queued keep the old list."""
+        arr, n = _obstacles.as_array(obstacles)
+        self._check(self._lib.sph_hip_set_obstacles(self._ctx, arr, n), "sph_hip_set_obstacles")
+
+    def getObstacles(self):
+        """The context's obstacles, in list order."""
+        return _get_obstacles(self._lib, self._ctx, self._check)
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
