@@ -98,6 +98,21 @@ hipError_t event_create(Event& ev, unsigned flags = hipEventDisableTiming)
    return hipEventCreateWithFlags(ev.out(), flags);
 }
 
+// Device scratch of one call, grown on demand; what it held is not kept.  reserve() makes room for
+// `count` elements: a larger buffer replaces the old one only once the context's stream is idle
+// (launches on it may still use the old one).  A failed wait is SPH_HIP_ERR_DEVICE; a failed
+// allocation is SPH_HIP_ERR_CAPACITY with the message `capacity_err` where one is given,
+// SPH_HIP_ERR_DEVICE otherwise.
+template <class T>
+struct Scratch {
+   DevBuf<T> buf;
+   size_t cap = 0;   // elements
+
+   int reserve(sph_hip_context* ctx, size_t count, const char* capacity_err = nullptr);
+   T* get() const { return buf.get(); }
+   operator T*() const { return buf.get(); }
+};
+
 } // namespace
 
 // One slab's communicator, exchange stream and message buffers (native RCCL exchange).
@@ -255,18 +270,15 @@ struct sph_hip_context {
    // staging for host <-> device in the reference's interleaved layouts
    DevBuf<float> stage; // capacity * 11 floats
 
-   // field sampler (sph_hip_sample_points / _lattice): probes and outputs of one chunk, grown on demand
-   DevBuf<float> sample_buf;
-   size_t sample_words = 0;
+   // field sampler (sph_hip_sample_points / _lattice): probes and outputs of one chunk
+   Scratch<float> sample_buf;
    int sample_route = 0;           // SAMPLE_ROUTE_*: SPH_HIP_SAMPLE_UNTILED=1 / SPH_HIP_SAMPLE_TILED=1 (tests, A/B runs)
    int sample_lds_set = 0;         // the tiled lattice kernels may take their dynamic LDS on this device
 
    // iso-surface extractor (sph_hip_extract_surface): one slab's scratch, the running totals per
    // slab, and the kept mesh (grown on demand, kept until the next extraction or destroy)
-   DevBuf<unsigned char> surf_scratch;
-   size_t surf_scratch_bytes = 0;
-   DevBuf<unsigned long long> surf_totals;   // 4 per slab boundary (k_surf_scan)
-   size_t surf_totals_len = 0;
+   Scratch<unsigned char> surf_scratch;
+   Scratch<unsigned long long> surf_totals;   // 4 per slab boundary (k_surf_scan)
    PinnedBuf<unsigned long long> surf_totals_host;   // 4
    DevBuf<float> surf_vtx, surf_nrm, surf_vel;
    DevBuf<int32_t> surf_tri;
@@ -276,12 +288,9 @@ struct sph_hip_context {
    int surf_kept = 0;
    int surf_planes_forced = 0;   // SPH_HIP_SURFACE_PLANES=n (tests): planes per slab
 
-   // renderer (sph_hip_render): one row chunk's scratch and the occupancy map (a byte per FULL cell),
-   // grown on demand
-   DevBuf<unsigned char> render_scratch;
-   size_t render_scratch_bytes = 0;
-   DevBuf<unsigned char> render_occ;
-   size_t render_occ_len = 0;
+   // renderer (sph_hip_render): one row chunk's scratch and the occupancy map (a byte per FULL cell)
+   Scratch<unsigned char> render_scratch;
+   Scratch<unsigned char> render_occ;
    int render_noskip = 0;   // SPH_HIP_RENDER_NOSKIP=1 (tests, A/B runs): every sample walks
 
    // static obstacles (sph_hip_set_obstacles): the list the next enqueued steps use, its device copy,
@@ -296,6 +305,24 @@ struct sph_hip_context {
 };
 
 namespace {
+
+template <class T>
+int Scratch<T>::reserve(sph_hip_context* ctx, size_t count, const char* capacity_err)
+{
+   if (count <= cap) return SPH_HIP_OK;
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   buf.reset();
+   cap = 0;
+   if (!capacity_err) {
+      SPH_TRY(dev_alloc(buf, count));
+   } else if (dev_alloc(buf, count) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = capacity_err;
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   cap = count;
+   return SPH_HIP_OK;
+}
 
 int check_ctx(sph_hip_context* ctx)
 {

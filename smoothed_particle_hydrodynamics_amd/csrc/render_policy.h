@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/sph_hip.h"
+#include "sample_policy.h"
 
 #define RENDER_MAX_DIM 16384
 #define RENDER_MAX_REFINE 30
@@ -59,15 +60,13 @@ inline const char* render_check(const sph_hip_camera* cam, const sph_hip_render_
 // rounded up to 256 bytes, and 256 bytes more hold the hit counter.  A chunk's rows are a multiple of
 // the 8-row pixel tile wherever the budget allows more than one tile row.
 #define RENDER_TILE 8
-#define RENDER_SCRATCH_BUDGET (64ll << 20)   // the sampler's chunk budget (sample_policy.h)
+#define RENDER_SCRATCH_BUDGET SAMPLE_SCRATCH_BUDGET   // the sampler's chunk budget (sample_policy.h)
 #define RENDER_PIXEL_BYTES 40
-
-inline long long render_round256(long long b) { return (b + 255) / 256 * 256; }
 
 inline long long render_scratch_bytes(int width, int rows)
 {
    const long long px = (long long)width * rows;
-   return render_round256(px * 4) * 4 + render_round256(px * 12) * 2 + 256;
+   return round256(px * 4) * 4 + round256(px * 12) * 2 + 256;
 }
 
 // rows per chunk: the most whole tile rows within the budget (at least one row), never more than the frame

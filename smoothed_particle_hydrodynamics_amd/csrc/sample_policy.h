@@ -2,11 +2,34 @@
 // functions of plain values: the brick of lattice points one workgroup covers, the LDS tile
 // capacity of a brick, the choice between the tiled and the per-probe walk, and the chunking that
 // bounds the device scratch of large probe sets.
+// The lattice argument checks, the scratch budget and the 256-byte rounding are shared with the
+// iso-surface extractor (surface_policy.h) and the renderer (render_policy.h).
 // Pure C++17 without HIP (tests/test_sample_cpu.py compiles it with g++); the environment switch
 // (SPH_HIP_SAMPLE_UNTILED) is read by the caller and passed in.
 #pragma once
 
+#include <math.h>
 #include <stdint.h>
+
+// Why the lattice origin + i * spacing, dims points per axis, is refused, or nullptr.
+inline const char* lattice_check(const float origin[3], const float spacing[3], const int32_t dims[3])
+{
+   if (!origin || !spacing || !dims) return "null origin, spacing or dims";
+   long long total = 1;
+   for (int a = 0; a < 3; a++) {
+      if (dims[a] <= 0 || !isfinite(origin[a]) || !isfinite(spacing[a]) || !(spacing[a] > 0.0f))
+         return "dims must be positive, the origin finite, the spacing finite and positive";
+      total *= dims[a];
+      if (total > 0x7fffffffll) return "more than 2^31 - 1 lattice points";
+   }
+   return nullptr;
+}
+
+// the lattice spacing in cell edges (inv: cells per unit length)
+inline void sample_spacing_cells(const float spacing[3], float inv, double cells[3])
+{
+   for (int a = 0; a < 3; a++) cells[a] = spacing[a] * (double)inv;
+}
 
 // One workgroup = one brick of lattice points, SAMPLE_THREADS of them, x fastest.  Its shape is
 // chosen per lattice from SAMPLE_BRICKS (sample_brick): lattices that span a scene's bounding box are
@@ -46,8 +69,13 @@ static const SampleBrick SAMPLE_BRICKS[SAMPLE_N_BRICKS] = {
 
 // Probes per chunk of a large probe set: the scratch holds a chunk's probes (3 floats per point
 // probe) and outputs (density, count, 3 velocity floats): 8 words per point probe, 5 per lattice
-// point, so 64 MiB / 40 MiB at most, whatever the caller asks for.
+// point, so 64 MiB / 40 MiB at most, whatever the caller asks for.  That 64 MiB is the device scratch
+// budget the extractor's slabs and the renderer's row chunks are sized to as well.
 #define SAMPLE_CHUNK_POINTS (1 << 21)
+#define SAMPLE_SCRATCH_BUDGET (64ll << 20)
+
+// scratch arrays start on 256-byte boundaries
+inline long long round256(long long b) { return (b + 255) / 256 * 256; }
 
 // Cells a brick's tile spans along one axis at the worst alignment: `points` points `spacing`
 // cell edges apart touch floor((points - 1) * spacing) + 2 cells, and their neighbourhoods one

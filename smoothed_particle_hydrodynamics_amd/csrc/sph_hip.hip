@@ -37,29 +37,28 @@ __global__ void k_selftest_sqrt(unsigned long long* __restrict__ out)
 
 // ---- field sampler (sample_kernels.h; decisions: sample_policy.h) ---------------------------------
 
+// ctx->err = "who: why"; the call is refused
+int refuse(sph_hip_context* ctx, const char* who, const char* why)
+{
+   ctx->err = std::string(who) + ": " + why;
+   return SPH_HIP_ERR_INVALID;
+}
+
 // Sampling reads a whole-grid FULL-mode state; a slab holds part of the grid and ghosts besides.
 int sample_check(sph_hip_context* ctx, const char* who)
 {
-   if (ctx->mode != SPH_HIP_MODE_FULL) {
-      ctx->err = std::string(who) + ": FULL and FULL_FAST contexts only";
-      return SPH_HIP_ERR_INVALID;
-   }
-   if (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange) {
-      ctx->err = std::string(who) + ": slab contexts (with neighbours, or that have exchanged) cannot be sampled";
-      return SPH_HIP_ERR_INVALID;
-   }
+   if (ctx->mode != SPH_HIP_MODE_FULL) return refuse(ctx, who, "FULL and FULL_FAST contexts only");
+   if (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange)
+      return refuse(ctx, who, "slab contexts (with neighbours, or that have exchanged) cannot be sampled");
    return SPH_HIP_OK;
 }
 
-// the chunk scratch, grown on demand (the old one is released once the stream is idle)
-int sample_scratch(sph_hip_context* ctx, size_t words)
+// nothing resident (the cell arrays may still describe an earlier upload): n samples of 0
+int sample_zero(size_t n, float* density, float* velocity_xyz, int32_t* count)
 {
-   if (words <= ctx->sample_words) return SPH_HIP_OK;
-   SPH_TRY(hipStreamSynchronize(ctx->stream));
-   ctx->sample_buf.reset();
-   ctx->sample_words = 0;
-   SPH_TRY(dev_alloc(ctx->sample_buf, words));
-   ctx->sample_words = words;
+   if (density) memset(density, 0, sizeof(float) * n);
+   if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * n);
+   if (count) memset(count, 0, sizeof(int32_t) * n);
    return SPH_HIP_OK;
 }
 
@@ -67,6 +66,34 @@ int sample_scratch(sph_hip_context* ctx, size_t words)
 // which consumes a pending prehash and moves the last sums with the particles, so that nothing a
 // caller can read or a later step computes changes.
 int sample_prepare(sph_hip_context* ctx) { return launch_cell_build(ctx, nullptr, nullptr, true); }
+
+// A lattice launch's origin, spacing and brick; the chunk it covers is the caller's to fill in.
+SampleLattice lattice_of(const float origin[3], const float spacing[3], const SampleBrick& brick)
+{
+   SampleLattice L = {};
+   L.ox = origin[0];
+   L.oy = origin[1];
+   L.oz = origin[2];
+   L.sx = spacing[0];
+   L.sy = spacing[1];
+   L.sz = spacing[2];
+   L.bx = brick.bx;
+   L.by = brick.by;
+   L.bz = brick.bz;
+   return L;
+}
+
+// Consecutive arrays of a scratch buffer, each rounded up to 256 bytes (surface_policy.h: surf_scratch,
+// render_policy.h: render_scratch_bytes).
+struct Carver {
+   unsigned char* p;
+   template <class T> T* take(long long bytes)
+   {
+      T* q = reinterpret_cast<T*>(p);
+      p += round256(bytes);
+      return q;
+   }
+};
 
 
 // ---- iso-surface extractor (surface_kernels.h; decisions: surface_policy.h) ------------------------
@@ -87,30 +114,6 @@ int surf_grow(sph_hip_context* ctx, DevBuf<T>& buf, long long& cap, long long ne
    if (keep > 0) SPH_TRY(hipMemcpy(fresh.get(), buf.get(), sizeof(T) * (size_t)keep, hipMemcpyDeviceToDevice));
    buf = std::move(fresh);
    cap = n;
-   return SPH_HIP_OK;
-}
-
-// the slab scratch and the totals array, grown on demand
-int surf_scratch_alloc(sph_hip_context* ctx, size_t bytes, size_t totals)
-{
-   if (bytes > ctx->surf_scratch_bytes) {
-      SPH_TRY(hipStreamSynchronize(ctx->stream));
-      ctx->surf_scratch.reset();
-      ctx->surf_scratch_bytes = 0;
-      if (dev_alloc(ctx->surf_scratch, bytes) != hipSuccess) {
-         (void)hipGetLastError();
-         return SPH_HIP_ERR_CAPACITY;
-      }
-      ctx->surf_scratch_bytes = bytes;
-   }
-   if (totals > ctx->surf_totals_len) {
-      SPH_TRY(hipStreamSynchronize(ctx->stream));
-      ctx->surf_totals.reset();
-      ctx->surf_totals_len = 0;
-      SPH_TRY(dev_alloc(ctx->surf_totals, totals));
-      ctx->surf_totals_len = totals;
-   }
-   if (!ctx->surf_totals_host) SPH_TRY(pinned_alloc(ctx->surf_totals_host, 4));
    return SPH_HIP_OK;
 }
 
@@ -1048,16 +1051,10 @@ int sph_hip_sample_points(sph_hip_context* ctx, int n, const float* xyz, float* 
    }
    if ((rc = sample_check(ctx, "sph_hip_sample_points"))) return rc;
    if (n == 0) return SPH_HIP_OK;
-   if (ctx->n == 0) {
-      // nothing resident (the cell arrays may still describe an earlier upload)
-      if (density) memset(density, 0, sizeof(float) * (size_t)n);
-      if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * (size_t)n);
-      if (count) memset(count, 0, sizeof(int32_t) * (size_t)n);
-      return SPH_HIP_OK;
-   }
+   if (ctx->n == 0) return sample_zero((size_t)n, density, velocity_xyz, count);
    if ((rc = sample_prepare(ctx))) return rc;
    const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS);
-   if ((rc = sample_scratch(ctx, (size_t)chunk * 8))) return rc;
+   if ((rc = ctx->sample_buf.reserve(ctx, (size_t)chunk * 8))) return rc;
    float* sxyz = ctx->sample_buf;
    float* srho = sxyz + 3 * (size_t)chunk;
    float* svel = srho + (size_t)chunk;
@@ -1087,32 +1084,12 @@ int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const fl
 {
    int rc = check_ctx(ctx);
    if (rc) return rc;
-   if (!origin || !spacing || !dims) {
-      ctx->err = "sph_hip_sample_lattice: null origin, spacing or dims";
-      return SPH_HIP_ERR_INVALID;
-   }
-   long long total = 1;
-   for (int a = 0; a < 3; a++) {
-      if (dims[a] <= 0 || !std::isfinite(origin[a]) || !std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) {
-         ctx->err = "sph_hip_sample_lattice: dims must be positive, the origin finite, the spacing finite and positive";
-         return SPH_HIP_ERR_INVALID;
-      }
-      total *= dims[a];
-      if (total > 0x7fffffffll) {
-         ctx->err = "sph_hip_sample_lattice: more than 2^31 - 1 lattice points";
-         return SPH_HIP_ERR_INVALID;
-      }
-   }
+   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, "sph_hip_sample_lattice", why);
    if ((rc = sample_check(ctx, "sph_hip_sample_lattice"))) return rc;
-   if (ctx->n == 0) {
-      if (density) memset(density, 0, sizeof(float) * (size_t)total);
-      if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * (size_t)total);
-      if (count) memset(count, 0, sizeof(int32_t) * (size_t)total);
-      return SPH_HIP_OK;
-   }
+   if (ctx->n == 0) return sample_zero((size_t)dims[0] * dims[1] * dims[2], density, velocity_xyz, count);
    if ((rc = sample_prepare(ctx))) return rc;
-   const double cells[3] = {spacing[0] * (double)ctx->grid.inv, spacing[1] * (double)ctx->grid.inv,
-                            spacing[2] * (double)ctx->grid.inv};
+   double cells[3];
+   sample_spacing_cells(spacing, ctx->grid.inv, cells);
    const SampleBrick brick = sample_brick(dims, cells);
    const bool tiled = sample_use_tiled(brick, dims, cells, SAMPLE_TILE_CAP, ctx->sample_route);
    if (tiled && !ctx->sample_lds_set) {
@@ -1131,23 +1108,14 @@ int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const fl
                                   (vel ? SAMPLE_TILE_BYTES_VELOCITY : SAMPLE_TILE_BYTES_DENSITY) : 0;
    const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
    const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
-   if ((rc = sample_scratch(ctx, chunk_points * 5))) return rc;
+   if ((rc = ctx->sample_buf.reserve(ctx, chunk_points * 5))) return rc;
    float* srho = ctx->sample_buf;
    float* svel = srho + chunk_points;
    int32_t* scnt = reinterpret_cast<int32_t*>(svel + 3 * chunk_points);
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
    hipStream_t st = ctx->stream;
-   SampleLattice L;
-   L.ox = origin[0];
-   L.oy = origin[1];
-   L.oz = origin[2];
-   L.sx = spacing[0];
-   L.sy = spacing[1];
-   L.sz = spacing[2];
-   L.bx = brick.bx;
-   L.by = brick.by;
-   L.bz = brick.bz;
+   SampleLattice L = lattice_of(origin, spacing, brick);
    // a chunk's outputs are a box of the caller's arrays: one copy per z-plane and array, or one for
    // the lot when the chunk spans whole planes
    auto copy_out = [&](void* dst, const void* src, size_t elem) -> hipError_t {
@@ -1199,30 +1167,8 @@ int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const f
    // the old mesh goes first: a refused or failed extraction keeps nothing
    ctx->surf_kept = 0;
    ctx->surf_nv = ctx->surf_nt = 0;
-   if (!origin || !spacing || !dims) {
-      ctx->err = "sph_hip_extract_surface: null origin, spacing or dims";
-      return SPH_HIP_ERR_INVALID;
-   }
-   long long total = 1;
-   for (int a = 0; a < 3; a++) {
-      if (dims[a] <= 0 || !std::isfinite(origin[a]) || !std::isfinite(spacing[a]) || !(spacing[a] > 0.0f)) {
-         ctx->err = "sph_hip_extract_surface: dims must be positive, the origin finite, the spacing finite and positive";
-         return SPH_HIP_ERR_INVALID;
-      }
-      total *= dims[a];
-      if (total > 0x7fffffffll) {
-         ctx->err = "sph_hip_extract_surface: more than 2^31 - 1 lattice points";
-         return SPH_HIP_ERR_INVALID;
-      }
-   }
-   if (!std::isfinite(iso) || !(iso > 0.0f)) {
-      ctx->err = "sph_hip_extract_surface: iso must be finite and positive";
-      return SPH_HIP_ERR_INVALID;
-   }
-   if (flags & ~(SPH_HIP_SURFACE_NORMALS | SPH_HIP_SURFACE_VELOCITY)) {
-      ctx->err = "sph_hip_extract_surface: unknown flag bits";
-      return SPH_HIP_ERR_INVALID;
-   }
+   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, "sph_hip_extract_surface", why);
+   if (const char* why = surf_check(iso, flags)) return refuse(ctx, "sph_hip_extract_surface", why);
    if ((rc = sample_check(ctx, "sph_hip_extract_surface"))) return rc;
    ctx->surf_flags = flags;
    const bool normals = (flags & SPH_HIP_SURFACE_NORMALS) != 0, vel = (flags & SPH_HIP_SURFACE_VELOCITY) != 0;
@@ -1242,33 +1188,28 @@ int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const f
       return SPH_HIP_ERR_CAPACITY;
    }
    const int nslabs = div_up(nz, P);
-   if ((rc = surf_scratch_alloc(ctx, (size_t)sz.bytes, 4 * (size_t)(nslabs + 1)))) {
-      if (rc == SPH_HIP_ERR_CAPACITY) ctx->err = "sph_hip_extract_surface: cannot allocate the slab scratch";
+   if ((rc = ctx->surf_scratch.reserve(ctx, (size_t)sz.bytes,
+                                       "sph_hip_extract_surface: cannot allocate the slab scratch")))
       return rc;
-   }
-   // scratch layout (surface_policy.h: surf_scratch)
-   unsigned char* p = ctx->surf_scratch;
-   auto carve = [&](long long bytes) {
-      unsigned char* q = p;
-      p += surf_round256(bytes);
-      return q;
-   };
-   float* srho = reinterpret_cast<float*>(carve(sz.sampled * 4));
-   int32_t* scnt = reinterpret_cast<int32_t*>(carve(sz.sampled * 4));
-   float* svel = vel ? reinterpret_cast<float*>(carve(sz.sampled * 12)) : nullptr;
-   uint8_t* codes = carve(sz.classified);
-   int32_t* vbase = reinterpret_cast<int32_t*>(carve(sz.classified * 4));
-   int2* active = reinterpret_cast<int2*>(carve(sz.own * 8));
-   uint32_t* bsum_pack = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
-   uint32_t* bsum_vown = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
-   uint32_t* boff_v = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
-   uint32_t* boff_t = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
-   uint32_t* boff_a = reinterpret_cast<uint32_t*>(carve(sz.blocks * 4));
+   if ((rc = ctx->surf_totals.reserve(ctx, 4 * (size_t)(nslabs + 1)))) return rc;
+   if (!ctx->surf_totals_host) SPH_TRY(pinned_alloc(ctx->surf_totals_host, 4));
+   Carver carve{ctx->surf_scratch};
+   float* srho = carve.take<float>(sz.sampled * 4);
+   int32_t* scnt = carve.take<int32_t>(sz.sampled * 4);
+   float* svel = vel ? carve.take<float>(sz.sampled * 12) : nullptr;
+   uint8_t* codes = carve.take<uint8_t>(sz.classified);
+   int32_t* vbase = carve.take<int32_t>(sz.classified * 4);
+   int2* active = carve.take<int2>(sz.own * 8);
+   uint32_t* bsum_pack = carve.take<uint32_t>(sz.blocks * 4);
+   uint32_t* bsum_vown = carve.take<uint32_t>(sz.blocks * 4);
+   uint32_t* boff_v = carve.take<uint32_t>(sz.blocks * 4);
+   uint32_t* boff_t = carve.take<uint32_t>(sz.blocks * 4);
+   uint32_t* boff_a = carve.take<uint32_t>(sz.blocks * 4);
    unsigned long long* totals = ctx->surf_totals;
    unsigned long long* host = ctx->surf_totals_host;
 
-   const double cells[3] = {spacing[0] * (double)ctx->grid.inv, spacing[1] * (double)ctx->grid.inv,
-                            spacing[2] * (double)ctx->grid.inv};
+   double cells[3];
+   sample_spacing_cells(spacing, ctx->grid.inv, cells);
    const SampleBrick brick = sample_brick(dims, cells);
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
@@ -1287,17 +1228,7 @@ int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const f
    S.sy = spacing[1];
    S.sz = spacing[2];
    S.iso = iso;
-   SampleLattice L;
-   L.ox = origin[0];
-   L.oy = origin[1];
-   L.oz = origin[2];
-   L.sx = spacing[0];
-   L.sy = spacing[1];
-   L.sz = spacing[2];
-   L.bx = brick.bx;
-   L.by = brick.by;
-   L.bz = brick.bz;
-   L.i0 = L.j0 = 0;
+   SampleLattice L = lattice_of(origin, spacing, brick);
    L.ex = nx;
    L.ey = ny;
    L.bricks_x = div_up(nx, L.bx);
@@ -1404,10 +1335,7 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
    int rc = check_ctx(ctx);
    if (rc) return rc;
    if ((rc = sample_check(ctx, "sph_hip_render"))) return rc;
-   if (const char* why = render_check(cam, rp, width, height, flags)) {
-      ctx->err = std::string("sph_hip_render: ") + why;
-      return SPH_HIP_ERR_INVALID;
-   }
+   if (const char* why = render_check(cam, rp, width, height, flags)) return refuse(ctx, "sph_hip_render", why);
    const size_t pixels = (size_t)width * height;
    const bool vel = (flags & SPH_HIP_RENDER_VELOCITY) != 0;
    if (velocity_xyz && !vel) memset(velocity_xyz, 0, sizeof(float) * 3 * pixels);
@@ -1427,46 +1355,25 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
    const CellGrid& g = ctx->grid;
    const bool skip = !ctx->render_noskip;
    if (skip) {
-      if ((size_t)g.ncells > ctx->render_occ_len) {
-         SPH_TRY(hipStreamSynchronize(st));
-         ctx->render_occ.reset();
-         ctx->render_occ_len = 0;
-         SPH_TRY(dev_alloc(ctx->render_occ, (size_t)g.ncells));
-         ctx->render_occ_len = (size_t)g.ncells;
-      }
+      if ((rc = ctx->render_occ.reserve(ctx, (size_t)g.ncells))) return rc;
       hipLaunchKernelGGL(k_render_occupancy, dim3(div_up(g.ncells, RENDER_THREADS)), dim3(RENDER_THREADS), 0, st,
                          ctx->cell_start, g, ctx->render_occ.get());
       SPH_TRY(hipGetLastError());
    }
    // scratch of one row chunk (render_policy.h)
    const int rows = render_chunk_rows(width, height);
-   const size_t bytes = (size_t)render_scratch_bytes(width, rows);
-   if (bytes > ctx->render_scratch_bytes) {
-      SPH_TRY(hipStreamSynchronize(st));
-      ctx->render_scratch.reset();
-      ctx->render_scratch_bytes = 0;
-      if (dev_alloc(ctx->render_scratch, bytes) != hipSuccess) {
-         (void)hipGetLastError();
-         ctx->err = "sph_hip_render: cannot allocate the chunk scratch";
-         return SPH_HIP_ERR_CAPACITY;
-      }
-      ctx->render_scratch_bytes = bytes;
-   }
+   if ((rc = ctx->render_scratch.reserve(ctx, (size_t)render_scratch_bytes(width, rows),
+                                         "sph_hip_render: cannot allocate the chunk scratch")))
+      return rc;
    const long long cp = (long long)width * rows;
-   unsigned char* base = ctx->render_scratch.get();
-   size_t off = 0;
-   auto carve = [&](long long n) {
-      unsigned char* q = base + off;
-      off += (size_t)render_round256(n);
-      return q;
-   };
-   uint32_t* s_rgba = reinterpret_cast<uint32_t*>(carve(cp * 4));
-   float* s_depth = reinterpret_cast<float*>(carve(cp * 4));
-   float* s_nrm = reinterpret_cast<float*>(carve(cp * 12));
-   float* s_vel = reinterpret_cast<float*>(carve(cp * 12));
-   int32_t* s_first = reinterpret_cast<int32_t*>(carve(cp * 4));
-   int32_t* s_hits = reinterpret_cast<int32_t*>(carve(cp * 4));
-   uint32_t* s_count = reinterpret_cast<uint32_t*>(carve(256));
+   Carver carve{ctx->render_scratch};
+   uint32_t* s_rgba = carve.take<uint32_t>(cp * 4);
+   float* s_depth = carve.take<float>(cp * 4);
+   float* s_nrm = carve.take<float>(cp * 12);
+   float* s_vel = carve.take<float>(cp * 12);
+   int32_t* s_first = carve.take<int32_t>(cp * 4);
+   int32_t* s_hits = carve.take<int32_t>(cp * 4);
+   uint32_t* s_count = carve.take<uint32_t>(256);
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
    const unsigned char* occ = skip ? ctx->render_occ.get() : nullptr;

@@ -1,11 +1,23 @@
 // Decisions of the iso-surface extractor (surface_kernels.h, sph_hip_extract_surface) that need no
-// GPU: the Kuhn split of a lattice cube into six tetrahedra, the seven edges a lattice point owns,
-// the oriented triangles of every tetrahedron case, and the z-slabs the lattice is meshed in.
+// GPU: the iso and flag checks, the Kuhn split of a lattice cube into six tetrahedra, the seven edges
+// a lattice point owns, the oriented triangles of every tetrahedron case, and the z-slabs the lattice
+// is meshed in.
 // Pure C++17 without HIP (tests/test_surface_cpu.py compiles it with g++); the environment switch
 // (SPH_HIP_SURFACE_PLANES) is read by the caller at context creation and passed in.
 #pragma once
 
 #include <stdint.h>
+
+#include "../../include/sph_hip.h"
+#include "sample_policy.h"
+
+// Why the extractor's iso and flags are refused, or nullptr (the lattice: sample_policy.h, lattice_check).
+inline const char* surf_check(float iso, int flags)
+{
+   if (!isfinite(iso) || !(iso > 0.0f)) return "iso must be finite and positive";
+   if (flags & ~(SPH_HIP_SURFACE_NORMALS | SPH_HIP_SURFACE_VELOCITY)) return "unknown flag bits";
+   return nullptr;
+}
 
 // corners of a lattice cube are numbered by bits: c = x + 2y + 4z (corner c is lattice point p + c)
 // The seven positive-direction edges of a lattice point, in the canonical order of vertex ids:
@@ -149,7 +161,7 @@ constexpr int surf_tet_case(int t, int cube_in)
 //   per own point         active-cube entry (8: cube index, triangle offset);
 //   per 256 points        block sums and offsets (20).
 #define SURF_THREADS 256
-#define SURF_SCRATCH_BUDGET (64ll << 20)   // the sampler's chunk budget (sample_policy.h)
+#define SURF_SCRATCH_BUDGET SAMPLE_SCRATCH_BUDGET   // the sampler's chunk budget (sample_policy.h)
 #define SURF_HALO_BELOW 1
 #define SURF_HALO_ABOVE 2
 
@@ -157,8 +169,6 @@ struct SurfScratch {
    long long sampled, classified, own, blocks;   // points of each kind, workgroups of a slab
    long long bytes;                              // total, each array rounded up to 256 bytes
 };
-
-inline long long surf_round256(long long b) { return (b + 255) / 256 * 256; }
 
 inline SurfScratch surf_scratch(const int dims[3], int planes, bool velocity)
 {
@@ -169,8 +179,8 @@ inline SurfScratch surf_scratch(const int dims[3], int planes, bool velocity)
    s.classified = plane * (planes + 1 < dims[2] ? planes + 1 : dims[2]);
    s.own = plane * (planes < dims[2] ? planes : dims[2]);
    s.blocks = (s.classified + SURF_THREADS - 1) / SURF_THREADS;
-   s.bytes = surf_round256(s.sampled * 4) * (velocity ? 5 : 2) + surf_round256(s.classified) +
-             surf_round256(s.classified * 4) + surf_round256(s.own * 8) + 5 * surf_round256(s.blocks * 4);
+   s.bytes = round256(s.sampled * 4) * (velocity ? 5 : 2) + round256(s.classified) +
+             round256(s.classified * 4) + round256(s.own * 8) + 5 * round256(s.blocks * 4);
    return s;
 }
 

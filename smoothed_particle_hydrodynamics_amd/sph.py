@@ -85,6 +85,16 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _lattice(origin, spacing, shape):
+    """origin, spacing and shape of a lattice call as its three C arrays, and shape as a list"""
+    o = (C.c_float * 3)(*[float(v) for v in origin])
+    s = (C.c_float * 3)(*[float(v) for v in spacing])
+    dims = [int(v) for v in shape]
+    if len(dims) != 3 or len(o) != 3 or len(s) != 3:
+        raise ValueError("origin, spacing and shape take three values each")
+    return o, s, (C.c_int32 * 3)(*dims), dims
+
+
 def _get_obstacles(lib, ctx, check):
     arr = (_obstacles.SphObstacle * _obstacles.MAX_OBSTACLES)()
     n = lib.sph_hip_get_obstacles(ctx, arr, _obstacles.MAX_OBSTACLES)
@@ -357,12 +367,7 @@ class SPH:
     def sampleLattice(self, origin, spacing, shape, velocity=True):
         """The same sums on the lattice origin + i * spacing (fp32, per axis), shape = (nx, ny, nz):
         (density[nz, ny, nx], velocity[nz, ny, nx, 3] or None, count[nz, ny, nx])."""
-        o = (C.c_float * 3)(*[float(v) for v in origin])
-        s = (C.c_float * 3)(*[float(v) for v in spacing])
-        dims = [int(v) for v in shape]
-        if len(dims) != 3 or len(o) != 3 or len(s) != 3:
-            raise ValueError("origin, spacing and shape take three values each")
-        d = (C.c_int32 * 3)(*dims)
+        o, s, d, dims = _lattice(origin, spacing, shape)
         grid = (max(dims[2], 0), max(dims[1], 0), max(dims[0], 0))
         total = grid[0] * grid[1] * grid[2]
         if total >= 2 ** 31:
@@ -378,14 +383,10 @@ class SPH:
         """The surface {density > iso} of the lattice sampleLattice(origin, spacing, shape) would
         give, meshed on the device (include/sph_hip.h: iso-surface extractor): a SurfaceMesh of
         numpy arrays.  The mesh stays in the context until the next extraction."""
-        o = (C.c_float * 3)(*[float(v) for v in origin])
-        s = (C.c_float * 3)(*[float(v) for v in spacing])
-        dims = [int(v) for v in shape]
-        if len(dims) != 3 or len(o) != 3 or len(s) != 3:
-            raise ValueError("origin, spacing and shape take three values each")
+        o, s, d, _ = _lattice(origin, spacing, shape)
         flags = (SURFACE_NORMALS if normals else 0) | (SURFACE_VELOCITY if velocity else 0)
         counts = (C.c_int32 * 2)()
-        self._check(self._lib.sph_hip_extract_surface(self._ctx, C.byref(o), C.byref(s), C.byref((C.c_int32 * 3)(*dims)),
+        self._check(self._lib.sph_hip_extract_surface(self._ctx, C.byref(o), C.byref(s), C.byref(d),
                                                       float(iso), flags, C.byref(counts)), "sph_hip_extract_surface")
         nv, nt = counts[0], counts[1]
         vtx = np.zeros((nv, 3), np.float32)

@@ -3,10 +3,29 @@ import ctypes as C
 import hashlib
 import json
 import os
+import shutil
+import subprocess
 
 import numpy as np
 
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "smoothed_particle_hydrodynamics_amd",
+                    "csrc")
 PINS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_pins.json")
+
+
+def compile_shim(source, flags, tmp_path_factory):
+    """Compile an extern "C" shim over csrc/'s plain C++ headers with g++ (no HIP include path: the
+    headers must compile without one) plus `flags`, and load it; skips the test where g++ is missing."""
+    import pytest
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    d = tmp_path_factory.mktemp("shim")
+    src, so = d / "shim.cpp", d / "libshim.so"
+    src.write_text(source)
+    subprocess.run([gxx, "-std=c++17", *flags, "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, str(src),
+                    "-o", str(so)], check=True)
+    return C.CDLL(str(so))
 
 
 def to_oracle_params(p):

@@ -2,14 +2,11 @@
 compiled here with g++ behind a small extern "C" shim and called through ctypes.  The expected
 values are worked out by hand from the formulas the library has always used."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "smoothed_particle_hydrodynamics_amd", "csrc")
+from helpers import compile_shim
+
 
 SHIM = r"""
 #include "launch_policy.h"
@@ -92,16 +89,7 @@ OFF, SUMS, PHASES = 0, 1, 2
 
 @pytest.fixture(scope="module")
 def pol(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if not gxx:
-        pytest.skip("g++ not found")
-    d = tmp_path_factory.mktemp("policy")
-    src, lib = d / "shim.cpp", d / "libpolicy.so"
-    src.write_text(SHIM)
-    # (no HIP include path: the header must compile without one)
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-fPIC", "-shared", "-I", CSRC,
-                    str(src), "-o", str(lib)], check=True)
-    p = C.CDLL(str(lib))
+    p = compile_shim(SHIM, ["-O1"], tmp_path_factory)
     p.trim.argtypes = [C.c_int, C.c_float, C.c_int, C.c_int]
     p.grown.argtypes = [C.c_longlong, C.c_int, C.c_int]
     return p

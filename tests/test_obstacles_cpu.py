@@ -4,17 +4,13 @@ g++ behind an extern "C" shim) against the numpy restatement tests/obstacle_emul
 the anchor to the reference's wall response (oracle.boundary), the bound on what is left inside, the
 integrate routes of csrc/launch_policy.h, and the Python side (obstacles.py, scenes.carve)."""
 import ctypes as C
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import obstacle_emulation as E
+from helpers import compile_shim
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "smoothed_particle_hydrodynamics_amd", "csrc")
 F32 = np.float32
 
 SHIM = r"""
@@ -53,17 +49,8 @@ void layout(long long* out)
 
 @pytest.fixture(scope="module")
 def policy(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("obstacle_policy")
-    src = d / "shim.cpp"
-    src.write_text(SHIM)
-    so = d / "libshim.so"
-    subprocess.run([gxx, "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Werror", "-shared", "-fPIC",
-                    "-I", CSRC, str(src), "-o", str(so)], check=True)
     from smoothed_particle_hydrodynamics_amd.obstacles import SphObstacle
-    lib = C.CDLL(str(so))
+    lib = compile_shim(SHIM, ["-O2", "-ffp-contract=off"], tmp_path_factory)
     lib.check.argtypes = [C.POINTER(SphObstacle), C.c_int]
     lib.check.restype = C.c_char_p
     lib.respond.argtypes = [C.POINTER(SphObstacle), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,

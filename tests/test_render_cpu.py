@@ -4,19 +4,17 @@ an extern "C" shim, as tests/test_surface_cpu.py does), the numpy restatement th
 against (tests/render_emulation.py) on analytic fields, and write_png."""
 import ctypes as C
 import os
-import shutil
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
 import render_emulation as E
+from helpers import compile_shim
 from test_sample_cpu import header_prototype
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "smoothed_particle_hydrodynamics_amd", "csrc")
 F32 = np.float32
 
 SHIM = r"""
@@ -53,17 +51,8 @@ void layout(long long* out)
 
 @pytest.fixture(scope="module")
 def policy(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("render_policy")
-    src = d / "shim.cpp"
-    src.write_text(SHIM)
-    so = d / "libshim.so"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, str(src),
-                    "-o", str(so)], check=True)
     from smoothed_particle_hydrodynamics_amd.lib import SphCamera, SphRenderParams
-    lib = C.CDLL(str(so))
+    lib = compile_shim(SHIM, ["-O1"], tmp_path_factory)
     lib.check.argtypes = [C.POINTER(SphCamera), C.POINTER(SphRenderParams), C.c_int, C.c_int, C.c_int]
     lib.check.restype = C.c_char_p
     lib.quant.argtypes = [C.c_float]

@@ -5,16 +5,14 @@ emulation the GPU tests check against (tests/sample_emulation.py), against a flo
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import sample_emulation as E
+from helpers import compile_shim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "smoothed_particle_hydrodynamics_amd", "csrc")
 ERR_INVALID = -1
 
 SHIM = r"""
@@ -48,26 +46,26 @@ void lattice_chunk(const int* dims, const int* brick, long long max_points, int*
    out[0] = c.ex; out[1] = c.ey; out[2] = c.ez;
 }
 int points_chunk(int n, int max_points) { return sample_points_chunk(n, max_points); }
+long long budget() { return SAMPLE_SCRATCH_BUDGET; }
+const char* check(const float* origin, const float* spacing, const int32_t* dims)
+{
+   const char* why = lattice_check(origin, spacing, dims);
+   return why ? why : "";
+}
 }
 """
 
 @pytest.fixture(scope="module")
 def policy(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("sample_policy")
-    src = d / "shim.cpp"
-    src.write_text(SHIM)
-    so = d / "libshim.so"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, str(src),
-                    "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = compile_shim(SHIM, ["-O1"], tmp_path_factory)
     lib.use_tiled.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int]
     lib.lattice_chunk.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_longlong, C.POINTER(C.c_int)]
     lib.tile_cells_axis.argtypes = [C.c_int, C.c_double]
     lib.brick_of.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.brick_of.restype = C.c_longlong
+    lib.budget.restype = C.c_longlong
+    lib.check.argtypes = [C.c_void_p] * 3
+    lib.check.restype = C.c_char_p
     return lib
 
 
@@ -162,6 +160,59 @@ def test_sample_lattice_refuses_null_arrays(hiplib):
     assert hiplib.sph_hip_sample_lattice(None, None, None, None, None, None, None) == ERR_INVALID
 
 
+# ---- lattice argument checks (csrc/sample_policy.h: lattice_check, sph_hip_sample_lattice and
+# sph_hip_extract_surface) --------------------------------------------------------------------------
+NAN, INF = float("nan"), float("inf")
+BAD_LATTICE = "dims must be positive, the origin finite, the spacing finite and positive"
+TOO_MANY = "more than 2^31 - 1 lattice points"
+
+
+def lattice_refusal(policy, origin=(0.0, 0.0, 0.0), spacing=(0.1, 0.1, 0.1), dims=(4, 4, 4)):
+    """lattice_check's reason, "" where the lattice is accepted; None stands for a null array"""
+    arrays = [None if v is None else C.cast((t * 3)(*v), C.c_void_p)
+              for t, v in ((C.c_float, origin), (C.c_float, spacing), (C.c_int32, dims))]
+    return policy.check(*arrays).decode()
+
+
+@pytest.mark.parametrize("origin,spacing,dims,why", [
+    # the cases test_sample_lattice_refuses_a_null_context_and_bad_arguments and
+    # test_gpu_surface.py::test_bad_arguments_are_refused list
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (0, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (4, -1, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (2, 2, 0), BAD_LATTICE),
+    ((NAN, 0.0, 0.0), (0.1, 0.1, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, INF, 0.0), (0.1, 0.1, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, -INF), (0.1, 0.1, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.0, 0.1, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, -0.0, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, -0.1, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, NAN), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (NAN, 0.1, 0.1), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, INF), (4, 4, 4), BAD_LATTICE),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (2048, 1024, 1024), TOO_MANY),     # 2^31 points
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (2 ** 31 - 1, 2, 1), TOO_MANY),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (65536, 65536, 0), TOO_MANY),      # the count is checked axis by axis
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (2 ** 31 - 1, 1, -1), BAD_LATTICE),
+    # valid edge cases
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (4, 4, 4), ""),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (1, 1, 1), ""),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (2 ** 31 - 1, 1, 1), ""),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (1, 1, 2 ** 31 - 1), ""),
+    ((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (2047, 1024, 1024), ""),
+    ((-3e38, 3e38, 0.0), (1e-45, 3e38, 1.0), (4, 4, 4), ""),              # a denormal spacing is positive
+])
+def test_lattice_check(policy, origin, spacing, dims, why):
+    assert lattice_refusal(policy, origin, spacing, dims) == why
+
+
+def test_lattice_check_refuses_null_arrays(policy):
+    for k in range(3):
+        args = [(0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (4, 4, 4)]
+        args[k] = None
+        assert lattice_refusal(policy, *args) == "null origin, spacing or dims"
+    assert lattice_refusal(policy, None, None, None) == "null origin, spacing or dims"
+
+
 # ---- launch decisions (csrc/sample_policy.h) -------------------------------------------------------
 def test_brick_and_tile_constants(policy):
     assert policy.threads() == 256
@@ -235,6 +286,7 @@ def test_route_ignores_the_spacing_of_single_point_axes(policy):
 def test_lattice_chunks(policy):
     most = policy.chunk_points()
     assert most == 1 << 21
+    assert policy.budget() == 8 * 4 * most      # the point-probe chunk: 8 words per probe
     assert chunk(policy, (128, 128, 128), most) == (128, 128, 128)       # 2^21 exactly: one chunk
     assert chunk(policy, (128, 128, 129), most) == (128, 128, 128)
     assert chunk(policy, (256, 256, 256), most) == (256, 256, 32)        # whole z-slabs of bricks

@@ -4,17 +4,15 @@ extern "C" shim, as tests/test_sample_cpu.py does), the numpy restatement the GP
 against (tests/surface_emulation.py) on analytic fields, and write_ply."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import surface_emulation as E
+from helpers import compile_shim
 from test_sample_cpu import header_prototype
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "smoothed_particle_hydrodynamics_amd", "csrc")
 F32 = np.float32
 
 SHIM = r"""
@@ -31,26 +29,24 @@ int tet_case(int t, int cube_in) { return surf_tet_case(t, cube_in); }
 int planes(const int* dims, int vel, int forced) { return surf_planes(dims, vel != 0, forced); }
 long long scratch_bytes(const int* dims, int planes, int vel) { return surf_scratch(dims, planes, vel != 0).bytes; }
 long long budget() { return SURF_SCRATCH_BUDGET; }
+const char* check(float iso, int flags)
+{
+   const char* why = surf_check(iso, flags);
+   return why ? why : "";
+}
 }
 """
 
 
 @pytest.fixture(scope="module")
 def policy(tmp_path_factory):
-    gxx = shutil.which("g++")
-    if gxx is None:
-        pytest.skip("g++ not available")
-    d = tmp_path_factory.mktemp("surface_policy")
-    src = d / "shim.cpp"
-    src.write_text(SHIM)
-    so = d / "libshim.so"
-    subprocess.run([gxx, "-std=c++17", "-O1", "-Wall", "-Werror", "-shared", "-fPIC", "-I", CSRC, str(src),
-                    "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
+    lib = compile_shim(SHIM, ["-O1"], tmp_path_factory)
     lib.planes.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int]
     lib.scratch_bytes.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int]
     lib.scratch_bytes.restype = C.c_longlong
     lib.budget.restype = C.c_longlong
+    lib.check.argtypes = [C.c_float, C.c_int]
+    lib.check.restype = C.c_char_p
     return lib
 
 
@@ -305,3 +301,28 @@ def test_write_ply_round_trips(tmp_path, with_normals):
         assert n.tobytes() == m.normals.tobytes()
     else:
         assert n is None
+
+
+# ---- iso and flag checks (csrc/surface_policy.h: surf_check) ------------------------------------------
+@pytest.mark.parametrize("iso,flags,why", [
+    # the cases test_gpu_surface.py::test_bad_arguments_are_refused lists
+    (0.0, 0, "iso must be finite and positive"),
+    (-1.0, 0, "iso must be finite and positive"),
+    (float("nan"), 0, "iso must be finite and positive"),
+    (float("inf"), 0, "iso must be finite and positive"),
+    (-float("inf"), 0, "iso must be finite and positive"),
+    (1.0, 4, "unknown flag bits"),
+    (1.0, 8, "unknown flag bits"),
+    (1.0, -1, "unknown flag bits"),
+    (1.0, 1 << 30, "unknown flag bits"),
+    (-0.0, 4, "iso must be finite and positive"),     # the iso is checked first
+    # valid edge cases: both flags, either, none; the smallest and largest positive floats
+    (1.0, 0, ""),
+    (1.0, 1, ""),
+    (1.0, 2, ""),
+    (1.0, 3, ""),
+    (1e-45, 3, ""),
+    (3.4e38, 0, ""),
+])
+def test_surf_check(policy, iso, flags, why):
+    assert policy.check(iso, flags).decode() == why
