@@ -72,6 +72,7 @@ class SphRenderParams(C.Structure):
     ]
 
 
+from . import obstacles as _obstacles  # noqa: E402
 from .obstacles import SphObstacle  # noqa: E402  (mirror of sph_hip_obstacle)
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
@@ -195,6 +196,111 @@ def load_library(path=None):
                           (path, abi & ~ABI_DIAGNOSTIC, ABI_VERSION))
     _LIB = lib
     return lib
+
+
+def _ptr(a):
+    """A numpy array (or None) as the void* argument of an entry point."""
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+class Context:
+    """Owner of one sph_hip_context handle: creation, destruction, the checked call, and the
+    operations that need nothing but the handle.  SPH (sph.py) and HipSlab (slab.py) derive from it."""
+
+    def __init__(self, creator, *args):
+        """creator: name of the entry point that makes the handle ("sph_hip_create",
+        "sph_hip_create_slab"); it is given the handle's address, then `args`."""
+        self._lib = load_library()
+        self._ctx = C.c_void_p()
+        rc = getattr(self._lib, creator)(C.byref(self._ctx), *args)
+        if rc != 0:
+            msg = self._lib.sph_hip_last_error(None).decode()
+            self._ctx = C.c_void_p()
+            raise SphHipError("%s failed (%d): %s" % (creator, rc, msg))
+
+    def close(self):
+        if getattr(self, "_ctx", None) is not None and self._ctx:
+            self._lib.sph_hip_destroy(self._ctx)
+            self._ctx = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def call(self, name, *args):
+        """Entry point `name` with the handle and `args`, checked."""
+        fn = getattr(self._lib, name)
+        return self.check(fn, fn(self._ctx, *args))
+
+    def check(self, fn, rc):
+        """What entry point `fn` returned: a negative value (every SPH_HIP_ERR_* is negative) raises
+        SphHipError with the context's message; anything else is passed on."""
+        if rc < 0:
+            msg = self._lib.sph_hip_last_error(self._ctx).decode()
+            raise SphHipError("%s failed (%d): %s" % (fn.__name__, rc, msg))
+        return rc
+
+    def synchronize(self):
+        self.call("sph_hip_synchronize")
+
+    def tile_stats(self):
+        """dict of the last step's LDS-tile statistics (sph_hip_get_tile_stats)."""
+        out = (C.c_int32 * 20)()
+        self.call("sph_hip_get_tile_stats", C.byref(out))
+        v = list(out)
+        return {"over_level": v[0:12], "workgroups": v[12], "largest_tile": v[13],
+                "untiled_density": v[14], "untiled_acceleration": v[15],
+                "capacity_density": v[16], "capacity_acceleration": v[17], "wide_entries": v[18],
+                "list_capacity": v[19]}
+
+    def phase_totals(self):
+        """(sum of the six phase times in ms over the steps since reset_timings(), steps)"""
+        ms = (C.c_double * 6)()
+        k = C.c_int32()
+        self.call("sph_hip_get_phase_totals", C.byref(ms), C.byref(k))
+        return list(ms), k.value
+
+    def energy(self):
+        """(kinetic, potential) energy total of the last integrate."""
+        ke, pe = C.c_float(), C.c_float()
+        self.call("sph_hip_get_energy", C.byref(ke), C.byref(pe))
+        return ke.value, pe.value
+
+    def reset_timings(self):
+        self.call("sph_hip_reset_timings")
+
+    def set_timing(self, level):
+        """Which intervals a step times: TIMING_PHASES (default, all six), TIMING_SUMS (density +
+        acceleration as one interval, in slot 2), TIMING_OFF.  Resets the collected timings."""
+        self.call("sph_hip_set_timing", int(level))
+
+    def set_timing_stride(self, every):
+        """Record the timing events on every `every`-th step only (sph_hip_set_timing_stride)."""
+        self.call("sph_hip_set_timing_stride", int(every))
+
+    def set_arithmetic(self, arithmetic):
+        """ARITH_EXACT / ARITH_FAST for the pair sums of a FULL-mode context (sph_hip_set_arithmetic)."""
+        self.call("sph_hip_set_arithmetic", int(arithmetic))
+
+    def set_obstacles(self, obstacles):
+        """Replace the static obstacles (obstacles.Sphere / Box / Cylinder, at most 64; an empty list
+        clears them).  Steps already queued keep the old list."""
+        arr, n = _obstacles.as_array(obstacles)
+        self.call("sph_hip_set_obstacles", arr, n)
+
+    def get_obstacles(self):
+        """The context's obstacles, in list order."""
+        arr = (SphObstacle * _obstacles.MAX_OBSTACLES)()
+        n = self.call("sph_hip_get_obstacles", arr, _obstacles.MAX_OBSTACLES)
+        return [_obstacles.from_struct(arr[i]) for i in range(n)]
 
 
 def default_params(h=0.1, cells=(32, 32, 32)):

@@ -9,14 +9,14 @@ process), the slab unpacks what it received and steps.  There is no collective i
 path: each slab talks to its two neighbours only.
 
 The orchestration here is backend-agnostic: `HipSlab` drives the HIP library; the tests plug a
-CPU stand-in with the same five methods to exercise planning, message flow and the
-torch.distributed transport under gloo.
+CPU stand-in with the same attributes and methods (listed at the top of the orchestration section)
+to exercise planning, message flow, rebalancing and the torch.distributed transport under gloo.
 """
 import ctypes as C
 
 import numpy as np
 
-from .lib import SphHipError, load_library
+from .lib import Context, SphHipError, _ptr, load_library
 
 HALO = 2
 HEADER_BYTES = 32
@@ -69,19 +69,13 @@ def message_bytes(capacity_records):
 
 # ---- one slab on one GPU ------------------------------------------------------------------------
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-class HipSlab:
+class HipSlab(Context):
     """A slab context of libsph_hip.so (sph_hip_create_slab) plus its message buffers."""
 
     def __init__(self, params, plane_lo, plane_hi, capacity, msg_capacity, device=0,
                  has_left=True, has_right=True, stream=None):
         import torch
         self._torch = torch
-        self._lib = load_library()
-        self._ctx = C.c_void_p()
         self.params = params.copy()
         self.plane_lo, self.plane_hi = int(plane_lo), int(plane_hi)
         self.capacity, self.msg_capacity = int(capacity), int(msg_capacity)
@@ -90,13 +84,15 @@ class HipSlab:
         self.msg_active = self.msg_capacity
         self._settings = {}
         self._counts_host = None
+        self.all_masses_equal = False      # until upload() / upload_records() say otherwise
         self.device = torch.device("cuda", device)
-        rc = self._lib.sph_hip_create_slab(C.byref(self._ctx), C.byref(self.params), self.capacity,
-                                           int(device), self.plane_lo, self.plane_hi)
-        if rc != 0:
-            msg = self._lib.sph_hip_last_error(None).decode()
-            self._ctx = C.c_void_p()
-            raise SphHipError("sph_hip_create_slab failed (%d): %s" % (rc, msg))
+        super().__init__("sph_hip_create_slab", C.byref(self.params), self.capacity, int(device),
+                         self.plane_lo, self.plane_hi)
+        # the entry points of a step, looked up once and called without call()'s argument
+        # forwarding: DistSlabStepper.step goes through three of them per step
+        lib = self._lib
+        self._pack, self._unpack, self._step = lib.sph_hip_slab_pack, lib.sph_hip_slab_unpack, lib.sph_hip_step
+        self._step_begin, self._step_end = lib.sph_hip_slab_step_begin, lib.sph_hip_slab_step_end
         # All launches of this slab go to ONE torch stream (a real stream object: torch's default
         # stream has the NULL handle, which the C ABI reads as "use the context's own stream").
         # torch.distributed orders its RCCL calls against the stream that is current when they
@@ -104,8 +100,7 @@ class HipSlab:
         # sharing a process share the stream, which orders pack(r) before unpack(r+1).
         with torch.cuda.device(self.device):
             self.stream = stream if stream is not None else torch.cuda.Stream()
-        self._check(self._lib.sph_hip_set_stream(self._ctx, C.c_void_p(self.stream.cuda_stream)),
-                    "set_stream")
+        self.call("sph_hip_set_stream", C.c_void_p(self.stream.cuda_stream))
         nbytes = message_bytes(self.msg_capacity)
         with torch.cuda.stream(self.stream):
             mk = lambda on: (torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
@@ -114,103 +109,76 @@ class HipSlab:
             self.recv_left, self.recv_right = mk(has_left), mk(has_right)
         self.stream.synchronize()
 
-    def close(self):
-        if getattr(self, "_ctx", None) is not None and self._ctx:
-            self._lib.sph_hip_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self._lib.sph_hip_last_error(self._ctx).decode()
-            raise SphHipError("%s failed (%d): %s" % (what, rc, msg))
-
     def upload(self, ids, pos, vel, mass, all_masses_equal):
         ids = np.ascontiguousarray(ids, np.uint32)
         pos = np.ascontiguousarray(pos, np.float32).reshape(-1)
         vel = np.ascontiguousarray(vel, np.float32).reshape(-1)
         mass = np.ascontiguousarray(mass, np.float32)
         self.all_masses_equal = bool(all_masses_equal)
-        self._check(self._lib.sph_hip_slab_upload(self._ctx, ids.size, _ptr(pos), _ptr(vel),
-                                                  _ptr(mass), _ptr(ids), int(all_masses_equal)),
-                    "sph_hip_slab_upload")
+        self.call("sph_hip_slab_upload", ids.size, _ptr(pos), _ptr(vel), _ptr(mass), _ptr(ids),
+                  int(all_masses_equal))
 
     @staticmethod
     def _dp(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
     def pack(self):
-        self._check(self._lib.sph_hip_slab_pack(self._ctx, self._dp(self.send_left),
-                                                self._dp(self.send_right), self.msg_active),
-                    "sph_hip_slab_pack")
+        self.check(self._pack, self._pack(self._ctx, self._dp(self.send_left), self._dp(self.send_right),
+                                          self.msg_active))
 
     def unpack(self, recv_left=None, recv_right=None):
         left = recv_left if recv_left is not None else self.recv_left
         right = recv_right if recv_right is not None else self.recv_right
-        self._check(self._lib.sph_hip_slab_unpack(self._ctx, self._dp(left), self._dp(right),
-                                                  self.msg_active), "sph_hip_slab_unpack")
+        self.check(self._unpack, self._unpack(self._ctx, self._dp(left), self._dp(right), self.msg_active))
 
     def step(self):
-        self._check(self._lib.sph_hip_step(self._ctx), "sph_hip_step")
+        self.check(self._step, self._step(self._ctx))
 
     def step_begin(self, exchange_stream=None):
         """Cell build, density, acceleration of the planes next to a neighbour, messages packed
         into send_left / send_right (sph_hip_slab_step_begin).  exchange_stream: torch stream the
         transport will run on; the border work is enqueued there (None: the slab's stream)."""
         ptr = C.c_void_p(exchange_stream.cuda_stream) if exchange_stream is not None else None
-        self._check(self._lib.sph_hip_slab_step_begin(self._ctx, self._dp(self.send_left),
-                                                      self._dp(self.send_right), self.msg_active,
-                                                      ptr),
-                    "sph_hip_slab_step_begin")
+        self.check(self._step_begin, self._step_begin(self._ctx, self._dp(self.send_left),
+                                                      self._dp(self.send_right), self.msg_active, ptr))
 
     def step_end(self):
         """Acceleration of the interior, integrate (sph_hip_slab_step_end)."""
-        self._check(self._lib.sph_hip_slab_step_end(self._ctx), "sph_hip_slab_step_end")
+        self.check(self._step_end, self._step_end(self._ctx))
 
     # ---- native RCCL exchange (the library issues ncclSend/ncclRecv itself) ----------------------
     def comm_init(self, unique_id, rank, world):
         """Create this slab's RCCL communicator from the 128-byte id every rank shares
         (rccl_unique_id() on one rank, then any broadcast)."""
         buf = (C.c_char * len(unique_id)).from_buffer_copy(bytes(unique_id))
-        self._check(self._lib.sph_hip_slab_comm_init(self._ctx, buf, len(unique_id), int(rank),
-                                                     int(world), self.msg_capacity),
-                    "sph_hip_slab_comm_init")
+        self.call("sph_hip_slab_comm_init", buf, len(unique_id), int(rank), int(world), self.msg_capacity)
 
     def comm_run(self, steps):
         """`steps` steps with the overlapped neighbour exchange, all enqueued by the library."""
-        self._check(self._lib.sph_hip_slab_comm_run(self._ctx, int(steps)), "sph_hip_slab_comm_run")
+        self.call("sph_hip_slab_comm_run", int(steps))
 
     def comm_trim(self, slack=1.25, extra=1024):
         """Native exchange: agree on the message size from what was packed last
         (sph_hip_slab_comm_trim; collective, synchronises)."""
         n = C.c_int32()
-        self._check(self._lib.sph_hip_slab_comm_trim(self._ctx, float(slack), int(extra), C.byref(n)),
-                    "sph_hip_slab_comm_trim")
+        self.call("sph_hip_slab_comm_trim", float(slack), int(extra), C.byref(n))
         self.msg_active = n.value
         return n.value
 
     def comm_selftest(self):
-        self._check(self._lib.sph_hip_slab_comm_selftest(self._ctx), "sph_hip_slab_comm_selftest")
+        self.call("sph_hip_slab_comm_selftest")
 
     def comm_exchange_check(self):
         """One checked message to and from each neighbour through the native calls
         (sph_hip_slab_comm_exchange_check; after comm_init, before the first step)."""
-        self._check(self._lib.sph_hip_slab_comm_exchange_check(self._ctx), "sph_hip_slab_comm_exchange_check")
+        self.call("sph_hip_slab_comm_exchange_check")
 
     def comm_stats(self):
         """dict: records the messages are transferred with / allocated for, growths, steps run
         (sph_hip_slab_comm_stats)."""
         out = (C.c_int32 * 4)()
-        self._check(self._lib.sph_hip_slab_comm_stats(self._ctx, out), "sph_hip_slab_comm_stats")
+        self.call("sph_hip_slab_comm_stats", out)
         return {"active_records": out[0], "capacity_records": out[1], "growths": out[2], "steps": out[3]}
-
-    def synchronize(self):
-        self._check(self._lib.sph_hip_synchronize(self._ctx), "sph_hip_synchronize")
 
     def send_counts(self):
         """Records in the two messages packed last (synchronises the slab's stream)."""
@@ -227,9 +195,7 @@ class HipSlab:
         with torch.cuda.device(self.device):
             buf = torch.empty((self.capacity, 8), dtype=torch.float32, device=self.device)
         rows = C.c_int32()
-        self._check(self._lib.sph_hip_slab_export_records(self._ctx, C.c_void_p(buf.data_ptr()),
-                                                          self.capacity, C.byref(rows)),
-                    "sph_hip_slab_export_records")
+        self.call("sph_hip_slab_export_records", C.c_void_p(buf.data_ptr()), self.capacity, C.byref(rows))
         return buf[:rows.value]
 
     def upload_records(self, records, all_masses_equal):
@@ -240,17 +206,15 @@ class HipSlab:
         assert rec.dtype == torch.float32 and rec.device == self.device and rec.shape[-1] == 8
         self.all_masses_equal = bool(all_masses_equal)
         self._torch.cuda.current_stream(self.device).synchronize()   # the records were made on torch's stream
-        self._check(self._lib.sph_hip_slab_upload_records(self._ctx, C.c_void_p(rec.data_ptr()),
-                                                          int(rec.shape[0]), int(all_masses_equal)),
-                    "sph_hip_slab_upload_records")
+        self.call("sph_hip_slab_upload_records", C.c_void_p(rec.data_ptr()), int(rec.shape[0]),
+                  int(all_masses_equal))
 
     def download_mass(self):
         """Masses of the owned particles, in the row order of download()."""
         cap = self.capacity
         mass = np.zeros(cap, np.float32)
         rows = C.c_int32()
-        self._check(self._lib.sph_hip_slab_download_mass(self._ctx, cap, C.byref(rows), _ptr(mass)),
-                    "sph_hip_slab_download_mass")
+        self.call("sph_hip_slab_download_mass", cap, C.byref(rows), _ptr(mass))
         return mass[:rows.value]
 
     def poll_errors(self):
@@ -258,14 +222,12 @@ class HipSlab:
         SphHipError once a copy of a non-zero error word has reached the host; otherwise asks for
         the next copy and returns the bits seen so far (0)."""
         e = C.c_int32()
-        self._check(self._lib.sph_hip_slab_poll_errors(self._ctx, C.byref(e)),
-                    "sph_hip_slab_poll_errors")
+        self.call("sph_hip_slab_poll_errors", C.byref(e))
         return e.value
 
     def status(self):
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
-        self._check(self._lib.sph_hip_slab_status(self._ctx, C.byref(a), C.byref(b), C.byref(c)),
-                    "sph_hip_slab_status")
+        self.call("sph_hip_slab_status", C.byref(a), C.byref(b), C.byref(c))
         return dict(live=a.value, owned=b.value, errors=c.value)
 
     def download(self):
@@ -274,56 +236,31 @@ class HipSlab:
         out = dict(ids=np.zeros(cap, np.uint32), pos=np.zeros(3 * cap, np.float32),
                    vel=np.zeros(3 * cap, np.float32), rho=np.zeros(cap, np.float32),
                    acc=np.zeros(3 * cap, np.float32), ncount=np.zeros(cap, np.int32))
-        self._check(self._lib.sph_hip_slab_download(self._ctx, cap, C.byref(rows), _ptr(out["ids"]),
-                                                    _ptr(out["pos"]), _ptr(out["vel"]),
-                                                    _ptr(out["rho"]), _ptr(out["acc"]),
-                                                    _ptr(out["ncount"])), "sph_hip_slab_download")
+        self.call("sph_hip_slab_download", cap, C.byref(rows), _ptr(out["ids"]), _ptr(out["pos"]),
+                  _ptr(out["vel"]), _ptr(out["rho"]), _ptr(out["acc"]), _ptr(out["ncount"]))
         n = rows.value
         return dict(ids=out["ids"][:n], pos=out["pos"][:3 * n], vel=out["vel"][:3 * n],
                     rho=out["rho"][:n], acc=out["acc"][:3 * n], ncount=out["ncount"][:n])
 
-    def tile_stats(self):
-        """dict of the last step's LDS-tile statistics (sph_hip_get_tile_stats), as SPH.tileStats()."""
-        out = (C.c_int32 * 20)()
-        self._check(self._lib.sph_hip_get_tile_stats(self._ctx, C.byref(out)), "sph_hip_get_tile_stats")
-        v = list(out)
-        return {"over_level": v[0:12], "workgroups": v[12], "largest_tile": v[13],
-                "untiled_density": v[14], "untiled_acceleration": v[15],
-                "capacity_density": v[16], "capacity_acceleration": v[17], "wide_entries": v[18],
-                "list_capacity": v[19]}
-
-    def phase_totals(self):
-        ms = (C.c_double * 6)()
-        k = C.c_int32()
-        self._check(self._lib.sph_hip_get_phase_totals(self._ctx, C.byref(ms), C.byref(k)),
-                    "sph_hip_get_phase_totals")
-        return list(ms), k.value
-
+    # lib.Context's setters, remembered for settings()
     def set_timing(self, level):
-        self._check(self._lib.sph_hip_set_timing(self._ctx, int(level)), "sph_hip_set_timing")
+        super().set_timing(level)
         self._settings["timing"] = int(level)
 
     def set_timing_stride(self, every):
-        self._check(self._lib.sph_hip_set_timing_stride(self._ctx, int(every)),
-                    "sph_hip_set_timing_stride")
+        super().set_timing_stride(every)
         self._settings["timing_stride"] = int(every)
 
     def set_arithmetic(self, arithmetic):
         """ARITH_EXACT / ARITH_FAST pair arithmetic (sph_hip_set_arithmetic); slabs start exact."""
-        self._check(self._lib.sph_hip_set_arithmetic(self._ctx, int(arithmetic)), "sph_hip_set_arithmetic")
+        super().set_arithmetic(arithmetic)
         self._settings["arithmetic"] = int(arithmetic)
 
     def set_obstacles(self, obstacles):
         """Static obstacles (sph_hip_set_obstacles): the same list on every slab of a run."""
-        from . import obstacles as O
         obstacles = list(obstacles)
-        arr, n = O.as_array(obstacles)
-        self._check(self._lib.sph_hip_set_obstacles(self._ctx, arr, n), "sph_hip_set_obstacles")
+        super().set_obstacles(obstacles)
         self._settings["obstacles"] = obstacles
-
-    def get_obstacles(self):
-        from .sph import _get_obstacles
-        return _get_obstacles(self._lib, self._ctx, self._check)
 
     def settings(self):
         """What set_timing / set_timing_stride / set_arithmetic / set_obstacles were last given: a
@@ -361,17 +298,19 @@ class HipSlab:
         self._counts_pending = True
         return seen
 
-    def reset_timings(self):
-        self._check(self._lib.sph_hip_reset_timings(self._ctx), "sph_hip_reset_timings")
-
-    def energy(self):
-        ke, pe = C.c_float(), C.c_float()
-        self._check(self._lib.sph_hip_get_energy(self._ctx, C.byref(ke), C.byref(pe)),
-                    "sph_hip_get_energy")
-        return ke.value, pe.value
-
 
 # ---- orchestration ------------------------------------------------------------------------------
+#
+# What the transports, steppers and groups below ask of a slab (HipSlab above; the tests' CPU
+# stand-in on CPU tensors).  Every slab has all of it, so nothing here probes for a method:
+#   attributes  params, plane_lo, plane_hi, msg_capacity, msg_active, all_masses_equal,
+#               device (torch.device), stream (a torch stream; None on a CPU stand-in: nothing to
+#               overlap with, no CUDA stream context), send_left / send_right / recv_left /
+#               recv_right (uint8 tensors of message_bytes(msg_capacity), None without that neighbour)
+#   stepping    upload, pack, unpack, step, step_begin(exchange_stream=None), step_end
+#   looking     status, poll_errors, send_counts, poll_send_counts, download
+#   rebalance   export_records, upload_records, settings, apply_settings, close
+
 
 def split_scene(params, cuts, rank, pos, vel, mass):
     """The particles (with their global ids) that slab `rank` owns initially."""
@@ -440,6 +379,18 @@ class NativeSlabStepper:
         return self.slab.comm_stats()["growths"]
 
 
+def neighbour_ops(rank, world, group, send_left, recv_left, send_right, recv_right):
+    """The neighbour exchange as one torch.distributed batch: send to and receive from rank - 1
+    and rank + 1 where they exist (a buffer without its neighbour is not looked at)."""
+    import torch.distributed as dist
+    ops = []
+    for peer, send, recv in ((rank - 1, send_left, recv_left), (rank + 1, send_right, recv_right)):
+        if 0 <= peer < world:
+            ops.append(dist.P2POp(dist.isend, send, peer, group))
+            ops.append(dist.P2POp(dist.irecv, recv, peer, group))
+    return ops
+
+
 def neighbour_exchange_works(rank, world, device, group=None, nbytes=4096, timeout_s=60.0):
     """Pre-flight of the slab exchange: one small batch_isend_irecv with each neighbouring rank on
     `device` ("cuda" for RCCL, "cpu" for gloo), checked for content.  Returns this rank's verdict:
@@ -452,13 +403,7 @@ def neighbour_exchange_works(rank, world, device, group=None, nbytes=4096, timeo
     try:
         mine = torch.full((nbytes,), (rank + 1) & 0xff, dtype=torch.uint8, device=device)
         from_left, from_right = torch.zeros_like(mine), torch.zeros_like(mine)
-        ops = []
-        if rank > 0:
-            ops.append(dist.P2POp(dist.isend, mine, rank - 1, group))
-            ops.append(dist.P2POp(dist.irecv, from_left, rank - 1, group))
-        if rank + 1 < world:
-            ops.append(dist.P2POp(dist.isend, mine, rank + 1, group))
-            ops.append(dist.P2POp(dist.irecv, from_right, rank + 1, group))
+        ops = neighbour_ops(rank, world, group, mine, from_left, mine, from_right)
         # the waiting is done by a helper thread: a transfer that never completes leaves that
         # thread behind (daemon), not the caller
         import threading
@@ -508,30 +453,18 @@ class DistTransport:
         import torch.distributed as dist
         self.dist, self.rank, self.world, self.group = dist, rank, world, group
         self._comm = None
+        self._op_cache = None        # (slab, its op list): the message buffers of a slab never change
 
     def _ops(self, slab):
-        # the message buffers of a slab never change: build the op list once per slab
-        cached = getattr(self, "_op_cache", None)
-        if cached is not None and cached[0] is slab:
-            return cached[1]
-        ops = self._build_ops(slab)
-        self._op_cache = (slab, ops)
-        return ops
-
-    def _build_ops(self, slab):
-        # only the part of a message buffer that can hold records right now travels
-        # (slab.msg_active <= msg_capacity, agreed by all ranks in trim_messages)
-        dist = self.dist
-        nbytes = message_bytes(getattr(slab, "msg_active", slab.msg_capacity))
-        ops = []
-        left, right = self.rank - 1, self.rank + 1
-        if left >= 0:
-            ops.append(dist.P2POp(dist.isend, slab.send_left[:nbytes], left, self.group))
-            ops.append(dist.P2POp(dist.irecv, slab.recv_left[:nbytes], left, self.group))
-        if right < self.world:
-            ops.append(dist.P2POp(dist.isend, slab.send_right[:nbytes], right, self.group))
-            ops.append(dist.P2POp(dist.irecv, slab.recv_right[:nbytes], right, self.group))
-        return ops
+        if self._op_cache is None or self._op_cache[0] is not slab:
+            # only the part of a message buffer that can hold records right now travels
+            # (slab.msg_active <= msg_capacity, agreed by all ranks in trim_messages)
+            nbytes = message_bytes(slab.msg_active)
+            part = lambda m: None if m is None else m[:nbytes]
+            self._op_cache = (slab, neighbour_ops(self.rank, self.world, self.group,
+                                                  part(slab.send_left), part(slab.recv_left),
+                                                  part(slab.send_right), part(slab.recv_right)))
+        return self._op_cache[1]
 
     def forget(self):
         """The slab or its active message size changed: rebuild the op list."""
@@ -543,18 +476,17 @@ class DistTransport:
                 req.wait()          # with RCCL: the current stream waits, the host does not
 
     def exchange(self, slab):
-        stream = getattr(slab, "stream", None)
-        if stream is not None:
-            import torch
-            with torch.cuda.stream(stream):   # RCCL work is ordered against the slab's stream
-                self._run(self._ops(slab))
-        else:
+        if slab.stream is None:
+            self._run(self._ops(slab))
+            return
+        import torch
+        with torch.cuda.stream(slab.stream):   # RCCL work is ordered against the slab's stream
             self._run(self._ops(slab))
 
     def comm_stream(self, slab):
         """The communication stream (high priority: its short border work should not queue behind
         the interior's workgroups); None for a CPU stand-in."""
-        if getattr(slab, "stream", None) is None:
+        if slab.stream is None:
             return None
         if self._comm is None:
             import torch
@@ -576,9 +508,8 @@ class DistTransport:
 
     def finish(self, slab):
         """The slab's stream waits for the exchange started by begin()."""
-        stream = getattr(slab, "stream", None)
-        if stream is not None and self._comm is not None:
-            stream.wait_event(self._arrived)
+        if self._comm is not None:
+            slab.stream.wait_event(self._arrived)
 
 
 class HostStagedTransport(DistTransport):
@@ -597,29 +528,16 @@ class HostStagedTransport(DistTransport):
 
     def exchange(self, slab):
         import torch
-        dist = self.dist
-        left, right = self.rank - 1, self.rank + 1
-        nbytes = message_bytes(getattr(slab, "msg_active", slab.msg_capacity))
+        nbytes = message_bytes(slab.msg_active)
         with torch.cuda.stream(slab.stream):
-            sends = {k: (getattr(slab, "send_" + k)[:nbytes].cpu()
-                         if getattr(slab, "send_" + k) is not None else None)
-                     for k in ("left", "right")}
+            sends = [None if m is None else m[:nbytes].cpu() for m in (slab.send_left, slab.send_right)]
         slab.stream.synchronize()
-        recvs = {k: (torch.empty_like(v) if v is not None else None) for k, v in sends.items()}
-        ops = []
-        if left >= 0:
-            ops.append(dist.P2POp(dist.isend, sends["left"], left, self.group))
-            ops.append(dist.P2POp(dist.irecv, recvs["left"], left, self.group))
-        if right < self.world:
-            ops.append(dist.P2POp(dist.isend, sends["right"], right, self.group))
-            ops.append(dist.P2POp(dist.irecv, recvs["right"], right, self.group))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
+        recvs = [None if m is None else torch.empty_like(m) for m in sends]
+        self._run(neighbour_ops(self.rank, self.world, self.group, sends[0], recvs[0], sends[1], recvs[1]))
         with torch.cuda.stream(slab.stream):
-            for k in ("left", "right"):
-                if recvs[k] is not None:
-                    getattr(slab, "recv_" + k)[:nbytes].copy_(recvs[k], non_blocking=False)
+            for to, got in zip((slab.recv_left, slab.recv_right), recvs):
+                if got is not None:
+                    to[:nbytes].copy_(got, non_blocking=False)
 
 
 class DistSlabStepper:
@@ -648,11 +566,10 @@ class DistSlabStepper:
         the transport's own group, tensors where that group wants them)."""
         self.slab, self.transport = slab, transport
         self.control_group = control_group
-        self.overlap = overlap and hasattr(slab, "step_begin")
+        self.overlap = overlap
         self.make_slab, self.cuts = make_slab, (list(cuts) if cuts is not None else None)
         self.rebalance_every, self.imbalance, self.trim_every = rebalance_every, imbalance, trim_every
         self.rebalances = 0
-        self.device_rebalances = 0      # ... of them without the host in the data path
         self.message_growths = 0
         self._trimmed = False           # trim_messages() has been used: all ranks poll from then on
         self._primed = False
@@ -670,7 +587,7 @@ class DistSlabStepper:
         """where the control group wants its tensors (RCCL: the slab's GPU; gloo: host)"""
         dist = self.transport.dist
         backend = dist.get_backend(self._group())
-        return self.slab.device if backend == "nccl" and hasattr(self.slab, "device") else "cpu"
+        return self.slab.device if backend == "nccl" else "cpu"
 
     def trim_messages(self, slack=1.25, extra=1024):
         """Only the used part of a halo message needs to cross the link: the buffers are sized
@@ -682,8 +599,6 @@ class DistSlabStepper:
         (trim_every).  Collective; synchronises."""
         import torch
         dist, slab = self.transport.dist, self.slab
-        if not hasattr(slab, "send_counts"):
-            return slab.msg_capacity
         self._trimmed = True
         want = min(slab.msg_capacity, int(max(slab.send_counts()) * slack) + extra)
         t = torch.tensor([want], dtype=torch.int64, device=self._device())
@@ -702,9 +617,9 @@ class DistSlabStepper:
         Collective over the control group (a few integers)."""
         import torch
         dist, slab = self.transport.dist, self.slab
-        if not hasattr(slab, "poll_send_counts") or self.transport.world == 1:
+        if self.transport.world == 1:
             return False
-        if getattr(slab, "msg_active", slab.msg_capacity) >= slab.msg_capacity and not self._trimmed:
+        if slab.msg_active >= slab.msg_capacity and not self._trimmed:
             return False
         seen = slab.poll_send_counts()
         wish = 1 if (seen is not None and max(seen) > fill * slab.msg_active) else 0
@@ -721,100 +636,30 @@ class DistSlabStepper:
         """Re-evaluate the cut planes from the current distribution of the particles along z and
         move the particles whose plane changed owner (cuts "re-evaluated
         periodically").  The state itself moves unchanged - ids, positions, velocities, masses - so
-        the run continues bit for bit as if the cuts had always been there.  Collective and
-        host-staged (download, point-to-point exchange of the rows that change owner, upload into a
-        new slab): meant for every few hundred steps.  Returns True if the cuts changed."""
+        the run continues bit for bit as if the cuts had always been there.  The host is not in the
+        data path: the owned particles leave the slab as message records where the slab lives
+        (export_records), are sorted into their new owners there, the rows that change owner travel
+        point-to-point over the transport's own group - device tensors over RCCL; over a gloo group
+        (rehearsals on one GPU) only those rows are staged through the host - and a new slab is
+        filled from the records (upload_records).  The agreements (slab sizes, histogram, row
+        counts) stay on the control group.  Collective: meant for every few hundred steps.  Returns
+        True if the cuts changed."""
         import torch
         dist, tr, slab = self.transport.dist, self.transport, self.slab
         rank, world, group = tr.rank, tr.world, self._group()
         if world == 1 or self.make_slab is None or self.cuts is None:
             return False
-        dev = self._device()
-        owned = torch.tensor([slab.status()["owned"]], dtype=torch.int64, device=dev)
+        cdev = self._device()
+        owned = torch.tensor([slab.status()["owned"]], dtype=torch.int64, device=cdev)
         every = [torch.zeros_like(owned) for _ in range(world)]
         dist.all_gather(every, owned, group=group)
         counts = np.array([int(t.item()) for t in every], np.float64)
         if not force and counts.max() <= self.imbalance * counts.mean():
             return False
-        if hasattr(slab, "export_records"):
-            return self._rebalance_on_device()
-        d = slab.download()
-        mass = slab.download_mass()
-        pos3 = d["pos"].reshape(-1, 3)
-        planes = plane_of(slab.params, pos3[:, 2])
-        nz = slab.params.full_cells_z
-        hist = torch.from_numpy(np.bincount(planes, minlength=nz).astype(np.int64)).to(dev)
-        dist.all_reduce(hist, op=dist.ReduceOp.SUM, group=group)
-        hist = hist.cpu().numpy()
-        new_cuts = cuts_from_histogram(hist, world)
-        if new_cuts == self.cuts:
-            return False
-        # rows {x, y, z, m, vx, vy, vz, id bits} by new owner
-        rows = np.empty((mass.size, 8), np.float32)
-        rows[:, 0:3] = pos3
-        rows[:, 3] = mass
-        rows[:, 4:7] = d["vel"].reshape(-1, 3)
-        rows[:, 7] = d["ids"].view(np.float32)
-        dest = np.searchsorted(np.asarray(new_cuts[1:], np.int64), planes, side="right")
-        out = [np.ascontiguousarray(rows[dest == r]) for r in range(world)]
-        mine = torch.tensor([o.shape[0] for o in out], dtype=torch.int64, device=dev)
-        table = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(table, mine, group=group)          # table[s][r] = rows s sends to r
-        ops, inbox, keep_alive = [], {}, []
-        for peer in range(world):
-            if peer == rank:
-                continue
-            if out[peer].shape[0]:
-                t = torch.from_numpy(out[peer]).to(dev)
-                keep_alive.append(t)
-                ops.append(dist.P2POp(dist.isend, t, peer, group))
-            n_in = int(table[peer][rank].item())
-            if n_in:
-                inbox[peer] = torch.empty((n_in, 8), dtype=torch.float32, device=dev)
-                ops.append(dist.P2POp(dist.irecv, inbox[peer], peer, group))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
-        if dev != "cpu":
-            torch.cuda.synchronize()
-        parts = [out[rank]] + [inbox[k].cpu().numpy() for k in sorted(inbox)]
-        rows = np.concatenate(parts) if len(parts) > 1 else parts[0]
-        rows = rows[np.argsort(rows[:, 7].copy().view(np.uint32), kind="stable")]
-        new_slab = self.make_slab(new_cuts, rank, hist)
-        new_slab.upload(np.ascontiguousarray(rows[:, 7]).view(np.uint32),
-                        np.ascontiguousarray(rows[:, 0:3]).reshape(-1),
-                        np.ascontiguousarray(rows[:, 4:7]).reshape(-1),
-                        np.ascontiguousarray(rows[:, 3]),
-                        all_masses_equal=bool(getattr(slab, "all_masses_equal", False)))
-        # the message size the ranks agreed on stays in force (all of them carry it over alike)
-        new_slab.msg_active = min(getattr(slab, "msg_active", new_slab.msg_capacity),
-                                  new_slab.msg_capacity)
-        # ... and so do the timing level, its stride and the pair arithmetic
-        if hasattr(slab, "settings") and hasattr(new_slab, "apply_settings"):
-            new_slab.apply_settings(slab.settings())
-        if hasattr(slab, "close"):
-            slab.close()
-        self.slab, self.cuts = new_slab, list(new_cuts)
-        self._primed = False            # the new slabs have no ghosts yet
-        tr.forget()
-        self.rebalances += 1
-        return True
-
-    def _rebalance_on_device(self):
-        """rebalance() without the host in the data path: the owned particles leave the slab as
-        message records in device memory (HipSlab.export_records), are sorted into their new
-        owners there, the rows that change owner travel point-to-point over the transport's own
-        group - device tensors over RCCL; over a gloo group (rehearsals on one GPU) only those rows
-        are staged through the host - and the new slab is filled from device records.  The
-        agreements (histogram, row counts) stay on the control group."""
-        import torch
-        dist, tr, slab = self.transport.dist, self.transport, self.slab
-        rank, world, group = tr.rank, tr.world, self._group()
-        cdev = self._device()
         rec = slab.export_records()                       # float32 [n, 8] on the slab's device
         p = slab.params
         nz = int(p.full_cells_z)
-        c = torch.floor(rec[:, 2] * float(np.float32(p.full_cell_inv)))      # plane_of(), on the device
+        c = torch.floor(rec[:, 2] * float(np.float32(p.full_cell_inv)))      # plane_of(), on a tensor
         c = torch.where(torch.isfinite(c), c, torch.full_like(c, -1.0))
         planes = torch.clamp(c, 0, nz - 1).to(torch.int64)
         hist = torch.bincount(planes, minlength=nz).to(torch.int64).to(cdev)
@@ -829,8 +674,7 @@ class DistSlabStepper:
         mine = torch.tensor([o.shape[0] for o in out], dtype=torch.int64, device=cdev)
         table = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(table, mine, group=group)          # table[s][r] = rows s sends to r
-        data_group = tr.group
-        on_device = dist.get_backend(data_group) == "nccl"
+        on_device = dist.get_backend(tr.group) == "nccl"   # else the rows travel as host tensors
         ops, inbox, keep_alive = [], {}, []
         for peer in range(world):
             if peer == rank:
@@ -838,15 +682,13 @@ class DistSlabStepper:
             if out[peer].shape[0]:
                 t = out[peer] if on_device else out[peer].cpu()
                 keep_alive.append(t)
-                ops.append(dist.P2POp(dist.isend, t, peer, data_group))
+                ops.append(dist.P2POp(dist.isend, t, peer, tr.group))
             n_in = int(table[peer][rank].item())
             if n_in:
                 inbox[peer] = torch.empty((n_in, 8), dtype=torch.float32,
                                           device=rec.device if on_device else "cpu")
-                ops.append(dist.P2POp(dist.irecv, inbox[peer], peer, data_group))
-        if ops:
-            for req in dist.batch_isend_irecv(ops):
-                req.wait()
+                ops.append(dist.P2POp(dist.irecv, inbox[peer], peer, tr.group))
+        tr._run(ops)
         if on_device:
             torch.cuda.synchronize()
         parts = [out[rank]] + [inbox[k].to(rec.device) for k in sorted(inbox)]
@@ -854,15 +696,16 @@ class DistSlabStepper:
         ids = rows[:, 7].contiguous().view(torch.int32).to(torch.int64) & 0xffffffff
         rows = rows[torch.argsort(ids, stable=True)].contiguous()
         new_slab = self.make_slab(new_cuts, rank, hist)
-        new_slab.upload_records(rows, bool(getattr(slab, "all_masses_equal", False)))
-        new_slab.msg_active = min(getattr(slab, "msg_active", new_slab.msg_capacity), new_slab.msg_capacity)
+        new_slab.upload_records(rows, slab.all_masses_equal)
+        # the message size the ranks agreed on stays in force (all of them carry it over alike)
+        new_slab.msg_active = min(slab.msg_active, new_slab.msg_capacity)
+        # ... and so do the timing level, its stride, the pair arithmetic and the obstacles
         new_slab.apply_settings(slab.settings())
         slab.close()
         self.slab, self.cuts = new_slab, list(new_cuts)
         self._primed = False            # the new slabs have no ghosts yet
         tr.forget()
         self.rebalances += 1
-        self.device_rebalances += 1
         return True
 
     def step(self):
@@ -870,8 +713,7 @@ class DistSlabStepper:
         # fail loudly: a run that has lost particles (message or capacity overflow, a particle the
         # early exchange missed) stops within 2 * CHECK_EVERY steps instead of running on
         if self._steps % self.CHECK_EVERY == 0:
-            if hasattr(slab, "poll_errors"):
-                slab.poll_errors()
+            slab.poll_errors()
             if self._trimmed:
                 self.grow_messages_if_needed()
         if self._steps > 0:
@@ -892,11 +734,7 @@ class DistSlabStepper:
             tr.exchange(slab)
             slab.unpack()
             self._primed = True
-        comm = tr.comm_stream(slab)
-        if comm is not None:
-            slab.step_begin(comm)
-        else:
-            slab.step_begin()
+        slab.step_begin(tr.comm_stream(slab))
         tr.begin(slab)
         slab.step_end()
         tr.finish(slab)
@@ -928,8 +766,7 @@ class LocalSlabGroup:
     def step(self):
         if self._steps % self.CHECK_EVERY == 0:
             for s in self.slabs:
-                if hasattr(s, "poll_errors"):
-                    s.poll_errors()
+                s.poll_errors()
         self._steps += 1
         if not self.overlap:
             for s in self.slabs:

@@ -14,8 +14,7 @@ import zlib
 
 import numpy as np
 
-from . import obstacles as _obstacles
-from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, SphCamera, SphHipError, SphParams, SphRenderParams, default_params, load_library
+from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Context, SphCamera, SphRenderParams, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
@@ -81,10 +80,6 @@ class Camera:
         return c
 
 
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def _lattice(origin, spacing, shape):
     """origin, spacing and shape of a lattice call as its three C arrays, and shape as a list"""
     o = (C.c_float * 3)(*[float(v) for v in origin])
@@ -95,15 +90,7 @@ def _lattice(origin, spacing, shape):
     return o, s, (C.c_int32 * 3)(*dims), dims
 
 
-def _get_obstacles(lib, ctx, check):
-    arr = (_obstacles.SphObstacle * _obstacles.MAX_OBSTACLES)()
-    n = lib.sph_hip_get_obstacles(ctx, arr, _obstacles.MAX_OBSTACLES)
-    if n < 0:
-        check(n, "sph_hip_get_obstacles")
-    return [_obstacles.from_struct(arr[i]) for i in range(n)]
-
-
-class SPH:
+class SPH(Context):
     """The reference's `SPH` (src/sph.h:15-216) with the step executed on an MI355X.
 
     Differences that are part of the contract:
@@ -117,43 +104,13 @@ class SPH:
     """
 
     def __init__(self, particle_count, params=None, mode=MODE_FULL, device=0, capacity=None):
-        self._lib = load_library()
-        self._ctx = C.c_void_p()
         self.mParticleCount = int(particle_count)
         self.mode = mode
         self._params = params.copy() if params is not None else default_params()
         cap = int(capacity) if capacity is not None else max(1, self.mParticleCount)
-        rc = self._lib.sph_hip_create(C.byref(self._ctx), C.byref(self._params), cap, int(mode),
-                                      int(device))
-        if rc != 0:
-            msg = self._lib.sph_hip_last_error(None).decode()
-            self._ctx = C.c_void_p()
-            raise SphHipError("sph_hip_create failed (%d): %s" % (rc, msg))
+        super().__init__("sph_hip_create", C.byref(self._params), cap, int(mode), int(device))
         self.mSrcParticles = Particle(self.mParticleCount)
         self._mirror_fresh = False
-
-    # ---- lifetime -------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_ctx", None) is not None and self._ctx:
-            self._lib.sph_hip_destroy(self._ctx)
-            self._ctx = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def _check(self, rc, what):
-        if rc != 0:
-            msg = self._lib.sph_hip_last_error(self._ctx).decode()
-            raise SphHipError("%s failed (%d): %s" % (what, rc, msg))
 
     # ---- scene ------------------------------------------------------------------------------
     def setParticles(self, position, velocity, mass):
@@ -171,16 +128,14 @@ class SPH:
         self.mSrcParticles.mPosition[:] = pos
         self.mSrcParticles.mVelocity[:] = vel
         self.mSrcParticles.mMass[:] = m
-        self._check(self._lib.sph_hip_upload(self._ctx, n, _ptr(pos), _ptr(vel), _ptr(m)),
-                    "sph_hip_upload")
+        self.call("sph_hip_upload", n, _ptr(pos), _ptr(vel), _ptr(m))
         self._mirror_fresh = False
 
     def syncParticles(self):
         """Refresh the host `Particle` mirror from the device."""
         p = self.mSrcParticles
-        self._check(self._lib.sph_hip_download(self._ctx, _ptr(p.mPosition), _ptr(p.mVelocity),
-                                               _ptr(p.mDensity), _ptr(p.mAcceleration),
-                                               _ptr(p.mNeighborCount)), "sph_hip_download")
+        self.call("sph_hip_download", _ptr(p.mPosition), _ptr(p.mVelocity), _ptr(p.mDensity),
+                  _ptr(p.mAcceleration), _ptr(p.mNeighborCount))
         self._mirror_fresh = True
         return p
 
@@ -214,16 +169,14 @@ class SPH:
         else:
             ncells = p.full_cells_x * p.full_cells_y * p.full_cells_z
         counts = np.zeros(ncells, np.int32)
-        self._check(self._lib.sph_hip_download_grid_counts(self._ctx, _ptr(counts)),
-                    "sph_hip_download_grid_counts")
+        self.call("sph_hip_download_grid_counts", _ptr(counts))
         return counts
 
     def getParams(self):
         return self._params.copy()
 
     def _push(self):
-        self._check(self._lib.sph_hip_set_params(self._ctx, C.byref(self._params)),
-                    "sph_hip_set_params")
+        self.call("sph_hip_set_params", C.byref(self._params))
 
     def getGravity(self):
         return tuple(self._params.gravity)
@@ -271,26 +224,17 @@ class SPH:
         self._params.cfl_limit2 = float(lim * lim)
         self._push()
 
-    # ---- static obstacles (sph_hip_set_obstacles) ----------------------------------------------
-    def setObstacles(self, obstacles):
-        """Replace the static obstacles (obstacles.Sphere / Box / Cylinder, at most 64; an empty list
-        clears them).  Steps already queued keep the old list."""
-        arr, n = _obstacles.as_array(obstacles)
-        self._check(self._lib.sph_hip_set_obstacles(self._ctx, arr, n), "sph_hip_set_obstacles")
-
-    def getObstacles(self):
-        """The context's obstacles, in list order."""
-        return _get_obstacles(self._lib, self._ctx, self._check)
+    setObstacles, getObstacles = Context.set_obstacles, Context.get_obstacles
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
         """SPH::step() (reference src/sph.cpp:190-304)."""
-        self._check(self._lib.sph_hip_step(self._ctx), "sph_hip_step")
+        self.call("sph_hip_step")
         self._mirror_fresh = False
 
     def run(self, steps):
         """`steps` steps queued back to back (SPH::run's loop body, src/sph.cpp:171-181)."""
-        self._check(self._lib.sph_hip_run(self._ctx, int(steps)), "sph_hip_run")
+        self.call("sph_hip_run", int(steps))
         self._mirror_fresh = False
 
     def runToFiles(self, total_steps, outdir="out"):
@@ -316,12 +260,8 @@ class SPH:
                 ft.write("%d, %s\n" % (s, ", ".join("%.4f" % v for v in self.elapsed())))
                 fn.write("%d, %d, %d\n" % self.neighborStats())
 
-    def synchronize(self):
-        self._check(self._lib.sph_hip_synchronize(self._ctx), "sph_hip_synchronize")
-
     def setArithmetic(self, arithmetic):
-        """ARITH_EXACT / ARITH_FAST for the pair sums of a FULL-mode context (sph_hip_set_arithmetic)."""
-        self._check(self._lib.sph_hip_set_arithmetic(self._ctx, int(arithmetic)), "sph_hip_set_arithmetic")
+        self.set_arithmetic(arithmetic)
         self._mirror_fresh = False
 
     def getArithmetic(self):
@@ -329,24 +269,23 @@ class SPH:
 
     # ---- protected pipeline (reference src/sph.h:96-112) ----------------------------------------
     def voxelizeParticles(self):
-        self._check(self._lib.sph_hip_voxelize(self._ctx), "sph_hip_voxelize")
+        self.call("sph_hip_voxelize")
         self._mirror_fresh = False
 
     def findNeighbors(self):
-        self._check(self._lib.sph_hip_find_neighbors(self._ctx), "sph_hip_find_neighbors")
+        self.call("sph_hip_find_neighbors")
         self._mirror_fresh = False
 
     def computeDensity(self):
-        self._check(self._lib.sph_hip_compute_density(self._ctx), "sph_hip_compute_density")
+        self.call("sph_hip_compute_density")
         self._mirror_fresh = False
 
     def computeAcceleration(self):
-        self._check(self._lib.sph_hip_compute_acceleration(self._ctx),
-                    "sph_hip_compute_acceleration")
+        self.call("sph_hip_compute_acceleration")
         self._mirror_fresh = False
 
     def integrate(self):
-        self._check(self._lib.sph_hip_integrate(self._ctx), "sph_hip_integrate")
+        self.call("sph_hip_integrate")
         self._mirror_fresh = False
 
     # ---- field sampler (sph_hip_sample_points / sph_hip_sample_lattice) ---------------------------
@@ -360,8 +299,7 @@ class SPH:
         rho = np.zeros(n, np.float32)
         vel = np.zeros((n, 3), np.float32) if velocity else None
         cnt = np.zeros(n, np.int32)
-        self._check(self._lib.sph_hip_sample_points(self._ctx, n, _ptr(pts), _ptr(rho), _ptr(vel), _ptr(cnt)),
-                    "sph_hip_sample_points")
+        self.call("sph_hip_sample_points", n, _ptr(pts), _ptr(rho), _ptr(vel), _ptr(cnt))
         return rho, vel, cnt
 
     def sampleLattice(self, origin, spacing, shape, velocity=True):
@@ -375,8 +313,8 @@ class SPH:
         rho = np.zeros(grid, np.float32)
         vel = np.zeros(grid + (3,), np.float32) if velocity else None
         cnt = np.zeros(grid, np.int32)
-        self._check(self._lib.sph_hip_sample_lattice(self._ctx, C.byref(o), C.byref(s), C.byref(d), _ptr(rho),
-                                                     _ptr(vel), _ptr(cnt)), "sph_hip_sample_lattice")
+        self.call("sph_hip_sample_lattice", C.byref(o), C.byref(s), C.byref(d), _ptr(rho), _ptr(vel),
+                  _ptr(cnt))
         return rho, vel, cnt
 
     def extractSurface(self, origin, spacing, shape, iso, normals=True, velocity=False):
@@ -386,15 +324,14 @@ class SPH:
         o, s, d, _ = _lattice(origin, spacing, shape)
         flags = (SURFACE_NORMALS if normals else 0) | (SURFACE_VELOCITY if velocity else 0)
         counts = (C.c_int32 * 2)()
-        self._check(self._lib.sph_hip_extract_surface(self._ctx, C.byref(o), C.byref(s), C.byref(d),
-                                                      float(iso), flags, C.byref(counts)), "sph_hip_extract_surface")
+        self.call("sph_hip_extract_surface", C.byref(o), C.byref(s), C.byref(d), float(iso), flags,
+                  C.byref(counts))
         nv, nt = counts[0], counts[1]
         vtx = np.zeros((nv, 3), np.float32)
         tri = np.zeros((nt, 3), np.int32)
         nrm = np.zeros((nv, 3), np.float32) if normals else None
         vel = np.zeros((nv, 3), np.float32) if velocity else None
-        self._check(self._lib.sph_hip_download_surface(self._ctx, _ptr(vtx), _ptr(nrm), _ptr(vel), _ptr(tri)),
-                    "sph_hip_download_surface")
+        self.call("sph_hip_download_surface", _ptr(vtx), _ptr(nrm), _ptr(vel), _ptr(tri))
         return SurfaceMesh(vtx, tri, nrm, vel)
 
     # ---- renderer (sph_hip_render) ------------------------------------------------------------------
@@ -440,61 +377,26 @@ class SPH:
         vel = np.zeros((H, W, 3), np.float32) if velocity else None
         first = np.zeros((H, W), np.int32)
         cam = camera.as_struct()
-        self._check(self._lib.sph_hip_render(self._ctx, C.byref(cam), C.byref(rp), W, H,
-                                             RENDER_VELOCITY if velocity else 0, _ptr(rgba), _ptr(depth),
-                                             _ptr(normal), _ptr(vel), _ptr(first)), "sph_hip_render")
+        self.call("sph_hip_render", C.byref(cam), C.byref(rp), W, H, RENDER_VELOCITY if velocity else 0,
+                  _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first))
         return RenderResult(rgba, depth, normal, vel, first)
 
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
         """The six numbers of SPH::updateElapsed (reference src/sph.cpp:292-299), in ms."""
         ms = (C.c_float * 6)()
-        self._check(self._lib.sph_hip_get_timings(self._ctx, C.byref(ms)), "sph_hip_get_timings")
+        self.call("sph_hip_get_timings", C.byref(ms))
         return list(ms)
 
-    def resetTimings(self):
-        self._check(self._lib.sph_hip_reset_timings(self._ctx), "sph_hip_reset_timings")
-
-    def setTiming(self, level):
-        """Which intervals step() times: TIMING_PHASES (default, all six), TIMING_SUMS (density +
-        acceleration as one interval, in slot 2), TIMING_OFF.  Resets the collected timings."""
-        self._check(self._lib.sph_hip_set_timing(self._ctx, int(level)), "sph_hip_set_timing")
-
-    def setTimingStride(self, every):
-        """Record the timing events on every `every`-th step() only (sph_hip_set_timing_stride)."""
-        self._check(self._lib.sph_hip_set_timing_stride(self._ctx, int(every)),
-                    "sph_hip_set_timing_stride")
-
-    def tileStats(self):
-        """dict of the last step's LDS-tile statistics (sph_hip_get_tile_stats)."""
-        out = (C.c_int32 * 20)()
-        self._check(self._lib.sph_hip_get_tile_stats(self._ctx, C.byref(out)), "sph_hip_get_tile_stats")
-        v = list(out)
-        return {"over_level": v[0:12], "workgroups": v[12], "largest_tile": v[13],
-                "untiled_density": v[14], "untiled_acceleration": v[15],
-                "capacity_density": v[16], "capacity_acceleration": v[17], "wide_entries": v[18],
-                "list_capacity": v[19]}
-
-    def phaseTotals(self):
-        """(sum of the six phase times in ms over the step() calls since resetTimings(), steps)"""
-        ms = (C.c_double * 6)()
-        k = C.c_int32()
-        self._check(self._lib.sph_hip_get_phase_totals(self._ctx, C.byref(ms), C.byref(k)),
-                    "sph_hip_get_phase_totals")
-        return list(ms), k.value
-
-    def energy(self):
-        """(mKineticEnergyTotal, mPotentialEnergyTotal) of the last integrate."""
-        ke, pe = C.c_float(), C.c_float()
-        self._check(self._lib.sph_hip_get_energy(self._ctx, C.byref(ke), C.byref(pe)),
-                    "sph_hip_get_energy")
-        return ke.value, pe.value
+    # the reference-style names of what every context can do (lib.Context)
+    resetTimings, setTiming = Context.reset_timings, Context.set_timing
+    setTimingStride = Context.set_timing_stride
+    tileStats, phaseTotals = Context.tile_stats, Context.phase_totals
 
     def neighborStats(self):
         """(avg, max, min) as written to out/neighbors.txt (reference src/sph.cpp:232)."""
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
-        self._check(self._lib.sph_hip_get_neighbor_stats(self._ctx, C.byref(a), C.byref(b),
-                                                         C.byref(c)), "sph_hip_get_neighbor_stats")
+        self.call("sph_hip_get_neighbor_stats", C.byref(a), C.byref(b), C.byref(c))
         return a.value, b.value, c.value
 
     def voxels(self):
@@ -502,8 +404,7 @@ class SPH:
         n = self.mParticleCount
         coords = np.zeros(3 * n, np.int32)
         ids = np.zeros(n, np.int32)
-        self._check(self._lib.sph_hip_download_voxels(self._ctx, _ptr(coords), _ptr(ids)),
-                    "sph_hip_download_voxels")
+        self.call("sph_hip_download_voxels", _ptr(coords), _ptr(ids))
         return coords, ids
 
     def neighborLists(self):
@@ -511,8 +412,7 @@ class SPH:
         m = self.mParticleCount * self._params.examine_count
         nb = np.zeros(m, np.uint32)
         nd = np.zeros(m, np.float32)
-        self._check(self._lib.sph_hip_download_neighbor_lists(self._ctx, _ptr(nb), _ptr(nd)),
-                    "sph_hip_download_neighbor_lists")
+        self.call("sph_hip_download_neighbor_lists", _ptr(nb), _ptr(nd))
         return nb, nd
 
 

@@ -1,17 +1,22 @@
 """TEST INFRASTRUCTURE: a CPU stand-in for smoothed_particle_hydrodynamics_amd.slab.HipSlab.
 
-Same methods (upload / pack / unpack / step / step_begin / step_end / download) and the same message format
-(8 int32 header words + 32-byte records), with the step computed by the oracle.  It lets the
+Every attribute and method the orchestration asks of a slab (the list at the top of slab.py's
+orchestration section) and the same message format (8 int32 header words + 32-byte records), with
+the step computed by the oracle.  It lets the
 slab orchestration (planning, message flow, torch.distributed transport) run on CPU tensors
 under gloo.  It lives under tests/ because it calls the oracle; the product never imports it.
 """
 import numpy as np
 import torch
 
+from smoothed_particle_hydrodynamics_amd.lib import SphHipError
 from smoothed_particle_hydrodynamics_amd.slab import HALO, message_bytes, plane_of
 
 
 class FakeSlab:
+    device = torch.device("cpu")
+    stream = None          # nothing to overlap with, no CUDA stream context
+
     def __init__(self, oracle, oparams, plane_lo, plane_hi, msg_capacity, has_left, has_right):
         self.o, self.p = oracle, oparams
         self.plane_lo, self.plane_hi = plane_lo, plane_hi
@@ -25,6 +30,7 @@ class FakeSlab:
         self.ghosts = None
         self.last = None
         self.errors = 0
+        self.all_masses_equal = False
         self._settings = {}
         self._counts_seen = None
 
@@ -116,7 +122,7 @@ class FakeSlab:
                          acc=out["acc"].reshape(-1, 3)[sel], ncount=out["ncount"][sel])
         self.ghosts = None
 
-    def step_begin(self):
+    def step_begin(self, exchange_stream=None):
         """Early-exchange protocol: the messages are ready before the step has finished.  Here
         the whole step simply runs first; what matters is the order of calls the stepper makes."""
         self.step()
@@ -130,8 +136,27 @@ class FakeSlab:
         return dict(ids=l["ids"], pos=l["pos"].reshape(-1), vel=l["vel"].reshape(-1),
                     rho=l["rho"], acc=l["acc"].reshape(-1), ncount=l["ncount"])
 
-    def download_mass(self):
-        return self.last["mass"]
+    def export_records(self):
+        """as HipSlab.export_records: the particles owned during the last step (download()'s rows)
+        as float32 [n, 8] message records {x, y, z, m, vx, vy, vz, id bits}"""
+        l = self.last
+        rec = np.empty((l["ids"].size, 8), np.float32)
+        rec[:, 0:3] = l["pos"]
+        rec[:, 3] = l["mass"]
+        rec[:, 4:7] = l["vel"]
+        rec[:, 7] = l["ids"].view(np.float32)
+        return torch.from_numpy(rec)
+
+    def upload_records(self, records, all_masses_equal):
+        assert records.dtype == torch.float32 and records.device == self.device and records.shape[-1] == 8
+        rec = records.contiguous().numpy()
+        self.upload(rec[:, 7].copy().view(np.uint32), rec[:, 0:3], rec[:, 4:7], rec[:, 3], all_masses_equal)
+
+    def poll_errors(self):
+        """as HipSlab.poll_errors: a slab that has lost particles stops the run"""
+        if self.errors:
+            raise SphHipError("fake slab: exchange error bits 0x%x" % self.errors)
+        return 0
 
     def send_counts(self):
         return tuple(int(m.numpy()[:4].view(np.int32)[0]) if m is not None else 0

@@ -140,6 +140,18 @@ def finite_parts(a, b, what=""):
     return np.where(keep, a, 0.0), np.where(keep, b, 0.0)
 
 
+def count_calls(cls, *names):
+    """Wrap the methods `names` of `cls` (for the rest of the process): every call appends the
+    method's name to the list returned here, then goes on to the method."""
+    calls = []
+    for name in names:
+        def counted(self, *args, _inner=getattr(cls, name), _name=name, **kwargs):
+            calls.append(_name)
+            return _inner(self, *args, **kwargs)
+        setattr(cls, name, counted)
+    return calls
+
+
 def energy_rtol(n):
     """the reference accumulates N fp32 terms serially: ~sqrt(N) * 2^-24 relative, x8 margin"""
     return 1e-6 + 8.0 * np.sqrt(float(n)) * 2.0 ** -24

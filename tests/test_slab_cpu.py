@@ -140,6 +140,7 @@ def _worker_rebalance(rank, world, port, steps, outdir, overlap):
     try:
         from oracle.oracle import Oracle
         from fake_slab import FakeSlab
+        from helpers import count_calls
         from smoothed_particle_hydrodynamics_amd.slab import (DistSlabStepper, DistTransport,
                                                               plan_cuts, split_scene)
         o = Oracle()
@@ -156,10 +157,13 @@ def _worker_rebalance(rank, world, port, steps, outdir, overlap):
                                   make_slab=make_slab, cuts=cuts, rebalance_every=3, imbalance=1.02,
                                   trim_every=4)
         history, active = [list(cuts)], []
+        downloads = count_calls(FakeSlab, "download")
         for _ in range(steps):
             stepper.step()
             history.append(list(stepper.cuts))
             active.append(stepper.slab.msg_active)
+        # the rebalances went the way a HipSlab's go: records out, records in, no host download
+        assert downloads == []
         d = stepper.slab.download()
         assert stepper.slab.status()["errors"] == 0
         np.savez(os.path.join(outdir, "rank%d.npz" % rank), cuts=np.array(history),
@@ -213,6 +217,7 @@ def _worker_growth(rank, world, port, steps, outdir):
     try:
         from oracle.oracle import Oracle
         from fake_slab import FakeSlab
+        from helpers import count_calls
         from smoothed_particle_hydrodynamics_amd.slab import (DistSlabStepper, DistTransport,
                                                               plan_cuts, split_scene)
         o = Oracle()
@@ -235,6 +240,7 @@ def _worker_growth(rank, world, port, steps, outdir):
                                   cuts=cuts, rebalance_every=0, control_group=control)
         stepper.CHECK_EVERY = 2
         active = []
+        downloads = count_calls(FakeSlab, "download")
         for s in range(steps):
             if s == 2:
                 stepper.trim_messages(slack=1.05, extra=4)      # tight on purpose
@@ -242,6 +248,7 @@ def _worker_growth(rank, world, port, steps, outdir):
                 stepper.rebalance(force=True)
             stepper.step()
             active.append(stepper.slab.msg_active)
+        assert downloads == []          # the rebalance moved records, as a HipSlab's does
         final = stepper.slab
         assert final is not slab and getattr(slab, "closed", False)
         assert final.settings() == {"timing": 1, "timing_stride": 5, "arithmetic": 1}
