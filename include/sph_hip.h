@@ -473,6 +473,47 @@ typedef struct sph_hip_obstacle {   /* field order is ABI: 48 bytes */
 int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, int n);
 int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity);
 
+/* ---- loads on walls and obstacles --------------------------------------------------------- *
+ *
+ * The impulse the fluid gives to each domain wall and each obstacle, step by step, summed on the
+ * device.  No counterpart in the reference.  The operation-by-operation contract is in
+ * csrc/load_policy.h.
+ *   solids     column s of a row: 0..5 the walls x-lo, x-hi, y-lo, y-hi, z-lo, z-hi; 6 + i obstacle i
+ *              of the list in force when the step was enqueued.  A row always has
+ *              SPH_HIP_LOAD_SOLIDS columns; unused ones stay zero.
+ *   response   one wall reflection of integrate (apply_walls), or one obstacle's turn at a particle
+ *              whose new position is inside it.  With vb / va the particle's velocity just before /
+ *              after it and m its mass: j_c = m * (vb_c - va_c) per component in fp32, the impulse
+ *              given to the solid.
+ *   sum        s_c = (double)j_c * 2^(-quantum_log2).  If the three s_c are finite and below 2^38 in
+ *              magnitude, llrint(s_c) (ties to even) is added to impulse[s][c] and 1 to count[s];
+ *              otherwise nothing is added and skipped[s] grows by 1.  All accumulators are int64:
+ *              a row is the same for every thread order, every route (sph_hip_step, sph_hip_run, the
+ *              phase calls) and every number of slabs (add the slabs' rows), and REF, FULL and
+ *              FULL_FAST differ only by what their velocities differ by.  impulse * 2^quantum_log2 is
+ *              the impulse in mass * velocity units; divided by time_step, the mean force of the step.
+ *              The default quantum_log2 = -24 suits unit masses: terms up to 16384 are kept.
+ * sph_hip_record_loads allocates and zeroes `rows` rows on the context's stream and restarts at row
+ * 0; rows = 0 stops recording and frees them.  Row r belongs to the r-th integrate enqueued after the
+ * call, whichever way (sph_hip_step, sph_hip_run, sph_hip_integrate, sph_hip_slab_step_end,
+ * sph_hip_slab_comm_run); no step synchronises for it.  Only owned particles are recorded, once.  While
+ * rows are left the context integrates in a kernel of its own behind the acceleration pass
+ * (k_integrate_loads); once they are used up, steps are not recorded and take their usual routes.  A
+ * recording changes no particle: positions, velocities and energies are bit-identical to a run
+ * without it.  SPH_HIP_ERR_INVALID, the previous recording kept, for rows < 0, quantum_log2 outside
+ * [-64, 32], and on a slab between sph_hip_slab_step_begin and sph_hip_slab_step_end;
+ * SPH_HIP_ERR_CAPACITY when the rows cannot be allocated.
+ * sph_hip_get_loads synchronises and copies rows [first_row, first_row + n_rows) to host arrays, any of
+ * which may be NULL; *rows_recorded = rows filled so far.  SPH_HIP_ERR_INVALID when nothing is being
+ * recorded or the range leaves the allocated rows.
+ * These two entry points were added without a change of SPH_HIP_ABI_VERSION: no struct and no
+ * existing prototype changed.  A host that must run with older libraries looks the symbols up. */
+#define SPH_HIP_LOAD_SOLIDS (6 + SPH_HIP_MAX_OBSTACLES)
+int sph_hip_record_loads(sph_hip_context* ctx, int rows, int quantum_log2);
+/* impulse[n_rows][SPH_HIP_LOAD_SOLIDS][3], count[n_rows][SPH_HIP_LOAD_SOLIDS], skipped likewise */
+int sph_hip_get_loads(sph_hip_context* ctx, int first_row, int n_rows, int64_t* impulse, int64_t* count,
+                      int64_t* skipped, int32_t* rows_recorded);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "cell_build.h"
+#include "load_policy.h"
 #include "obstacle_policy.h"
 #include "pair_math.h"
 
@@ -50,9 +51,11 @@ __device__ __forceinline__ void handle_boundaries(const PairConsts& k, const flo
 // point-mass gravity only, evaluated at the new position (reference src/sph.cpp:937-1022).
 // Updates x (position, mass kept) and v (velocity, id kept); ke/pe = the particle's energy terms.
 // `after` (ObstacleHook: static obstacles) runs on (old position, new velocity, new position) after
-// the wall handling, before the energy terms; the default does nothing.
+// the wall handling, before the energy terms; the default does nothing.  A hook that `records`
+// (LoadHook: sph_hip_record_loads) also sees every wall response, and is given the particle's mass.
 struct NoHook {
    static constexpr bool active = false;
+   static constexpr bool records = false;
    __device__ void operator()(const float*, float*, float*) const {}
 };
 template <bool UNIT_SCALE, class Hook>
@@ -113,14 +116,16 @@ __device__ __forceinline__ void integrate_particle_hooked(const PairConsts& k, f
    if (k.apply_walls) { // extension: the reference's own (unwired) wall handling
       const float pos[3] = {x.x, x.y, x.z};
       float nv[3] = {nvx, nvy, nvz}, np[3] = {nx, ny, nz};
-      handle_boundaries(k, pos, nv, dt, np);
+      if constexpr (Hook::records) after.walls(k, pos, nv, dt, np, x.w);
+      else handle_boundaries(k, pos, nv, dt, np);
       nvx = nv[0]; nvy = nv[1]; nvz = nv[2];
       nx = np[0]; ny = np[1]; nz = np[2];
    }
    if constexpr (Hook::active) {
       const float pos[3] = {x.x, x.y, x.z};
       float nv[3] = {nvx, nvy, nvz}, np[3] = {nx, ny, nz};
-      after(pos, nv, np);
+      if constexpr (Hook::records) after(pos, nv, np, x.w);
+      else after(pos, nv, np);
       nvx = nv[0]; nvy = nv[1]; nvz = nv[2];
       nx = np[0]; ny = np[1]; nz = np[2];
    }
@@ -141,12 +146,60 @@ __device__ __forceinline__ void integrate_particle_hooked(const PairConsts& k, f
 // obstacle - measured slower: 2.03x instead of 1.30x the obstacle-free step with 64 obstacles.)
 struct ObstacleHook {
    static constexpr bool active = true;
+   static constexpr bool records = false;
    const sph_hip_obstacle* list;
    int n;
    float dt, damping;
    __device__ void operator()(const float* p, float* v, float* q) const
    {
       for (int i = 0; i < n; i++) obstacle_respond(list[i], p, v, q, dt, damping);
+   }
+};
+
+// Load recording (load_policy.h; sph_hip_record_loads): the wall and obstacle responses of
+// load_policy.h with this hook as their recorder.  Every lane of the wave calls record() for every
+// solid in turn (k_integrate_loads keeps the lanes without a particle in step, live = false), so
+// the solid is wave-uniform: one vote, and only where some lane was hit a wave reduction of the three
+// terms and the two counters and one 64-bit atomic add per non-zero sum into the step's row.
+struct LoadHook {
+   static constexpr bool active = true;
+   static constexpr bool records = true;
+   const sph_hip_obstacle* list;
+   int n;
+   float dt, damping;
+   unsigned long long* row;   // LOAD_ROW_WORDS words of this step
+   double scale;              // load_scale(quantum_log2)
+   bool live;
+   __device__ void operator()(int s, bool hit, float m, const float* vb, const float* va) const
+   {
+      hit = hit && live;
+      if (!__any(hit)) return;
+      long long sum[5] = {0, 0, 0, 0, 0};   // the term, count, skipped
+      if (hit) {
+         if (load_term(m, vb, va, scale, sum)) sum[3] = 1;
+         else sum[4] = 1;
+      }
+#pragma unroll
+      for (int d = SPH_WAVE / 2; d > 0; d >>= 1) {
+#pragma unroll
+         for (int i = 0; i < 5; i++) sum[i] += __shfl_down(sum[i], d);
+      }
+      if ((threadIdx.x & (SPH_WAVE - 1)) == 0) {
+#pragma unroll
+         for (int c = 0; c < 3; c++)
+            if (sum[c] != 0) atomicAdd(row + 3 * s + c, (unsigned long long)sum[c]);
+         if (sum[3] != 0) atomicAdd(row + LOAD_ROW_COUNT + s, (unsigned long long)sum[3]);
+         if (sum[4] != 0) atomicAdd(row + LOAD_ROW_SKIPPED + s, (unsigned long long)sum[4]);
+      }
+   }
+   __device__ void walls(const PairConsts& k, const float* pos, float* nv, float dt_, float* np, float m) const
+   {
+      const float maxv[3] = {k.max_x, k.max_y, k.max_z};
+      load_walls_respond(maxv, k.damping, pos, nv, dt_, np, m, *this);
+   }
+   __device__ void operator()(const float* p, float* v, float* q, float m) const
+   {
+      load_obstacles_respond(list, n, p, v, q, dt, damping, m, *this);
    }
 };
 
@@ -248,6 +301,66 @@ k_integrate_obst(float4* __restrict__ posm, float4* __restrict__ velp, const flo
          c = cell_of(g, x.x, x.y, x.z, cx, cy, cz);
          key[p] = c;
       }
+   }
+   if (HASH) count_cell_runs(c, live, p, cell_count, slot, (uint32_t)g.ncells);
+   // block reduction, fixed order
+   __shared__ double s_ke[RED_THREADS / SPH_WAVE], s_pe[RED_THREADS / SPH_WAVE];
+#pragma unroll
+   for (int d = SPH_WAVE / 2; d > 0; d >>= 1) {
+      ke += __shfl_down(ke, d);
+      pe += __shfl_down(pe, d);
+   }
+   const int lane = threadIdx.x & (SPH_WAVE - 1), w = threadIdx.x / SPH_WAVE;
+   if (lane == 0) {
+      s_ke[w] = ke;
+      s_pe[w] = pe;
+   }
+   __syncthreads();
+   if (threadIdx.x == 0) {
+      double a = 0.0, b = 0.0;
+#pragma unroll
+      for (int q = 0; q < RED_THREADS / SPH_WAVE; q++) {
+         a += s_ke[q];
+         b += s_pe[q];
+      }
+      epart[2 * blockIdx.x + 0] = a;
+      epart[2 * blockIdx.x + 1] = b;
+   }
+}
+
+// k_integrate_obst (n_obst may be 0: k_integrate) that also adds every wall and obstacle response to
+// `row`, this step's row of the context's load recording (LoadHook above).  Lanes past the last owned
+// particle integrate a particle of zeros, so that the whole wave takes part in the votes and
+// reductions; nothing of it is stored, recorded or summed.
+template <bool UNIT_SCALE, bool HASH>
+__global__ void __launch_bounds__(RED_THREADS)
+k_integrate_loads(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
+                  const int32_t* __restrict__ meta, PairConsts k, double* __restrict__ epart, CellGrid g,
+                  uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                  uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                  unsigned long long* __restrict__ row, int quantum_log2)
+{
+   // owned particles only: ghosts are integrated by the slab that owns them
+   const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   double ke = 0.0, pe = 0.0;
+   const bool live = p < meta[META_OWN_END];
+   const LoadHook after = {obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live};
+   uint32_t c = 0xffffffffu;
+   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+   float4 x = live ? posm[p] : zero;
+   float4 v = live ? velp[p] : zero;
+   integrate_particle<UNIT_SCALE>(k, x, v, live ? acc[p] : zero, ke, pe, after);
+   if (live) {
+      posm[p] = x;
+      velp[p] = v;
+      if (HASH) {
+         int cx, cy, cz;
+         c = cell_of(g, x.x, x.y, x.z, cx, cy, cz);
+         key[p] = c;
+      }
+   } else {
+      ke = 0.0;
+      pe = 0.0;
    }
    if (HASH) count_cell_runs(c, live, p, cell_count, slot, (uint32_t)g.ncells);
    // block reduction, fixed order

@@ -302,6 +302,12 @@ struct sph_hip_context {
    Event ev_obst_copied;
    int obst_copy_pending = 0;
    int slab_step_open = 0;         // between sph_hip_slab_step_begin and _end (the list must not change)
+
+   // load recording (sph_hip_record_loads): loads_rows rows of LOAD_ROW_WORDS int64, the next integrate
+   // enqueued fills row loads_next (load_row below)
+   DevBuf<unsigned long long> loads_dev;
+   int loads_rows = 0, loads_next = 0;
+   int loads_quantum = LOAD_QUANTUM_DEFAULT;
 };
 
 namespace {
@@ -323,6 +329,9 @@ int Scratch<T>::reserve(sph_hip_context* ctx, size_t count, const char* capacity
    cap = count;
    return SPH_HIP_OK;
 }
+
+// whether the next integrate enqueued fills a row of the load recording
+bool loads_pending(const sph_hip_context* ctx) { return ctx->loads_next < ctx->loads_rows; }
 
 int check_ctx(sph_hip_context* ctx)
 {

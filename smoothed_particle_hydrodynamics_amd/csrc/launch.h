@@ -521,15 +521,24 @@ int launch_accel(sph_hip_context* ctx, int part = 0, hipStream_t part_stream = n
 }
 
 // with_hash: the kernel also does the first step of the next cell build (see k_integrate);
-// with static obstacles, k_integrate_obst
+// with static obstacles, k_integrate_obst; while a load recording has rows left, k_integrate_loads
+// into the next row (an integrate without particles uses its row up too: the rows of the slabs of
+// one run stay in step)
 int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
 {
    const int n = ctx->n;
+   unsigned long long* load_row = nullptr;
+   if (loads_pending(ctx)) load_row = ctx->loads_dev.get() + (size_t)ctx->loads_next++ * LOAD_ROW_WORDS;
    if (n == 0) return SPH_HIP_OK;
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const int blocks = div_up(n, RED_THREADS);
    bind_flags([&](auto U, auto H) {
-      if (ctx->n_obst > 0)
+      if (load_row)
+         hipLaunchKernelGGL((k_integrate_loads<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,
+                            load_row, ctx->loads_quantum);
+      else if (ctx->n_obst > 0)
          hipLaunchKernelGGL((k_integrate_obst<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
                             ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
                             ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst);
@@ -629,7 +638,8 @@ int step_impl(sph_hip_context* ctx, bool timed)
    // hashes and counts for the next cell build - and the tiled acceleration pass does both itself
    const bool hash_too = ctx->mode == SPH_HIP_MODE_FULL && !ctx->had_exchange && ctx->plane_lo == 0 &&
                          ctx->plane_hi == ctx->grid.nz_global && !ctx->no_prehash;
-   const bool fused = fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst);
+   const bool fused = fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
+                                     loads_pending(ctx));
    if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;
    if (fused) fused_step_done(ctx, 1);

@@ -257,15 +257,22 @@ inline PlaneRanges plane_ranges(int plane_lo, int plane_hi, int z0, int nz, int 
 // (FusedStep), instead of a k_integrate launch behind it: `hash_too` (FULL mode, whole grid, never
 // exchanged, prehash allowed), the tiled kernels, particles to move, no SPH_HIP_NO_FUSED_INTEGRATE,
 // and no static obstacles - their response runs in k_integrate_obst, the fused kernels stay as tuned.
-inline bool fuse_integrate(bool hash_too, bool tiled, int n, bool no_fused_integrate, int n_obstacles)
+// record_loads: the step fills a row of a load recording (sph_hip_record_loads), which only
+// k_integrate_loads does.
+inline bool fuse_integrate(bool hash_too, bool tiled, int n, bool no_fused_integrate, int n_obstacles,
+                           bool record_loads = false)
 {
-   return hash_too && tiled && n > 0 && !no_fused_integrate && n_obstacles == 0;
+   return hash_too && tiled && n > 0 && !no_fused_integrate && n_obstacles == 0 && !record_loads;
 }
 
 // Whether a slab's early-exchange step (sph_hip_slab_step_begin / _end) integrates, hashes and packs
 // in its acceleration launches (FusedStep.slab), instead of k_slab_pack_early + k_integrate: not
-// with SPH_HIP_NO_FUSED_SLAB, nor with static obstacles (k_slab_pack_early_obst + k_integrate_obst).
-inline bool fuse_slab_step(bool no_fused_slab, int n_obstacles) { return !no_fused_slab && n_obstacles == 0; }
+// with SPH_HIP_NO_FUSED_SLAB, nor with static obstacles (k_slab_pack_early_obst + k_integrate_obst),
+// nor while a load recording has rows left (k_slab_pack_early[_obst] + k_integrate_loads).
+inline bool fuse_slab_step(bool no_fused_slab, int n_obstacles, bool record_loads = false)
+{
+   return !no_fused_slab && n_obstacles == 0 && !record_loads;
+}
 
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring

@@ -90,8 +90,9 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
    // The two parts of the acceleration launch do the rest of the step themselves (FusedStep):
    // integrate into the other pair of state buffers, hash for the next build, and - the border
    // part - the messages.  SPH_HIP_NO_FUSED_SLAB=1, or static obstacles, keep k_slab_pack_early +
-   // k_integrate (their _obst forms).
-   ctx->slab_fused = fuse_slab_step(ctx->no_fused_slab != 0, ctx->n_obst) ? 1 : 0;
+   // k_integrate (their _obst forms); so does a load recording with rows left (k_slab_pack_early
+   // records nothing: the border particles are counted once, by k_integrate_loads).
+   ctx->slab_fused = fuse_slab_step(ctx->no_fused_slab != 0, ctx->n_obst, loads_pending(ctx)) ? 1 : 0;
    ctx->slab_step_open = 1;
    ctx->slab_msgs[0] = left_device;
    ctx->slab_msgs[1] = right_device;

@@ -841,6 +841,70 @@ int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capac
    return ctx->n_obst;
 }
 
+// ---- loads on walls and obstacles (load_policy.h; kernel: k_integrate_loads) ----------------------
+
+int sph_hip_record_loads(sph_hip_context* ctx, int rows, int quantum_log2)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = load_check(rows, quantum_log2)) {
+      ctx->err = std::string("sph_hip_record_loads: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (ctx->slab_step_open) {
+      ctx->err = "sph_hip_record_loads: not between sph_hip_slab_step_begin and sph_hip_slab_step_end";
+      return SPH_HIP_ERR_INVALID;
+   }
+   DevBuf<unsigned long long> fresh;
+   if (rows > 0) {
+      const size_t words = (size_t)rows * LOAD_ROW_WORDS;
+      if (dev_alloc(fresh, words) != hipSuccess) {
+         (void)hipGetLastError();
+         ctx->err = "sph_hip_record_loads: cannot allocate " + std::to_string(rows) + " rows";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      SPH_TRY(hipMemsetAsync(fresh, 0, words * sizeof(unsigned long long), ctx->stream));
+   }
+   // steps already queued may still be adding to the rows this call replaces
+   if (ctx->loads_dev) SPH_TRY(hipStreamSynchronize(ctx->stream));
+   ctx->loads_dev = std::move(fresh);
+   ctx->loads_rows = rows;
+   ctx->loads_next = 0;
+   ctx->loads_quantum = quantum_log2;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_loads(sph_hip_context* ctx, int first_row, int n_rows, int64_t* impulse, int64_t* count,
+                      int64_t* skipped, int32_t* rows_recorded)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!ctx->loads_dev) {
+      ctx->err = "sph_hip_get_loads: nothing is being recorded (sph_hip_record_loads)";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (const char* why = load_range_check(first_row, n_rows, ctx->loads_rows)) {
+      ctx->err = std::string("sph_hip_get_loads: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (rows_recorded) *rows_recorded = ctx->loads_next;
+   if (n_rows == 0) return SPH_HIP_OK;
+   // a device row is impulse | count | skipped: one strided copy per output
+   const size_t word = sizeof(int64_t), S = SPH_HIP_LOAD_SOLIDS;
+   const unsigned long long* first = ctx->loads_dev.get() + (size_t)first_row * LOAD_ROW_WORDS;
+   if (impulse)
+      SPH_TRY(hipMemcpy2D(impulse, 3 * S * word, first, LOAD_ROW_WORDS * word, 3 * S * word, (size_t)n_rows,
+                          hipMemcpyDeviceToHost));
+   if (count)
+      SPH_TRY(hipMemcpy2D(count, S * word, first + LOAD_ROW_COUNT, LOAD_ROW_WORDS * word, S * word, (size_t)n_rows,
+                          hipMemcpyDeviceToHost));
+   if (skipped)
+      SPH_TRY(hipMemcpy2D(skipped, S * word, first + LOAD_ROW_SKIPPED, LOAD_ROW_WORDS * word, S * word,
+                          (size_t)n_rows, hipMemcpyDeviceToHost));
+   return SPH_HIP_OK;
+}
+
 int sph_hip_synchronize(sph_hip_context* ctx)
 {
    int rc = check_ctx(ctx);

@@ -124,6 +124,8 @@ PROTOTYPES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_set_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_get_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
+    "sph_hip_record_loads": (C.c_int, [_ctx, C.c_int, C.c_int]),
+    "sph_hip_get_loads": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -201,6 +203,45 @@ def load_library(path=None):
 def _ptr(a):
     """A numpy array (or None) as the void* argument of an entry point."""
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+LOAD_SOLIDS = 6 + _obstacles.MAX_OBSTACLES   # SPH_HIP_LOAD_SOLIDS
+LOAD_QUANTUM_LOG2 = -24                      # the default quantum of a load recording
+LOAD_NAMES = tuple(["x-lo", "x-hi", "y-lo", "y-hi", "z-lo", "z-hi"] +
+                   ["obstacle %d" % i for i in range(_obstacles.MAX_OBSTACLES)])
+
+
+class Loads:
+    """The rows of a load recording (sph_hip_get_loads), one per recorded step:
+    impulse_q int64 [steps, LOAD_SOLIDS, 3], the impulse given to each solid in quanta of
+    `quantum` = 2**quantum_log2; count and skipped int64 [steps, LOAD_SOLIDS], the responses summed
+    and those left out (a term that was not finite or reached 2^38 quanta); names: the columns.
+    Rows of several slabs add up exactly: a + b."""
+
+    names = LOAD_NAMES
+
+    def __init__(self, impulse_q, count, skipped, quantum_log2):
+        self.impulse_q, self.count, self.skipped = impulse_q, count, skipped
+        self.quantum_log2 = int(quantum_log2)
+
+    @property
+    def quantum(self):
+        return 2.0 ** self.quantum_log2
+
+    @property
+    def impulse(self):
+        """float64 [steps, LOAD_SOLIDS, 3], in mass * velocity units"""
+        return self.impulse_q.astype("float64") * self.quantum
+
+    def force(self, time_step):
+        """the mean force on each solid during each step: impulse / time_step"""
+        return self.impulse / float(time_step)
+
+    def __add__(self, other):
+        if self.quantum_log2 != other.quantum_log2 or self.impulse_q.shape != other.impulse_q.shape:
+            raise ValueError("loads of different quanta or step counts do not add")
+        return Loads(self.impulse_q + other.impulse_q, self.count + other.count, self.skipped + other.skipped,
+                     self.quantum_log2)
 
 
 class Context:
@@ -301,6 +342,24 @@ class Context:
         arr = (SphObstacle * _obstacles.MAX_OBSTACLES)()
         n = self.call("sph_hip_get_obstacles", arr, _obstacles.MAX_OBSTACLES)
         return [_obstacles.from_struct(arr[i]) for i in range(n)]
+
+    def record_loads(self, steps, quantum_log2=LOAD_QUANTUM_LOG2):
+        """Record the impulse the next `steps` steps give to every wall and obstacle
+        (sph_hip_record_loads); steps = 0 stops and frees the recording."""
+        self.call("sph_hip_record_loads", int(steps), int(quantum_log2))
+        self._loads_quantum_log2 = int(quantum_log2)
+
+    def get_loads(self):
+        """The rows recorded so far, as a Loads (sph_hip_get_loads; synchronises)."""
+        import numpy as np
+        done = C.c_int32()
+        self.call("sph_hip_get_loads", 0, 0, None, None, None, C.byref(done))
+        n = done.value
+        imp = np.zeros((n, LOAD_SOLIDS, 3), np.int64)
+        cnt = np.zeros((n, LOAD_SOLIDS), np.int64)
+        skp = np.zeros((n, LOAD_SOLIDS), np.int64)
+        self.call("sph_hip_get_loads", 0, n, _ptr(imp), _ptr(cnt), _ptr(skp), None)
+        return Loads(imp, cnt, skp, self._loads_quantum_log2)
 
 
 def default_params(h=0.1, cells=(32, 32, 32)):

@@ -16,7 +16,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import Context, SphHipError, _ptr, load_library
+from .lib import LOAD_QUANTUM_LOG2, Context, SphHipError, _ptr, load_library
 
 HALO = 2
 HEADER_BYTES = 32
@@ -261,6 +261,11 @@ class HipSlab(Context):
         obstacles = list(obstacles)
         super().set_obstacles(obstacles)
         self._settings["obstacles"] = obstacles
+
+    # record_loads / get_loads are lib.Context's: a slab records the responses of the particles it owns
+    # (each particle is owned by one slab), so the rows of all slabs of a run add up to the single
+    # context's (LocalSlabGroup.get_loads; across ranks, an integer all-reduce of Loads.impulse_q,
+    # count and skipped).  A recording does not follow a rebalance: read it before.
 
     def settings(self):
         """What set_timing / set_timing_stride / set_arithmetic / set_obstacles were last given: a
@@ -787,6 +792,19 @@ class LocalSlabGroup:
         if self.exchange_stream is not None:
             self.slabs[0].stream.wait_stream(self.exchange_stream)
         self._deliver()
+
+    def record_loads(self, steps, quantum_log2=LOAD_QUANTUM_LOG2):
+        """HipSlab.record_loads on every slab: row r of each is the group's step r."""
+        for s in self.slabs:
+            s.record_loads(steps, quantum_log2)
+
+    def get_loads(self):
+        """The loads of the whole fluid: the slabs' int64 rows added up (exact, so the same as one
+        context's, whatever the number of slabs)."""
+        total = self.slabs[0].get_loads()
+        for s in self.slabs[1:]:
+            total = total + s.get_loads()
+        return total
 
     def gather(self, n_total):
         """Per-id arrays assembled from every slab's owned particles."""

@@ -225,6 +225,7 @@ class SPH(Context):
         self._push()
 
     setObstacles, getObstacles = Context.set_obstacles, Context.get_obstacles
+    recordLoads, getLoads = Context.record_loads, Context.get_loads
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
