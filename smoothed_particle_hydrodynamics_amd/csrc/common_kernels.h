@@ -9,6 +9,9 @@
 
 #define RED_THREADS 256
 
+// The wall response of the kernels without a hook, the integrate fused into k_full_accel_lists among
+// them: load_walls_respond (load_policy.h) with LoadNoRecorder operation for operation, kept as written
+// because calling that function here changed k_full_accel_lists' code (tools/kernel_isa_diff.py).
 // SPH::applyBoundary (reference src/sph.cpp:1124-1148): reflect at a wall with unit normal
 // along `axis` (sign sgn), continue for the rest of the step scaled by mDamping.  vec3
 // operators of the reference are component-wise fp32 operations.
@@ -50,18 +53,22 @@ __device__ __forceinline__ void handle_boundaries(const PairConsts& k, const flo
 // "KDK as coded": half kick with the SPH acceleration, drift, then a FULL-dt kick with the
 // point-mass gravity only, evaluated at the new position (reference src/sph.cpp:937-1022).
 // Updates x (position, mass kept) and v (velocity, id kept); ke/pe = the particle's energy terms.
-// `after` (ObstacleHook: static obstacles) runs on (old position, new velocity, new position) after
-// the wall handling, before the energy terms; the default does nothing.  A hook that `records`
-// (LoadHook: sph_hip_record_loads) also sees every wall response, and is given the particle's mass.
+// A hook is what a context adds to the step of one particle of mass m, two calls:
+//   walls(k, pos, nv, dt, np, m)   the wall handling (only where k.apply_walls),
+//   after(pos, nv, np, m)          on (old position, new velocity, new position) after the walls and
+//                                  before the energy terms.
+// Hook::active: after() does something.  Hook::records: every lane of the wave must make both calls,
+// the lanes without a particle too (integrate_block).
 struct NoHook {
    static constexpr bool active = false;
    static constexpr bool records = false;
-   __device__ void operator()(const float*, float*, float*) const {}
+   __device__ void walls(const PairConsts& k, const float* pos, float* nv, float dt, float* np, float) const { handle_boundaries(k, pos, nv, dt, np); }
+   __device__ void after(const float*, float*, float*, float) const {}
 };
 template <bool UNIT_SCALE, class Hook>
 __device__ __forceinline__ void integrate_particle_hooked(const PairConsts& k, float4& x, float4& v,
                                                    const float4 a, double& ke, double& pe,
-                                                   const Hook after)
+                                                   const Hook hook)
 {
    const float dt = k.dt;
    const float pos_dt = dt * k.sim_scale_inv;
@@ -113,19 +120,11 @@ __device__ __forceinline__ void integrate_particle_hooked(const PairConsts& k, f
    float nvy = vhy + (agy * dt);
    float nvz = vhz + (agz * dt);
    float nx = nx0, ny = ny0, nz = nz0;
-   if (k.apply_walls) { // extension: the reference's own (unwired) wall handling
+   if (k.apply_walls || Hook::active) {
       const float pos[3] = {x.x, x.y, x.z};
       float nv[3] = {nvx, nvy, nvz}, np[3] = {nx, ny, nz};
-      if constexpr (Hook::records) after.walls(k, pos, nv, dt, np, x.w);
-      else handle_boundaries(k, pos, nv, dt, np);
-      nvx = nv[0]; nvy = nv[1]; nvz = nv[2];
-      nx = np[0]; ny = np[1]; nz = np[2];
-   }
-   if constexpr (Hook::active) {
-      const float pos[3] = {x.x, x.y, x.z};
-      float nv[3] = {nvx, nvy, nvz}, np[3] = {nx, ny, nz};
-      if constexpr (Hook::records) after(pos, nv, np, x.w);
-      else after(pos, nv, np);
+      if (k.apply_walls) hook.walls(k, pos, nv, dt, np, x.w); // extension: the reference's own (unwired) wall handling
+      hook.after(pos, nv, np, x.w);
       nvx = nv[0]; nvy = nv[1]; nvz = nv[2];
       nx = np[0]; ny = np[1]; nz = np[2];
    }
@@ -150,15 +149,20 @@ struct ObstacleHook {
    const sph_hip_obstacle* list;
    int n;
    float dt, damping;
-   __device__ void operator()(const float* p, float* v, float* q) const
+   __device__ void walls(const PairConsts& k, const float* pos, float* nv, float dt_, float* np, float m) const
    {
-      for (int i = 0; i < n; i++) obstacle_respond(list[i], p, v, q, dt, damping);
+      const float maxv[3] = {k.max_x, k.max_y, k.max_z};
+      load_walls_respond(maxv, k.damping, pos, nv, dt_, np, m, LoadNoRecorder());
+   }
+   __device__ void after(const float* p, float* v, float* q, float) const
+   {
+      obstacles_respond(list, n, p, v, q, dt, damping);
    }
 };
 
 // Load recording (load_policy.h; sph_hip_record_loads): the wall and obstacle responses of
-// load_policy.h with this hook as their recorder.  Every lane of the wave calls record() for every
-// solid in turn (k_integrate_loads keeps the lanes without a particle in step, live = false), so
+// load_policy.h with this hook as their recorder.  Every lane of the wave calls the recorder for every
+// solid in turn (integrate_block keeps the lanes without a particle in step, live = false), so
 // the solid is wave-uniform: one vote, and only where some lane was hit a wave reduction of the three
 // terms and the two counters and one 64-bit atomic add per non-zero sum into the step's row.
 struct LoadHook {
@@ -197,33 +201,88 @@ struct LoadHook {
       const float maxv[3] = {k.max_x, k.max_y, k.max_z};
       load_walls_respond(maxv, k.damping, pos, nv, dt_, np, m, *this);
    }
-   __device__ void operator()(const float* p, float* v, float* q, float m) const
+   __device__ void after(const float* p, float* v, float* q, float m) const
    {
       load_obstacles_respond(list, n, p, v, q, dt, damping, m, *this);
    }
 };
 
 // The call the tuned kernels make, with the signature they always had (a hook parameter with a
-// default changed the code of k_full_accel_lists: tools/kernel_isa_diff.py), and the one with a hook.
+// default changed the code of k_full_accel_lists: tools/kernel_isa_diff.py).
 template <bool UNIT_SCALE>
 __device__ __forceinline__ void integrate_particle(const PairConsts& k, float4& x, float4& v,
                                                    const float4 a, double& ke, double& pe)
 {
    integrate_particle_hooked<UNIT_SCALE>(k, x, v, a, ke, pe, NoHook());
 }
-template <bool UNIT_SCALE, class Hook>
-__device__ __forceinline__ void integrate_particle(const PairConsts& k, float4& x, float4& v,
-                                                   const float4 a, double& ke, double& pe, const Hook& after)
-{
-   integrate_particle_hooked<UNIT_SCALE>(k, x, v, a, ke, pe, after);
-}
 
+// The body of the three integrate kernels: particle p (live: an owned one) stepped with `hook`.
 // KE/PE contributions are reduced per block in double (the reference's serial fp32 running sum
 // is order dependent).
 // HASH: the context holds the whole grid and exchanges with nobody, so the sorted state this
 // kernel leaves is exactly the input of the next cell build: the build's first step (cell id,
 // counting atomics - k_hash_count) is done here, on the position just computed, and the next
 // build starts at its scan.  One launch and one read of the positions less per step.
+// Under a hook that records, the lanes without a particle integrate a particle of zeros, so that the
+// whole wave takes part in the hook's votes and reductions; nothing of it is stored or summed.
+template <bool UNIT_SCALE, bool HASH, class Hook>
+__device__ __forceinline__ void integrate_block(float4* __restrict__ posm, float4* __restrict__ velp,
+                                                const float4* __restrict__ acc, const PairConsts& k,
+                                                double* __restrict__ epart, const CellGrid& g,
+                                                uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                                                uint32_t* __restrict__ cell_count, int p, bool live,
+                                                const Hook& hook)
+{
+   double ke = 0.0, pe = 0.0;
+   uint32_t c = 0xffffffffu;
+   if (live || Hook::records) {
+      float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f), v = x, a = x;
+      if (live) {
+         x = posm[p];
+         v = velp[p];
+         a = acc[p];
+      }
+      integrate_particle_hooked<UNIT_SCALE>(k, x, v, a, ke, pe, hook);
+      if (live) {
+         posm[p] = x;
+         velp[p] = v;
+         if (HASH) {
+            int cx, cy, cz;
+            c = cell_of(g, x.x, x.y, x.z, cx, cy, cz);
+            key[p] = c;
+         }
+      } else {
+         ke = 0.0;
+         pe = 0.0;
+      }
+   }
+   if (HASH) count_cell_runs(c, live, p, cell_count, slot, (uint32_t)g.ncells);
+   // block reduction, fixed order
+   __shared__ double s_ke[RED_THREADS / SPH_WAVE], s_pe[RED_THREADS / SPH_WAVE];
+#pragma unroll
+   for (int d = SPH_WAVE / 2; d > 0; d >>= 1) {
+      ke += __shfl_down(ke, d);
+      pe += __shfl_down(pe, d);
+   }
+   const int lane = threadIdx.x & (SPH_WAVE - 1), w = threadIdx.x / SPH_WAVE;
+   if (lane == 0) {
+      s_ke[w] = ke;
+      s_pe[w] = pe;
+   }
+   __syncthreads();
+   if (threadIdx.x == 0) {
+      double a = 0.0, b = 0.0;
+#pragma unroll
+      for (int q = 0; q < RED_THREADS / SPH_WAVE; q++) {
+         a += s_ke[q];
+         b += s_pe[q];
+      }
+      epart[2 * blockIdx.x + 0] = a;
+      epart[2 * blockIdx.x + 1] = b;
+   }
+}
+
+// Owned particles only: ghosts are integrated by the slab that owns them.
 template <bool UNIT_SCALE, bool HASH>
 __global__ void __launch_bounds__(RED_THREADS)
 k_integrate(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
@@ -231,52 +290,12 @@ k_integrate(float4* __restrict__ posm, float4* __restrict__ velp, const float4* 
             uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
             uint32_t* __restrict__ cell_count)
 {
-   // owned particles only: ghosts are integrated by the slab that owns them
    const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
-   double ke = 0.0, pe = 0.0;
-   const bool live = p < meta[META_OWN_END];
-   uint32_t c = 0xffffffffu;
-   if (live) {
-      float4 x = posm[p];
-      float4 v = velp[p];
-      integrate_particle<UNIT_SCALE>(k, x, v, acc[p], ke, pe);
-      posm[p] = x;
-      velp[p] = v;
-      if (HASH) {
-         int cx, cy, cz;
-         c = cell_of(g, x.x, x.y, x.z, cx, cy, cz);
-         key[p] = c;
-      }
-   }
-   if (HASH) count_cell_runs(c, live, p, cell_count, slot, (uint32_t)g.ncells);
-   // block reduction, fixed order
-   __shared__ double s_ke[RED_THREADS / SPH_WAVE], s_pe[RED_THREADS / SPH_WAVE];
-#pragma unroll
-   for (int d = SPH_WAVE / 2; d > 0; d >>= 1) {
-      ke += __shfl_down(ke, d);
-      pe += __shfl_down(pe, d);
-   }
-   const int lane = threadIdx.x & (SPH_WAVE - 1), w = threadIdx.x / SPH_WAVE;
-   if (lane == 0) {
-      s_ke[w] = ke;
-      s_pe[w] = pe;
-   }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      double a = 0.0, b = 0.0;
-#pragma unroll
-      for (int q = 0; q < RED_THREADS / SPH_WAVE; q++) {
-         a += s_ke[q];
-         b += s_pe[q];
-      }
-      epart[2 * blockIdx.x + 0] = a;
-      epart[2 * blockIdx.x + 1] = b;
-   }
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, p < meta[META_OWN_END], NoHook());
 }
 
 // k_integrate followed by the response to the `n_obst` static obstacles of `obst` (a context with
-// obstacles takes this kernel instead of the fused routes: launch_policy.h, fuse_integrate).  The
-// same body as k_integrate, kept apart so that k_integrate's code stays as tuned.
+// obstacles takes this kernel instead of the fused routes: launch_policy.h, fuse_integrate).
 template <bool UNIT_SCALE, bool HASH>
 __global__ void __launch_bounds__(RED_THREADS)
 k_integrate_obst(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
@@ -284,54 +303,13 @@ k_integrate_obst(float4* __restrict__ posm, float4* __restrict__ velp, const flo
                  uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
                  uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst)
 {
-   const ObstacleHook after = {obst, n_obst, k.dt, k.damping};
-   // owned particles only: ghosts are integrated by the slab that owns them
    const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
-   double ke = 0.0, pe = 0.0;
-   const bool live = p < meta[META_OWN_END];
-   uint32_t c = 0xffffffffu;
-   if (live) {
-      float4 x = posm[p];
-      float4 v = velp[p];
-      integrate_particle<UNIT_SCALE>(k, x, v, acc[p], ke, pe, after);
-      posm[p] = x;
-      velp[p] = v;
-      if (HASH) {
-         int cx, cy, cz;
-         c = cell_of(g, x.x, x.y, x.z, cx, cy, cz);
-         key[p] = c;
-      }
-   }
-   if (HASH) count_cell_runs(c, live, p, cell_count, slot, (uint32_t)g.ncells);
-   // block reduction, fixed order
-   __shared__ double s_ke[RED_THREADS / SPH_WAVE], s_pe[RED_THREADS / SPH_WAVE];
-#pragma unroll
-   for (int d = SPH_WAVE / 2; d > 0; d >>= 1) {
-      ke += __shfl_down(ke, d);
-      pe += __shfl_down(pe, d);
-   }
-   const int lane = threadIdx.x & (SPH_WAVE - 1), w = threadIdx.x / SPH_WAVE;
-   if (lane == 0) {
-      s_ke[w] = ke;
-      s_pe[w] = pe;
-   }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      double a = 0.0, b = 0.0;
-#pragma unroll
-      for (int q = 0; q < RED_THREADS / SPH_WAVE; q++) {
-         a += s_ke[q];
-         b += s_pe[q];
-      }
-      epart[2 * blockIdx.x + 0] = a;
-      epart[2 * blockIdx.x + 1] = b;
-   }
+   const ObstacleHook hook = {obst, n_obst, k.dt, k.damping};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, p < meta[META_OWN_END], hook);
 }
 
 // k_integrate_obst (n_obst may be 0: k_integrate) that also adds every wall and obstacle response to
-// `row`, this step's row of the context's load recording (LoadHook above).  Lanes past the last owned
-// particle integrate a particle of zeros, so that the whole wave takes part in the votes and
-// reductions; nothing of it is stored, recorded or summed.
+// `row`, this step's row of the context's load recording (LoadHook above).
 template <bool UNIT_SCALE, bool HASH>
 __global__ void __launch_bounds__(RED_THREADS)
 k_integrate_loads(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
@@ -340,52 +318,10 @@ k_integrate_loads(float4* __restrict__ posm, float4* __restrict__ velp, const fl
                   uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
                   unsigned long long* __restrict__ row, int quantum_log2)
 {
-   // owned particles only: ghosts are integrated by the slab that owns them
    const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
-   double ke = 0.0, pe = 0.0;
    const bool live = p < meta[META_OWN_END];
-   const LoadHook after = {obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live};
-   uint32_t c = 0xffffffffu;
-   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-   float4 x = live ? posm[p] : zero;
-   float4 v = live ? velp[p] : zero;
-   integrate_particle<UNIT_SCALE>(k, x, v, live ? acc[p] : zero, ke, pe, after);
-   if (live) {
-      posm[p] = x;
-      velp[p] = v;
-      if (HASH) {
-         int cx, cy, cz;
-         c = cell_of(g, x.x, x.y, x.z, cx, cy, cz);
-         key[p] = c;
-      }
-   } else {
-      ke = 0.0;
-      pe = 0.0;
-   }
-   if (HASH) count_cell_runs(c, live, p, cell_count, slot, (uint32_t)g.ncells);
-   // block reduction, fixed order
-   __shared__ double s_ke[RED_THREADS / SPH_WAVE], s_pe[RED_THREADS / SPH_WAVE];
-#pragma unroll
-   for (int d = SPH_WAVE / 2; d > 0; d >>= 1) {
-      ke += __shfl_down(ke, d);
-      pe += __shfl_down(pe, d);
-   }
-   const int lane = threadIdx.x & (SPH_WAVE - 1), w = threadIdx.x / SPH_WAVE;
-   if (lane == 0) {
-      s_ke[w] = ke;
-      s_pe[w] = pe;
-   }
-   __syncthreads();
-   if (threadIdx.x == 0) {
-      double a = 0.0, b = 0.0;
-#pragma unroll
-      for (int q = 0; q < RED_THREADS / SPH_WAVE; q++) {
-         a += s_ke[q];
-         b += s_pe[q];
-      }
-      epart[2 * blockIdx.x + 0] = a;
-      epart[2 * blockIdx.x + 1] = b;
-   }
+   const LoadHook hook = {obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
 }
 
 // one block: totals of the per-block partials, written to out[0..1]

@@ -71,9 +71,12 @@ OBST_HD inline bool load_term(float m, const float vb[3], const float va[3], dou
    return true;
 }
 
-// SPH::handleBoundaryConditions / applyBoundary (reference src/sph.cpp:1025-1148) as handle_boundaries
-// and apply_boundary of common_kernels.h compute them, operation for operation, with rec(solid, hit, m,
-// vb, va) called for BOTH walls of every axis, hit or not: a device recorder votes across the wave.
+// SPH::handleBoundaryConditions / applyBoundary (reference src/sph.cpp:1025-1148): x, then y, then z;
+// reflect at a wall with unit normal along the axis, continue for the rest of the step scaled by
+// mDamping (the reference's vec3 operators are component-wise fp32 operations).  rec(solid, hit, m, vb,
+// va) is called for BOTH walls of every axis, hit or not: a device recorder votes across the wave.  With
+// LoadNoRecorder it is the plain wall response, which every hooked integrate uses; handle_boundaries of
+// common_kernels.h computes the same operation for operation for the kernels without a hook.
 template <class Rec>
 OBST_HD inline void load_walls_respond(const float maxv[3], float damping, const float pos[3], float nv[3],
                                        float dt, float np[3], float m, const Rec& rec)
@@ -100,6 +103,8 @@ OBST_HD inline void load_walls_respond(const float maxv[3], float damping, const
       rec(2 * axis + 1, hi, m, vb, nv);
    }
 }
+
+struct LoadNoRecorder { OBST_HD void operator()(int, bool, float, const float*, const float*) const {} };
 
 // obstacles_respond (obstacle_policy.h) with rec called at every obstacle's turn.
 template <class Rec>

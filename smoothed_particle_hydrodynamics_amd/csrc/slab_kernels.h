@@ -34,6 +34,21 @@ __device__ __forceinline__ int msg_reserve(int32_t* __restrict__ counter, bool w
    return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
 }
 
+// The record {x, v} into `msg` for every lane that wants one; a record past the capacity sets error
+// bit 2 instead.  All lanes of the wave must call it (msg_reserve).
+__device__ __forceinline__ void msg_append(SlabMsg* __restrict__ msg, bool want, const float4 x, const float4 v,
+                                           int capacity, int32_t* __restrict__ meta)
+{
+   const int s = msg_reserve(&msg->header[0], want);
+   if (!want) return;
+   if (s < capacity) {
+      msg->rec[2 * s] = x;
+      msg->rec[2 * s + 1] = v;
+   } else {
+      atomicOr(&meta[META_ERRORS], 2);
+   }
+}
+
 // After integrate: classify every live entry of the sorted state.
 //   ghosts (outside the owned range)         -> dropped (re-sent by their owner every step)
 //   owned, now in plane <  lo + halo          -> copied to the left message
@@ -63,28 +78,8 @@ k_slab_pack(const float4* __restrict__ posm, float4* __restrict__ velp, int32_t*
       to_right = have_right && plane >= hi - halo;
       drop = plane < g.z0 || plane >= g.z0 + g.nz;  // migrated beyond the halo
    }
-   if (have_left) {
-      const int s = msg_reserve(&left->header[0], to_left);
-      if (to_left) {
-         if (s < capacity) {
-            left->rec[2 * s] = x;
-            left->rec[2 * s + 1] = v;
-         } else {
-            atomicOr(&meta[META_ERRORS], 2);
-         }
-      }
-   }
-   if (have_right) {
-      const int s = msg_reserve(&right->header[0], to_right);
-      if (to_right) {
-         if (s < capacity) {
-            right->rec[2 * s] = x;
-            right->rec[2 * s + 1] = v;
-         } else {
-            atomicOr(&meta[META_ERRORS], 2);
-         }
-      }
-   }
+   if (have_left) msg_append(left, to_left, x, v, capacity, meta);
+   if (have_right) msg_append(right, to_right, x, v, capacity, meta);
    if (drop) {
       v.w = __uint_as_float(SPH_DEAD_ID);
       velp[p] = v;
@@ -102,12 +97,15 @@ k_slab_pack(const float4* __restrict__ posm, float4* __restrict__ velp, int32_t*
 // Fixed grid, grid-stride.  The record counters are the headers' count words themselves, zeroed
 // by this step's k_scatter (a "last workgroup publishes the count" scheme needs a device-scope
 // fence per workgroup, which on this multi-L2 chip is an L2 write-back: it cost 60 us).
-template <bool UNIT_SCALE>
-__global__ void __launch_bounds__(256)
-k_slab_pack_early(const float4* __restrict__ posm, const float4* __restrict__ velp,
-                  const float4* __restrict__ acc, int32_t* __restrict__ meta, PairConsts k,
-                  CellGrid g, SlabZone zone, SlabMsg* __restrict__ left,
-                  SlabMsg* __restrict__ right, int capacity)
+// slab_pack_early is the body; `hook` is the one the later integrate will use (common_kernels.h), so
+// that the records carry what it will write for the particle and ghosts agree with their owners bit
+// for bit.
+template <bool UNIT_SCALE, class Hook>
+__device__ __forceinline__ void slab_pack_early(const float4* __restrict__ posm, const float4* __restrict__ velp,
+                                                const float4* __restrict__ acc, int32_t* __restrict__ meta,
+                                                const PairConsts& k, const CellGrid& g, const SlabZone& zone,
+                                                SlabMsg* __restrict__ left, SlabMsg* __restrict__ right,
+                                                int capacity, const Hook& hook)
 {
    const int ob = meta[META_OWN_BEGIN], oe = meta[META_OWN_END];
    const int lo_end = min(meta[META_BND_LO_END], oe);
@@ -124,34 +122,14 @@ k_slab_pack_early(const float4* __restrict__ posm, const float4* __restrict__ ve
          v = velp[p];
          if (__float_as_uint(v.w) != SPH_DEAD_ID) {
             double ke, pe;
-            integrate_particle<UNIT_SCALE>(k, x, v, acc[p], ke, pe);
+            integrate_particle_hooked<UNIT_SCALE>(k, x, v, acc[p], ke, pe, hook);
             const int plane = cell_coord(x.z, g.inv, g.nz_global);
             to_left = zone.have_left && plane < zone.lo + zone.halo;
             to_right = zone.have_right && plane >= zone.hi - zone.halo;
          }
       }
-      if (zone.have_left) {
-         const int s = msg_reserve(&left->header[0], to_left);
-         if (to_left) {
-            if (s < capacity) {
-               left->rec[2 * s] = x;
-               left->rec[2 * s + 1] = v;
-            } else {
-               atomicOr(&meta[META_ERRORS], 2);
-            }
-         }
-      }
-      if (zone.have_right) {
-         const int s = msg_reserve(&right->header[0], to_right);
-         if (to_right) {
-            if (s < capacity) {
-               right->rec[2 * s] = x;
-               right->rec[2 * s + 1] = v;
-            } else {
-               atomicOr(&meta[META_ERRORS], 2);
-            }
-         }
-      }
+      if (zone.have_left) msg_append(left, to_left, x, v, capacity, meta);
+      if (zone.have_right) msg_append(right, to_right, x, v, capacity, meta);
    }
    if (blockIdx.x == 0 && threadIdx.x == 0) {
       if (left) left->header[1] = capacity;
@@ -159,9 +137,17 @@ k_slab_pack_early(const float4* __restrict__ posm, const float4* __restrict__ ve
    }
 }
 
-// The same with static obstacles (its own copy of the body, so that k_slab_pack_early's code stays as
-// tuned): the records carry what k_integrate_obst will write for the particle, so that ghosts agree
-// with their owners bit for bit.
+template <bool UNIT_SCALE>
+__global__ void __launch_bounds__(256)
+k_slab_pack_early(const float4* __restrict__ posm, const float4* __restrict__ velp,
+                  const float4* __restrict__ acc, int32_t* __restrict__ meta, PairConsts k,
+                  CellGrid g, SlabZone zone, SlabMsg* __restrict__ left,
+                  SlabMsg* __restrict__ right, int capacity)
+{
+   slab_pack_early<UNIT_SCALE>(posm, velp, acc, meta, k, g, zone, left, right, capacity, NoHook());
+}
+
+// The same with static obstacles (the step's integrate is then k_integrate_obst).
 template <bool UNIT_SCALE>
 __global__ void __launch_bounds__(256)
 k_slab_pack_early_obst(const float4* __restrict__ posm, const float4* __restrict__ velp,
@@ -170,55 +156,8 @@ k_slab_pack_early_obst(const float4* __restrict__ posm, const float4* __restrict
                        SlabMsg* __restrict__ right, int capacity,
                        const sph_hip_obstacle* __restrict__ obst, int n_obst)
 {
-   const ObstacleHook after = {obst, n_obst, k.dt, k.damping};
-   const int ob = meta[META_OWN_BEGIN], oe = meta[META_OWN_END];
-   const int lo_end = min(meta[META_BND_LO_END], oe);
-   const int hi_begin = min(max(meta[META_BND_HI_BEGIN], lo_end), oe);
-   const int n_left = lo_end - ob, n_right = oe - hi_begin;
-   // (whole waves stay in the loop together: msg_reserve is a wave-wide operation)
-   for (int q0 = blockIdx.x * blockDim.x; q0 < n_left + n_right; q0 += gridDim.x * blockDim.x) {
-      const int q = q0 + threadIdx.x;
-      bool to_left = false, to_right = false;
-      float4 x = make_float4(0.f, 0.f, 0.f, 0.f), v = x;
-      if (q < n_left + n_right) {
-         const int p = q < n_left ? ob + q : hi_begin + (q - n_left);
-         x = posm[p];
-         v = velp[p];
-         if (__float_as_uint(v.w) != SPH_DEAD_ID) {
-            double ke, pe;
-            integrate_particle<UNIT_SCALE>(k, x, v, acc[p], ke, pe, after);
-            const int plane = cell_coord(x.z, g.inv, g.nz_global);
-            to_left = zone.have_left && plane < zone.lo + zone.halo;
-            to_right = zone.have_right && plane >= zone.hi - zone.halo;
-         }
-      }
-      if (zone.have_left) {
-         const int s = msg_reserve(&left->header[0], to_left);
-         if (to_left) {
-            if (s < capacity) {
-               left->rec[2 * s] = x;
-               left->rec[2 * s + 1] = v;
-            } else {
-               atomicOr(&meta[META_ERRORS], 2);
-            }
-         }
-      }
-      if (zone.have_right) {
-         const int s = msg_reserve(&right->header[0], to_right);
-         if (to_right) {
-            if (s < capacity) {
-               right->rec[2 * s] = x;
-               right->rec[2 * s + 1] = v;
-            } else {
-               atomicOr(&meta[META_ERRORS], 2);
-            }
-         }
-      }
-   }
-   if (blockIdx.x == 0 && threadIdx.x == 0) {
-      if (left) left->header[1] = capacity;
-      if (right) right->header[1] = capacity;
-   }
+   const ObstacleHook hook = {obst, n_obst, k.dt, k.damping};
+   slab_pack_early<UNIT_SCALE>(posm, velp, acc, meta, k, g, zone, left, right, capacity, hook);
 }
 
 // Cell build of a slab whose last step was integrated and hashed by its acceleration pass
