@@ -445,7 +445,7 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
  * moves it to the nearest surface point and reflects an inward velocity component only.  The
  * operation-by-operation contract is in csrc/obstacle_policy.h.  The KE term of sph_hip_get_energy
  * uses the final velocity.  Obstacles carry no density or pressure (the walls do not either); they
- * do not move.
+ * stand still unless sph_hip_set_obstacle_motion gives them a velocity (moving obstacles, below).
  *   sphere    center, radius.
  *   box       lo, hi.
  *   cylinder  axis (0 x, 1 y, 2 z), center (its axis component is ignored), radius, and its caps at
@@ -472,6 +472,45 @@ typedef struct sph_hip_obstacle {   /* field order is ABI: 48 bytes */
 } sph_hip_obstacle;
 int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, int n);
 int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity);
+
+/* ---- moving obstacles ---------------------------------------------------------------------- *
+ *
+ * Pistons, gates and paddles: obstacle i of the list translates at motion i's constant velocity
+ * while the context's motion clock tau is between `start` and `stop`, and rests before and after.
+ * The fluid does not act back on it.  The operation-by-operation contract is in
+ * csrc/obstacle_policy.h: the obstacle at tau is the list entry shifted by
+ * velocity * (clamp(tau, start, stop) - start), and a particle that ends its step inside the obstacle
+ * as it stands at the end of the step gets the static response in the frame that moves with the solid
+ * during the step - a piston moving at u into fluid at rest leaves it at 2u along its normal.  An
+ * entry whose velocity is zero is used exactly as without motions.  The loads (below) record a moving
+ * obstacle's turn with the world velocities before and after it.
+ *   motion clock  one fp32 value per context, kept on the host.  A successful
+ *                 sph_hip_set_obstacle_motion sets it to 0.  Every integrate enqueued while some entry
+ *                 moves - sph_hip_step, sph_hip_run, sph_hip_integrate, sph_hip_slab_step_end,
+ *                 sph_hip_slab_comm_run - takes tau0 = tau and tau1 = tau + time_step (fp32 add, the
+ *                 time step in force) and leaves tau = tau1; both launches of a slab's early-exchange
+ *                 step get the same pair.  The pair reaches the kernels by value: nothing synchronises
+ *                 for it, and steps already queued keep theirs.  Slab contexts given the same motions
+ *                 advance in lock-step and agree.
+ * sph_hip_set_obstacle_motion: n is the current obstacle count, or 0 to clear all motions; ordered on
+ * the context's stream like sph_hip_set_obstacles.  Refused with SPH_HIP_ERR_INVALID, the previous
+ * motions and clock kept, for a velocity that is not finite, a start that is not finite or not >= 0,
+ * stop < start or a NaN stop (stop may be +INFINITY), an n that is neither 0 nor the obstacle count,
+ * a null list with n > 0, and on a slab between sph_hip_slab_step_begin and sph_hip_slab_step_end.
+ * sph_hip_set_obstacles clears all motions and the clock.
+ * sph_hip_get_obstacle_motion copies up to `capacity` motions to `out`, the clock to *clock (either
+ * may be NULL) and returns how many motions are set (0 or the obstacle count).
+ * sph_hip_get_obstacles keeps returning the list as it was set; sph_hip_get_obstacles_now returns it
+ * displaced to the current clock (computed on the host by the function the device uses).
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no struct and no existing
+ * prototype changed. */
+typedef struct sph_hip_obstacle_motion {   /* field order is ABI: 20 bytes */
+   float velocity[3];               /* position units per unit of time_step */
+   float start, stop;               /* on the motion clock; stop may be +INFINITY */
+} sph_hip_obstacle_motion;
+int sph_hip_set_obstacle_motion(sph_hip_context* ctx, const sph_hip_obstacle_motion* list, int n);
+int sph_hip_get_obstacle_motion(sph_hip_context* ctx, sph_hip_obstacle_motion* out, int capacity, float* clock);
+int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity);
 
 /* ---- loads on walls and obstacles --------------------------------------------------------- *
  *

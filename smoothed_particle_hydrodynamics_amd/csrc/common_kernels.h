@@ -207,6 +207,29 @@ struct LoadHook {
    }
 };
 
+// The two hooks above for a list in which some entry moves (obstacle_policy.h: moving obstacles): the
+// motion list is a second device buffer read wave-uniformly, tau0 and tau1 - the motion clock at the
+// start and the end of this step - are kernel arguments, and every lane forms the same shifts from them
+// (9 adds per moving obstacle); no device state is written for it.  Only after() differs.
+struct MovingObstacleHook : ObstacleHook {
+   const sph_hip_obstacle_motion* motion;
+   float tau0, tau1;
+   __device__ void after(const float* p, float* v, float* q, float) const
+   {
+      obstacles_respond_moving(list, motion, n, p, v, q, dt, damping, tau0, tau1);
+   }
+};
+
+struct MovingLoadHook : LoadHook {
+   const sph_hip_obstacle_motion* motion;
+   float tau0, tau1;
+   __device__ void after(const float* p, float* v, float* q, float m) const
+   {
+      load_obstacles_respond_moving(list, motion, n, p, v, q, dt, damping, tau0, tau1, m,
+                                    static_cast<const LoadHook&>(*this));
+   }
+};
+
 // The call the tuned kernels make, with the signature they always had (a hook parameter with a
 // default changed the code of k_full_accel_lists: tools/kernel_isa_diff.py).
 template <bool UNIT_SCALE>
@@ -321,6 +344,36 @@ k_integrate_loads(float4* __restrict__ posm, float4* __restrict__ velp, const fl
    const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
    const bool live = p < meta[META_OWN_END];
    const LoadHook hook = {obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
+}
+
+// k_integrate_obst and k_integrate_loads for a list in which some entry moves (launch_policy.h:
+// use_moving_kernels): `motion` holds one entry per obstacle, tau0 / tau1 the motion clock of this step.
+template <bool UNIT_SCALE, bool HASH>
+__global__ void __launch_bounds__(RED_THREADS)
+k_integrate_obst_moving(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
+                        const int32_t* __restrict__ meta, PairConsts k, double* __restrict__ epart, CellGrid g,
+                        uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                        uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                        const sph_hip_obstacle_motion* __restrict__ motion, float tau0, float tau1)
+{
+   const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   const MovingObstacleHook hook = {{obst, n_obst, k.dt, k.damping}, motion, tau0, tau1};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, p < meta[META_OWN_END], hook);
+}
+
+template <bool UNIT_SCALE, bool HASH>
+__global__ void __launch_bounds__(RED_THREADS)
+k_integrate_loads_moving(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
+                         const int32_t* __restrict__ meta, PairConsts k, double* __restrict__ epart, CellGrid g,
+                         uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                         uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                         unsigned long long* __restrict__ row, int quantum_log2,
+                         const sph_hip_obstacle_motion* __restrict__ motion, float tau0, float tau1)
+{
+   const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   const bool live = p < meta[META_OWN_END];
+   const MovingLoadHook hook = {{obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live}, motion, tau0, tau1};
    integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
 }
 

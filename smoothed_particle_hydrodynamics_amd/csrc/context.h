@@ -303,6 +303,19 @@ struct sph_hip_context {
    int obst_copy_pending = 0;
    int slab_step_open = 0;         // between sph_hip_slab_step_begin and _end (the list must not change)
 
+   // moving obstacles (sph_hip_set_obstacle_motion): one motion per obstacle (n_motion = 0 or n_obst),
+   // n_moving of them with a velocity, staged and copied like the obstacle list; the motion clock, and
+   // the pair a slab's early pack took for its step (the integrate behind it uses the same)
+   sph_hip_obstacle_motion motion_host[SPH_HIP_MAX_OBSTACLES];
+   int n_motion = 0, n_moving = 0;
+   DevBuf<sph_hip_obstacle_motion> motion_dev;
+   PinnedBuf<sph_hip_obstacle_motion> motion_stage;
+   Event ev_motion_copied;
+   int motion_copy_pending = 0;
+   float motion_tau = 0.0f;
+   float step_tau[2] = {0.0f, 0.0f};
+   int step_tau_taken = 0;
+
    // load recording (sph_hip_record_loads): loads_rows rows of LOAD_ROW_WORDS int64, the next integrate
    // enqueued fills row loads_next (load_row below)
    DevBuf<unsigned long long> loads_dev;
@@ -521,6 +534,9 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    CREATE_TRY(dev_alloc(ctx->obst_dev, SPH_HIP_MAX_OBSTACLES));
    CREATE_TRY(pinned_alloc(ctx->obst_stage, SPH_HIP_MAX_OBSTACLES));
    CREATE_TRY(event_create(ctx->ev_obst_copied));
+   CREATE_TRY(dev_alloc(ctx->motion_dev, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(pinned_alloc(ctx->motion_stage, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(event_create(ctx->ev_motion_copied));
    CREATE_TRY(hipStreamSynchronize(ctx->stream));
 #undef CREATE_TRY
    *out = ctx.release();

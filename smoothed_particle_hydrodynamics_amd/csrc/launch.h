@@ -520,20 +520,60 @@ int launch_accel(sph_hip_context* ctx, int part = 0, hipStream_t part_stream = n
    return SPH_HIP_OK;
 }
 
+// `n` entries of `list` into `dev` through the pinned `stage`.  The staging is memory the previous
+// call's copy may still be reading: wait for that copy (not for the steps queued before it), then copy
+// behind everything enqueued so far.
+template <class T>
+int stage_list(sph_hip_context* ctx, const T* list, int n, PinnedBuf<T>& stage, DevBuf<T>& dev, Event& copied,
+               int& pending)
+{
+   if (pending) SPH_TRY(hipEventSynchronize(copied));
+   pending = 0;
+   memcpy(stage.get(), list, sizeof(T) * (size_t)n);
+   SPH_TRY(hipMemcpyAsync(dev, stage.get(), sizeof(T) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+   SPH_TRY(hipEventRecord(copied, ctx->stream));
+   pending = 1;
+   return SPH_HIP_OK;
+}
+
+// The motion clock of the step being enqueued (obstacle_policy.h: moving obstacles): tau at its start
+// and at its end, the clock left at the end.  Host values only: they travel as kernel arguments.
+void motion_tick(sph_hip_context* ctx, float tau[2])
+{
+   tau[0] = ctx->motion_tau;
+   tau[1] = obstacle_clock_next(ctx->motion_tau, ctx->prm.time_step);
+   ctx->motion_tau = tau[1];
+}
+
 // with_hash: the kernel also does the first step of the next cell build (see k_integrate);
 // with static obstacles, k_integrate_obst; while a load recording has rows left, k_integrate_loads
 // into the next row (an integrate without particles uses its row up too: the rows of the slabs of
-// one run stay in step)
+// one run stay in step); while some obstacle moves, their _moving forms with the step's motion clock,
+// which a slab's early pack has already taken (an integrate without particles advances it too)
 int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
 {
    const int n = ctx->n;
    unsigned long long* load_row = nullptr;
    if (loads_pending(ctx)) load_row = ctx->loads_dev.get() + (size_t)ctx->loads_next++ * LOAD_ROW_WORDS;
+   const bool moving = use_moving_kernels(ctx->n_obst, ctx->n_moving);
+   if (moving && !ctx->step_tau_taken) motion_tick(ctx, ctx->step_tau);
+   ctx->step_tau_taken = 0;
+   const float tau0 = ctx->step_tau[0], tau1 = ctx->step_tau[1];
    if (n == 0) return SPH_HIP_OK;
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const int blocks = div_up(n, RED_THREADS);
    bind_flags([&](auto U, auto H) {
-      if (load_row)
+      if (moving && load_row)
+         hipLaunchKernelGGL((k_integrate_loads_moving<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,
+                            load_row, ctx->loads_quantum, ctx->motion_dev, tau0, tau1);
+      else if (moving)
+         hipLaunchKernelGGL((k_integrate_obst_moving<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,
+                            ctx->motion_dev, tau0, tau1);
+      else if (load_row)
          hipLaunchKernelGGL((k_integrate_loads<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
                             ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
                             ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,

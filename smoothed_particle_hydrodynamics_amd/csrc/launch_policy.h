@@ -274,6 +274,12 @@ inline bool fuse_slab_step(bool no_fused_slab, int n_obstacles, bool record_load
    return !no_fused_slab && n_obstacles == 0 && !record_loads;
 }
 
+// Whether a step's integrate, and a slab's early pack, take the kernels for moving obstacles
+// (k_integrate_obst_moving, k_integrate_loads_moving, k_slab_pack_early_obst_moving) and the motion clock
+// advances: some entry of the motion list moves.  A context in which nothing moves launches what it
+// always launched.  (n_obstacles > 0 then also keeps the step off the fused routes above.)
+inline bool use_moving_kernels(int n_obstacles, int n_moving) { return n_obstacles > 0 && n_moving > 0; }
+
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
 // slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary

@@ -119,6 +119,21 @@ OBST_HD inline void load_obstacles_respond(const sph_hip_obstacle* list, int n, 
    }
 }
 
+// obstacles_respond_moving (obstacle_policy.h) with rec called at every obstacle's turn: a moving entry's
+// turn is recorded when q is inside the obstacle as it stands at the end of the step, vb and va being
+// the world velocities before and after that turn.
+template <class Rec>
+OBST_HD inline void load_obstacles_respond_moving(const sph_hip_obstacle* list, const sph_hip_obstacle_motion* motion,
+                                                  int n, const float p[3], float v[3], float q[3], float dt,
+                                                  float damping, float tau0, float tau1, float m, const Rec& rec)
+{
+   for (int i = 0; i < n; i++) {
+      const float vb[3] = {v[0], v[1], v[2]};
+      const bool in = obstacle_turn(list[i], motion[i], p, v, q, dt, damping, tau0, tau1);
+      rec(6 + i, in, m, vb, v);
+   }
+}
+
 // A recorder that adds term by term into one row (LOAD_ROW_WORDS int64): what the device's wave
 // reductions and atomic adds sum to.
 struct LoadRowAdder {

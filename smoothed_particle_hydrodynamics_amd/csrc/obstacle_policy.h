@@ -49,6 +49,24 @@
 //              component: only an inward component is reflected, without damping.
 // The result is not strictly inside the obstacle except by the rounding of the last formula applied
 // (the sphere's and the side's q are rounded once per component from an exact surface point).
+//
+// Moving obstacles (include/sph_hip.h: sph_hip_set_obstacle_motion; k_integrate_obst_moving,
+// k_integrate_loads_moving, k_slab_pack_early_obst_moving; tests/test_moving_obstacles_cpu.py against
+// tests/moving_obstacle_emulation.py).  Entry i of the motion list belongs to obstacle i; tau is the
+// context's motion clock, tau0 at the start of the step and tau1 = tau0 + dt at its end (fp32 add).
+//   moves      any velocity[c] != 0.  An entry that does not move is used untouched and responds as
+//              above (no "+ 0": a -0 field keeps its sign).
+//   shift      s(tau) = (tau < start ? start : tau > stop ? stop : tau) - start;
+//              D_c(tau) = velocity[c] * s(tau); the obstacle at tau is the list entry with D_c added to
+//              center[c], lo[c] and hi[c] on all three axes, the unused fields included.
+//   response   D0 = D(tau0), D1 = D(tau1), o1 = the obstacle at tau1.  q not strictly inside o1: the
+//              particle is untouched, bit for bit.  d_c = D1_c - D0_c.  All three d_c == 0 (not started,
+//              stopped, dt == 0): the response above with o1; nothing is divided.  Otherwise
+//              ue_c = d_c / dt, pr_c = p_c + d_c, w_c = v_c - ue_c; the response above with
+//              (o1, pr, w, q); then v_c = w_c + ue_c.  This is the static response in the frame that
+//              moves with the solid and coincides with the world at the end of the step: a solid moving
+//              at u into a particle at rest leaves it at 2u along the normal.
+// Obstacles act in list order, moving or not, each on the v, q the one before it left.
 #pragma once
 
 #include <math.h>
@@ -273,4 +291,116 @@ OBST_HD inline void obstacles_respond(const sph_hip_obstacle* list, int n, const
                                       float dt, float damping)
 {
    for (int i = 0; i < n; i++) obstacle_respond(list[i], p, v, q, dt, damping);
+}
+
+// ---- moving obstacles (the contract's second part) ------------------------------------------------
+
+// Why a motion list for `n_obstacles` obstacles is refused, or nullptr.  n = 0 clears all motions.
+inline const char* obstacle_motion_check(const sph_hip_obstacle_motion* list, int n, int n_obstacles)
+{
+   if (n != 0 && n != n_obstacles) return "the motion count must be 0 or the obstacle count";
+   if (n > 0 && !list) return "null motion list";
+   for (int i = 0; i < n; i++) {
+      const sph_hip_obstacle_motion& m = list[i];
+      if (!isfinite(m.velocity[0]) || !isfinite(m.velocity[1]) || !isfinite(m.velocity[2]))
+         return "a motion's velocity must be finite";
+      if (!isfinite(m.start) || !(m.start >= 0.0f)) return "a motion's start must be finite and >= 0";
+      if (!(m.stop >= m.start)) return "a motion needs stop >= start";
+   }
+   return nullptr;
+}
+
+OBST_HD inline bool obstacle_moves(const sph_hip_obstacle_motion& m)
+{
+   return m.velocity[0] != 0.0f || m.velocity[1] != 0.0f || m.velocity[2] != 0.0f;
+}
+
+// how many entries of a motion list move
+inline int obstacles_moving(const sph_hip_obstacle_motion* list, int n)
+{
+   int k = 0;
+   for (int i = 0; i < n; i++) k += obstacle_moves(list[i]) ? 1 : 0;
+   return k;
+}
+
+// the motion clock after a step of dt
+inline float obstacle_clock_next(float tau, float dt) { return tau + dt; }
+
+OBST_HD inline float obstacle_motion_s(const sph_hip_obstacle_motion& m, float tau)
+{
+   return (tau < m.start ? m.start : tau > m.stop ? m.stop : tau) - m.start;
+}
+
+OBST_HD inline void obstacle_displacement(const sph_hip_obstacle_motion& m, float tau, float D[3])
+{
+   const float s = obstacle_motion_s(m, tau);
+   for (int c = 0; c < 3; c++) D[c] = m.velocity[c] * s;
+}
+
+OBST_HD inline sph_hip_obstacle obstacle_shifted(const sph_hip_obstacle& o, const float D[3])
+{
+   sph_hip_obstacle s = o;
+   for (int c = 0; c < 3; c++) {
+      s.center[c] = o.center[c] + D[c];
+      s.lo[c] = o.lo[c] + D[c];
+      s.hi[c] = o.hi[c] + D[c];
+   }
+   return s;
+}
+
+// the obstacle at tau: shifted when its motion moves it, untouched otherwise (m may be null)
+OBST_HD inline sph_hip_obstacle obstacle_at(const sph_hip_obstacle& o, const sph_hip_obstacle_motion* m, float tau)
+{
+   if (!m || !obstacle_moves(*m)) return o;
+   float D[3];
+   obstacle_displacement(*m, tau, D);
+   return obstacle_shifted(o, D);
+}
+
+// The response of one moving obstacle whose shifts at the start and the end of the step are D0 and D1,
+// o1 being the obstacle at the end (one obstacle_respond call site for both branches of the contract).
+OBST_HD inline void obstacle_respond_moved(const sph_hip_obstacle& o1, const float D0[3], const float D1[3],
+                                           const float p[3], float v[3], float q[3], float dt, float damping)
+{
+   if (!obstacle_inside(o1, q)) return;
+   const float d[3] = {D1[0] - D0[0], D1[1] - D0[1], D1[2] - D0[2]};
+   const bool boost = d[0] != 0.0f || d[1] != 0.0f || d[2] != 0.0f;
+   float ue[3] = {0.0f, 0.0f, 0.0f}, pr[3] = {p[0], p[1], p[2]}, w[3] = {v[0], v[1], v[2]};
+   if (boost) {
+      for (int c = 0; c < 3; c++) {
+         ue[c] = d[c] / dt;
+         pr[c] = p[c] + d[c];
+         w[c] = v[c] - ue[c];
+      }
+   }
+   obstacle_respond(o1, pr, w, q, dt, damping);
+   for (int c = 0; c < 3; c++) v[c] = boost ? w[c] + ue[c] : w[c];
+}
+
+// One entry's turn in a list with motions: obstacle_respond for one that does not move,
+// obstacle_respond_moved for one that does.  Returns whether q was strictly inside the obstacle as it
+// stands at the end of the step (what the load recorder calls a response).
+OBST_HD inline bool obstacle_turn(const sph_hip_obstacle& o, const sph_hip_obstacle_motion& m, const float p[3],
+                                  float v[3], float q[3], float dt, float damping, float tau0, float tau1)
+{
+   if (!obstacle_moves(m)) {
+      const bool in = obstacle_inside(o, q);
+      obstacle_respond(o, p, v, q, dt, damping);
+      return in;
+   }
+   float D0[3], D1[3];
+   obstacle_displacement(m, tau0, D0);
+   obstacle_displacement(m, tau1, D1);
+   const sph_hip_obstacle o1 = obstacle_shifted(o, D1);
+   const bool in = obstacle_inside(o1, q);
+   obstacle_respond_moved(o1, D0, D1, p, v, q, dt, damping);
+   return in;
+}
+
+// Every obstacle of a list with motions, in order.
+OBST_HD inline void obstacles_respond_moving(const sph_hip_obstacle* list, const sph_hip_obstacle_motion* motion,
+                                             int n, const float p[3], float v[3], float q[3], float dt,
+                                             float damping, float tau0, float tau1)
+{
+   for (int i = 0; i < n; i++) obstacle_turn(list[i], motion[i], p, v, q, dt, damping, tau0, tau1);
 }

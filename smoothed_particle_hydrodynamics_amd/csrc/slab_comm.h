@@ -102,8 +102,20 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
    if (!ctx->slab_fused) {
       const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
       const SlabZone zone = slab_zone(ctx);
+      // the pack integrates with the motion clock of this step; the integrate of sph_hip_slab_step_end
+      // uses the same pair (launch_integrate)
+      const bool moving = use_moving_kernels(ctx->n_obst, ctx->n_moving);
+      if (moving) {
+         motion_tick(ctx, ctx->step_tau);
+         ctx->step_tau_taken = 1;
+      }
       bind_flags([&](auto U) {
-         if (ctx->n_obst > 0)
+         if (moving)
+            hipLaunchKernelGGL(k_slab_pack_early_obst_moving<U.value>, dim3(SLAB_PACK_BLOCKS), dim3(256), 0, side,
+                               ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->grid,
+                               zone, (SlabMsg*)left_device, (SlabMsg*)right_device, capacity_records,
+                               ctx->obst_dev, ctx->n_obst, ctx->motion_dev, ctx->step_tau[0], ctx->step_tau[1]);
+         else if (ctx->n_obst > 0)
             hipLaunchKernelGGL(k_slab_pack_early_obst<U.value>, dim3(SLAB_PACK_BLOCKS), dim3(256), 0, side,
                                ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->grid,
                                zone, (SlabMsg*)left_device, (SlabMsg*)right_device, capacity_records,

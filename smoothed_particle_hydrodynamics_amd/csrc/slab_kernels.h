@@ -160,6 +160,21 @@ k_slab_pack_early_obst(const float4* __restrict__ posm, const float4* __restrict
    slab_pack_early<UNIT_SCALE>(posm, velp, acc, meta, k, g, zone, left, right, capacity, hook);
 }
 
+// ... and with a list in which some entry moves (the step's integrate is then k_integrate_obst_moving
+// or k_integrate_loads_moving, with the same tau0 and tau1).
+template <bool UNIT_SCALE>
+__global__ void __launch_bounds__(256)
+k_slab_pack_early_obst_moving(const float4* __restrict__ posm, const float4* __restrict__ velp,
+                              const float4* __restrict__ acc, int32_t* __restrict__ meta, PairConsts k,
+                              CellGrid g, SlabZone zone, SlabMsg* __restrict__ left,
+                              SlabMsg* __restrict__ right, int capacity,
+                              const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                              const sph_hip_obstacle_motion* __restrict__ motion, float tau0, float tau1)
+{
+   const MovingObstacleHook hook = {{obst, n_obst, k.dt, k.damping}, motion, tau0, tau1};
+   slab_pack_early<UNIT_SCALE>(posm, velp, acc, meta, k, g, zone, left, right, capacity, hook);
+}
+
 // Cell build of a slab whose last step was integrated and hashed by its acceleration pass
 // (FusedStep): key, slot and the cells' counts of the owned entries of the previous sorted order
 // [OWN_BEGIN, OWN_END) are already there.  What is left: that order's other entries - last step's

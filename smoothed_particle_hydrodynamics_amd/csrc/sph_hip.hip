@@ -814,18 +814,13 @@ int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, in
       return SPH_HIP_ERR_INVALID;
    }
    if (n > 0) {
-      // the staging is pinned host memory the previous call's copy may still be reading: wait for
-      // that copy (not for the steps queued before it), then copy behind everything enqueued so far
-      if (ctx->obst_copy_pending) SPH_TRY(hipEventSynchronize(ctx->ev_obst_copied));
-      ctx->obst_copy_pending = 0;
-      memcpy(ctx->obst_stage.get(), list, sizeof(sph_hip_obstacle) * (size_t)n);
-      SPH_TRY(hipMemcpyAsync(ctx->obst_dev, ctx->obst_stage.get(), sizeof(sph_hip_obstacle) * (size_t)n,
-                             hipMemcpyHostToDevice, ctx->stream));
-      SPH_TRY(hipEventRecord(ctx->ev_obst_copied, ctx->stream));
-      ctx->obst_copy_pending = 1;
+      if ((rc = stage_list(ctx, list, n, ctx->obst_stage, ctx->obst_dev, ctx->ev_obst_copied, ctx->obst_copy_pending)))
+         return rc;
       memcpy(ctx->obst_host, list, sizeof(sph_hip_obstacle) * (size_t)n);
    }
    ctx->n_obst = n;   // the steps enqueued from here on take the routes of this count
+   ctx->n_motion = ctx->n_moving = 0;   // a new list stands still
+   ctx->motion_tau = 0.0f;
    return SPH_HIP_OK;
 }
 
@@ -838,6 +833,58 @@ int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capac
    }
    const int k = capacity < ctx->n_obst ? capacity : ctx->n_obst;
    if (k > 0) memcpy(out, ctx->obst_host, sizeof(sph_hip_obstacle) * (size_t)k);
+   return ctx->n_obst;
+}
+
+// ---- moving obstacles (obstacle_policy.h; routes: launch_policy.h use_moving_kernels) --------------
+
+int sph_hip_set_obstacle_motion(sph_hip_context* ctx, const sph_hip_obstacle_motion* list, int n)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = obstacle_motion_check(list, n, ctx->n_obst)) {
+      ctx->err = std::string("sph_hip_set_obstacle_motion: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (ctx->slab_step_open) {
+      ctx->err = "sph_hip_set_obstacle_motion: not between sph_hip_slab_step_begin and sph_hip_slab_step_end";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (n > 0) {
+      if ((rc = stage_list(ctx, list, n, ctx->motion_stage, ctx->motion_dev, ctx->ev_motion_copied,
+                           ctx->motion_copy_pending)))
+         return rc;
+      memcpy(ctx->motion_host, list, sizeof(sph_hip_obstacle_motion) * (size_t)n);
+   }
+   ctx->n_motion = n;   // the steps enqueued from here on take the routes of these motions
+   ctx->n_moving = obstacles_moving(ctx->motion_host, n);
+   ctx->motion_tau = 0.0f;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_obstacle_motion(sph_hip_context* ctx, sph_hip_obstacle_motion* out, int capacity, float* clock)
+{
+   if (!ctx) return SPH_HIP_ERR_INVALID;
+   if (capacity < 0 || (capacity > 0 && !out)) {
+      ctx->err = "sph_hip_get_obstacle_motion: capacity must be >= 0, out non-null when it is > 0";
+      return SPH_HIP_ERR_INVALID;
+   }
+   const int k = capacity < ctx->n_motion ? capacity : ctx->n_motion;
+   if (k > 0) memcpy(out, ctx->motion_host, sizeof(sph_hip_obstacle_motion) * (size_t)k);
+   if (clock) *clock = ctx->motion_tau;
+   return ctx->n_motion;
+}
+
+int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity)
+{
+   if (!ctx) return SPH_HIP_ERR_INVALID;
+   if (capacity < 0 || (capacity > 0 && !out)) {
+      ctx->err = "sph_hip_get_obstacles_now: capacity must be >= 0, out non-null when it is > 0";
+      return SPH_HIP_ERR_INVALID;
+   }
+   const int k = capacity < ctx->n_obst ? capacity : ctx->n_obst;
+   for (int i = 0; i < k; i++)
+      out[i] = obstacle_at(ctx->obst_host[i], i < ctx->n_motion ? &ctx->motion_host[i] : nullptr, ctx->motion_tau);
    return ctx->n_obst;
 }
 

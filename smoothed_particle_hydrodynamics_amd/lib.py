@@ -73,7 +73,7 @@ class SphRenderParams(C.Structure):
 
 
 from . import obstacles as _obstacles  # noqa: E402
-from .obstacles import SphObstacle  # noqa: E402  (mirror of sph_hip_obstacle)
+from .obstacles import SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of sph_hip_obstacle[_motion])
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -124,6 +124,9 @@ PROTOTYPES = {
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_set_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_get_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
+    "sph_hip_set_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int]),
+    "sph_hip_get_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int, _P(C.c_float)]),
+    "sph_hip_get_obstacles_now": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_record_loads": (C.c_int, [_ctx, C.c_int, C.c_int]),
     "sph_hip_get_loads": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
@@ -337,11 +340,26 @@ class Context:
         arr, n = _obstacles.as_array(obstacles)
         self.call("sph_hip_set_obstacles", arr, n)
 
-    def get_obstacles(self):
-        """The context's obstacles, in list order."""
+    def get_obstacles(self, now=False):
+        """The context's obstacles, in list order: as they were set, or (now=True) displaced by their
+        motions to the current motion clock (sph_hip_get_obstacles_now)."""
         arr = (SphObstacle * _obstacles.MAX_OBSTACLES)()
-        n = self.call("sph_hip_get_obstacles", arr, _obstacles.MAX_OBSTACLES)
+        n = self.call("sph_hip_get_obstacles_now" if now else "sph_hip_get_obstacles", arr, _obstacles.MAX_OBSTACLES)
         return [_obstacles.from_struct(arr[i]) for i in range(n)]
+
+    def set_obstacle_motion(self, motions):
+        """Drive the obstacles (sph_hip_set_obstacle_motion): one obstacles.Motion per obstacle, None
+        for one at rest; an empty list clears all motions.  Sets the motion clock to 0; steps already
+        queued keep the motions and the clock they were enqueued with."""
+        arr, n = _obstacles.as_motion_array(motions)
+        self.call("sph_hip_set_obstacle_motion", arr, n)
+
+    def get_obstacle_motion(self):
+        """([Motion per obstacle] - empty when no motions are set -, the motion clock)."""
+        arr = (SphObstacleMotion * _obstacles.MAX_OBSTACLES)()
+        clock = C.c_float()
+        n = self.call("sph_hip_get_obstacle_motion", arr, _obstacles.MAX_OBSTACLES, C.byref(clock))
+        return [_obstacles.motion_from_struct(arr[i]) for i in range(n)], clock.value
 
     def record_loads(self, steps, quantum_log2=LOAD_QUANTUM_LOG2):
         """Record the impulse the next `steps` steps give to every wall and obstacle

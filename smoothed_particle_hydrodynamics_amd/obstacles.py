@@ -2,10 +2,13 @@
 
 `Sphere`, `Box` and `Cylinder` describe the solids a context's particles collide with; `as_struct()`
 gives the C ABI's sph_hip_obstacle, `signed_distance(points)` the numpy distance to the surface
-(negative inside), for placing obstacles and checking results.  The collision response itself is
-csrc/obstacle_policy.h and runs on the GPU.
+(negative inside), for placing obstacles and checking results.  `Motion` is the constant velocity an
+obstacle is driven at between two readings of the context's motion clock
+(sph_hip_set_obstacle_motion).  The collision response itself is csrc/obstacle_policy.h and runs on
+the GPU.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -133,6 +136,58 @@ def as_array(obstacles):
     for i, o in enumerate(obstacles):
         arr[i] = o if isinstance(o, SphObstacle) else o.as_struct()
     return arr, len(obstacles)
+
+
+class SphObstacleMotion(C.Structure):
+    """Mirror of sph_hip_obstacle_motion (include/sph_hip.h): 20 bytes, field order is ABI."""
+
+    _fields_ = [("velocity", C.c_float * 3), ("start", C.c_float), ("stop", C.c_float)]
+
+
+class Motion:
+    """An obstacle translating at `velocity` (position units per unit of time_step) while the motion
+    clock is in [start, stop], at rest before and after; stop may be math.inf."""
+
+    def __init__(self, velocity, start=0.0, stop=math.inf):
+        self.velocity = _vec3(velocity)
+        self.start, self.stop = np.float32(start), np.float32(stop)
+
+    def as_struct(self):
+        s = SphObstacleMotion()
+        s.velocity[:] = [float(v) for v in self.velocity]
+        s.start, s.stop = float(self.start), float(self.stop)
+        return s
+
+    def moves(self):
+        return bool((self.velocity != 0).any())
+
+    def displacement(self, clock):
+        """The shift at motion clock `clock`, float32[3], in the C ABI's fp32 arithmetic."""
+        tau = np.float32(clock)
+        s = (self.start if tau < self.start else self.stop if tau > self.stop else tau) - self.start
+        with np.errstate(over="ignore"):
+            return (self.velocity * np.float32(s)).astype(np.float32)
+
+    def __eq__(self, other):
+        return isinstance(other, Motion) and bytes(self.as_struct()) == bytes(other.as_struct())
+
+    def __repr__(self):
+        return "Motion(%s, %g, %g)" % (list(self.velocity), self.start, self.stop)
+
+
+def motion_from_struct(s):
+    return Motion(list(s.velocity), s.start, s.stop)
+
+
+def as_motion_array(motions):
+    """A ctypes array of sph_hip_obstacle_motion for a list of Motion, struct or None (at rest)."""
+    motions = list(motions)
+    arr = (SphObstacleMotion * max(1, len(motions)))()
+    for i, m in enumerate(motions):
+        if m is None:
+            m = Motion((0.0, 0.0, 0.0))
+        arr[i] = m if isinstance(m, SphObstacleMotion) else m.as_struct()
+    return arr, len(motions)
 
 
 def inside_any(points, obstacles):

@@ -182,3 +182,26 @@ def dam_break_pillar(n, pillar=(0.35, 0.5), radius=0.08, surge=0.7, box=(1.0, 1.
     obstacles = [Cylinder(1, (pillar[0], 0.0, pillar[1]), radius, -1.0, 2.0 * float(p.max_y) + 1.0)]
     pos, vel, mass = carve(pos, vel, mass, obstacles)
     return p, pos, vel, mass, obstacles
+
+
+def dam_break_gate(n, lift_speed, thickness=2.0, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0),
+                   neighbors=32.0, seed=42, gravity=-9.81):
+    """The dam column of dam_break_pillar (gravity along -y, the walls on, the surge along +x) held behind
+    a gate: a Box `thickness` kernel radii thick whose upstream face stands one kernel radius from the
+    column's face, from below the floor to above the column and across the whole box along z.  Its
+    Motion lifts it along +y at `lift_speed` (position units per unit of time_step) until its lower edge
+    is one kernel radius above the column, and stops.  Particles that would start inside the gate are
+    dropped (carve).  Returns (params, pos, vel, mass, [Box], [Motion]): setObstacles, then
+    setObstacleMotion."""
+    from .obstacles import Box, Motion
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    vel.reshape(-1, 3)[:, 0] = np.float32(surge)
+    h = float(p.h)
+    x0, top = box[0] * fill[0] + h, box[1] * fill[1]
+    gate = Box((x0, -h, -h), (x0 + thickness * h, top + h, float(p.max_z) + h))
+    pos, vel, mass = carve(pos, vel, mass, [gate])
+    travel = top + 2.0 * h
+    return p, pos, vel, mass, [gate], [Motion((0.0, lift_speed, 0.0), 0.0, travel / lift_speed)]

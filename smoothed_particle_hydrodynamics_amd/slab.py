@@ -261,6 +261,13 @@ class HipSlab(Context):
         obstacles = list(obstacles)
         super().set_obstacles(obstacles)
         self._settings["obstacles"] = obstacles
+        self._settings.pop("obstacle_motion", None)   # a new list stands still
+
+    def set_obstacle_motion(self, motions):
+        """Moving obstacles (sph_hip_set_obstacle_motion): the same motions, set before the same step,
+        on every slab of a run - their motion clocks then advance in lock-step."""
+        super().set_obstacle_motion(motions)
+        self._settings["obstacle_motion"] = self.get_obstacle_motion()[0]   # a Motion per obstacle, or []
 
     # record_loads / get_loads are lib.Context's: a slab records the responses of the particles it owns
     # (each particle is owned by one slab), so the rows of all slabs of a run add up to the single
@@ -281,6 +288,8 @@ class HipSlab(Context):
             self.set_timing_stride(settings["timing_stride"])
         if "obstacles" in settings:
             self.set_obstacles(settings["obstacles"])
+        if "obstacle_motion" in settings:
+            self.set_obstacle_motion(settings["obstacle_motion"])   # (nothing moves: see rebalance)
 
     def poll_send_counts(self):
         """Records in the two messages, without draining the stream: returns what the copy
@@ -654,6 +663,12 @@ class DistSlabStepper:
         rank, world, group = tr.rank, tr.world, self._group()
         if world == 1 or self.make_slab is None or self.cuts is None:
             return False
+        # the motion clock lives in the context and a new slab starts at 0: while an obstacle moves the
+        # cuts stay (every rank holds the same motions, so all of them decide alike)
+        if any(m.moves() for m in slab.settings().get("obstacle_motion", ())):
+            if force:
+                raise SphHipError("rebalance: the motion clock of moving obstacles cannot be carried to new slabs")
+            return False
         cdev = self._device()
         owned = torch.tensor([slab.status()["owned"]], dtype=torch.int64, device=cdev)
         every = [torch.zeros_like(owned) for _ in range(world)]
@@ -792,6 +807,15 @@ class LocalSlabGroup:
         if self.exchange_stream is not None:
             self.slabs[0].stream.wait_stream(self.exchange_stream)
         self._deliver()
+
+    def set_obstacles(self, obstacles):
+        for s in self.slabs:
+            s.set_obstacles(obstacles)
+
+    def set_obstacle_motion(self, motions):
+        """HipSlab.set_obstacle_motion on every slab, between two steps of the group."""
+        for s in self.slabs:
+            s.set_obstacle_motion(motions)
 
     def record_loads(self, steps, quantum_log2=LOAD_QUANTUM_LOG2):
         """HipSlab.record_loads on every slab: row r of each is the group's step r."""

@@ -225,6 +225,7 @@ class SPH(Context):
         self._push()
 
     setObstacles, getObstacles = Context.set_obstacles, Context.get_obstacles
+    setObstacleMotion, getObstacleMotion = Context.set_obstacle_motion, Context.get_obstacle_motion
     recordLoads, getLoads = Context.record_loads, Context.get_loads
 
     # ---- slots ---------------------------------------------------------------------------------
