@@ -553,6 +553,66 @@ int sph_hip_record_loads(sph_hip_context* ctx, int rows, int quantum_log2);
 int sph_hip_get_loads(sph_hip_context* ctx, int first_row, int n_rows, int64_t* impulse, int64_t* count,
                       int64_t* skipped, int32_t* rows_recorded);
 
+/* ---- free bodies ---------------------------------------------------------------------------- *
+ *
+ * Obstacles that the fluid's own loads set in motion: debris, a float, a gate the water opens.  Body
+ * i of the list belongs to obstacle i; an entry with mass == 0 is not a body and behaves exactly as
+ * without this call, at rest or under its motion.  A body translates (no rotation, no contact between
+ * bodies); its state lives on the device and is advanced by one single-wave launch per step, so queued
+ * steps stay queued.  The operation-by-operation contract is in csrc/body_policy.h:
+ *   state      per obstacle: the displacement D at the end of the last enqueued step, Dprev at its
+ *              start, the velocity V, and two int64 counters, skipped and steps.  All zero when bodies
+ *              are set, except V = velocity on the free components.
+ *   advance    once per step, before that step's integrate, from the load row the previous integrate
+ *              filled (column 6 + i; the first step after sph_hip_set_bodies has no such row and takes a
+ *              zero impulse).  Dprev = D; per free component c, in fp32, unfused:
+ *              J = (float)((double)impulse_q[6 + i][c] * 2^quantum_log2); V_c = V_c + J / mass;
+ *              V_c = V_c + accel_c * time_step; D_c = D_c + V_c * time_step; D_c < travel_lo[c]:
+ *              D_c = travel_lo[c], V_c = 0; D_c > travel_hi[c]: D_c = travel_hi[c], V_c = 0.  A
+ *              component that is not free keeps V_c = 0 and D_c = 0.  skipped grows by the row's skipped
+ *              count of that column, steps by 1.
+ *   response   inside integrate, the body's turn is the moving obstacle's with the shifts Dprev and D
+ *              (obstacle_respond_moved), and the loads record it as they record a moving entry.
+ *   lag        the coupling is explicit: the impulse received in step k changes the velocity used in
+ *              step k + 1.  Within a step the response treats the solid as infinitely heavy, so a body
+ *              much lighter than the fluid that touches it in one step oscillates: use heavy bodies.
+ *   quantum    sph_hip_set_bodies fixes the quantum of the rows the bodies consume.  A context with
+ *              bodies always records: into the caller's row while a recording has rows left, otherwise
+ *              into one of two internal rows.  While bodies are set, sph_hip_record_loads with rows > 0
+ *              and another quantum is refused; sph_hip_set_bodies is refused while a recording with
+ *              another quantum has rows left.  A recording therefore still changes no particle and no
+ *              body.
+ * sph_hip_set_bodies: n is the obstacle count, or 0 to clear the bodies; ordered on the context's stream
+ * like sph_hip_set_obstacles.  Refused with SPH_HIP_ERR_INVALID, the previous bodies and their state
+ * kept: an n that is neither; a null list with n > 0; quantum_log2 outside [-64, 32]; for an entry with
+ * mass != 0, a mass that is not finite and > 0, a velocity or accel that is not finite, free_axes with
+ * a bit above bit 2, travel_lo[c] <= 0 <= travel_hi[c] not holding (infinities are allowed); a body on
+ * an entry whose motion moves (and sph_hip_set_obstacle_motion refuses a moving motion on a body); the
+ * quantum rule above; any slab context (a body needs the sum of all slabs' rows before any slab may
+ * advance it: one all-reduce per step, which is not built); between sph_hip_slab_step_begin and _end.
+ * A context with bodies refuses sph_hip_slab_pack, _unpack and _step_begin.
+ * sph_hip_set_obstacles clears the bodies, as it clears the motions.
+ * sph_hip_get_bodies synchronises, copies up to `capacity` entries to `list` and `state` (either may be
+ * NULL) and returns how many entries are set (0 or the obstacle count).  sph_hip_get_obstacles_now adds
+ * a body's displacement to its obstacle and synchronises only when bodies are set.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no
+ * existing prototype changed. */
+typedef struct sph_hip_body {       /* field order is ABI: 56 bytes */
+   float mass;                      /* 0: not a body */
+   float velocity[3];               /* initial velocity, position units per unit of time_step */
+   float accel[3];                  /* body force per unit mass (gravity, say); the caller states it */
+   uint32_t free_axes;              /* bit c: component c may move */
+   float travel_lo[3], travel_hi[3];/* limits of the displacement: the stops */
+} sph_hip_body;
+typedef struct sph_hip_body_state { /* field order is ABI: 40 bytes */
+   float displacement[3];
+   float velocity[3];
+   int64_t skipped;                 /* responses the rows it consumed had left out */
+   int64_t steps;                   /* advances so far */
+} sph_hip_body_state;
+int sph_hip_set_bodies(sph_hip_context* ctx, const sph_hip_body* list, int n, int quantum_log2);
+int sph_hip_get_bodies(sph_hip_context* ctx, sph_hip_body* list, sph_hip_body_state* state, int capacity);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

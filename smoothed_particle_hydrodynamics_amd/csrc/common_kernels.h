@@ -2,6 +2,7 @@
 // neighbour-count statistics.
 #pragma once
 
+#include "body_policy.h"
 #include "cell_build.h"
 #include "load_policy.h"
 #include "obstacle_policy.h"
@@ -230,6 +231,21 @@ struct MovingLoadHook : LoadHook {
    }
 };
 
+// MovingLoadHook for a list with free bodies (body_policy.h): an entry takes the body turn with the
+// shifts its BodyState holds (written by k_bodies_advance earlier on the stream, read wave-uniformly), the
+// turn of its motion (`motion` is null when no motions are set), or the static turn.  Only after() differs.
+struct BodyLoadHook : LoadHook {
+   const sph_hip_obstacle_motion* motion;
+   float tau0, tau1;
+   const sph_hip_body* bodies;
+   const BodyState* state;
+   __device__ void after(const float* p, float* v, float* q, float m) const
+   {
+      body_obstacles_respond(list, motion, bodies, state, n, p, v, q, dt, damping, tau0, tau1, m,
+                             static_cast<const LoadHook&>(*this));
+   }
+};
+
 // The call the tuned kernels make, with the signature they always had (a hook parameter with a
 // default changed the code of k_full_accel_lists: tools/kernel_isa_diff.py).
 template <bool UNIT_SCALE>
@@ -374,6 +390,43 @@ k_integrate_loads_moving(float4* __restrict__ posm, float4* __restrict__ velp, c
    const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
    const bool live = p < meta[META_OWN_END];
    const MovingLoadHook hook = {{obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live}, motion, tau0, tau1};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
+}
+
+// Free bodies (body_policy.h; launch_policy.h: use_body_kernels).  One wave in front of every integrate of
+// a context with bodies: lane i advances the body of obstacle i from `row`, the load row the previous
+// integrate filled (null: none yet), and the wave zeroes `clear`, the internal row the coming integrate
+// fills (null: it fills a row of the caller's recording).  Every lane loads and stores its own words.
+__global__ void __launch_bounds__(SPH_WAVE)
+k_bodies_advance(const sph_hip_body* __restrict__ bodies, BodyState* __restrict__ state, int n_obst,
+                 const unsigned long long* row, int quantum_log2, float dt, unsigned long long* clear)
+{
+   const int lane = threadIdx.x;
+   if (clear)
+      for (int w = lane; w < LOAD_ROW_WORDS; w += SPH_WAVE) clear[w] = 0ull;
+   if (lane >= n_obst) return;
+   const sph_hip_body b = bodies[lane];
+   BodyState s = state[lane];
+   body_advance(b, s, reinterpret_cast<const long long*>(row), lane, quantum_log2, dt);
+   state[lane] = s;
+}
+
+// k_integrate_loads_moving for a list with bodies: `bodies` and `state` hold one entry per obstacle,
+// `motion` too or is null; always records into `row`.
+template <bool UNIT_SCALE, bool HASH>
+__global__ void __launch_bounds__(RED_THREADS)
+k_integrate_bodies(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
+                   const int32_t* __restrict__ meta, PairConsts k, double* __restrict__ epart, CellGrid g,
+                   uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                   uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                   unsigned long long* __restrict__ row, int quantum_log2,
+                   const sph_hip_obstacle_motion* __restrict__ motion, float tau0, float tau1,
+                   const sph_hip_body* __restrict__ bodies, const BodyState* __restrict__ state)
+{
+   const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   const bool live = p < meta[META_OWN_END];
+   const BodyLoadHook hook = {{obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live}, motion, tau0, tau1,
+                              bodies, state};
    integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
 }
 

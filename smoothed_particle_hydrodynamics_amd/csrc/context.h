@@ -321,6 +321,26 @@ struct sph_hip_context {
    DevBuf<unsigned long long> loads_dev;
    int loads_rows = 0, loads_next = 0;
    int loads_quantum = LOAD_QUANTUM_DEFAULT;
+
+   // free bodies (sph_hip_set_bodies): one entry per obstacle (n_body_entries = 0 or n_obst), n_bodies of
+   // them with a mass; the list and the initial state are staged and copied like the obstacle list.  The
+   // state lives on the device (k_bodies_advance).  body_rows: the two internal load rows, used alternately
+   // when no recording has rows left (body_flip: the one last filled); body_last_row: the row the last
+   // integrate enqueued filled - the caller's or an internal one - or null before the first
+   sph_hip_body bodies_host[SPH_HIP_MAX_OBSTACLES];
+   int n_body_entries = 0, n_bodies = 0;
+   int body_quantum = LOAD_QUANTUM_DEFAULT;
+   DevBuf<sph_hip_body> bodies_dev;
+   PinnedBuf<sph_hip_body> bodies_stage;
+   Event ev_bodies_copied;
+   int bodies_copy_pending = 0;
+   DevBuf<BodyState> body_state_dev;
+   PinnedBuf<BodyState> body_state_stage;
+   Event ev_body_state_copied;
+   int body_state_copy_pending = 0;
+   DevBuf<unsigned long long> body_rows;
+   int body_flip = 0;
+   const unsigned long long* body_last_row = nullptr;
 };
 
 namespace {
@@ -537,6 +557,13 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    CREATE_TRY(dev_alloc(ctx->motion_dev, SPH_HIP_MAX_OBSTACLES));
    CREATE_TRY(pinned_alloc(ctx->motion_stage, SPH_HIP_MAX_OBSTACLES));
    CREATE_TRY(event_create(ctx->ev_motion_copied));
+   CREATE_TRY(dev_alloc(ctx->bodies_dev, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(pinned_alloc(ctx->bodies_stage, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(event_create(ctx->ev_bodies_copied));
+   CREATE_TRY(dev_alloc(ctx->body_state_dev, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(pinned_alloc(ctx->body_state_stage, SPH_HIP_MAX_OBSTACLES));
+   CREATE_TRY(event_create(ctx->ev_body_state_copied));
+   CREATE_TRY(dev_alloc(ctx->body_rows, 2 * LOAD_ROW_WORDS));
    CREATE_TRY(hipStreamSynchronize(ctx->stream));
 #undef CREATE_TRY
    *out = ctx.release();

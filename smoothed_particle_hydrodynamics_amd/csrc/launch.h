@@ -549,7 +549,8 @@ void motion_tick(sph_hip_context* ctx, float tau[2])
 // with static obstacles, k_integrate_obst; while a load recording has rows left, k_integrate_loads
 // into the next row (an integrate without particles uses its row up too: the rows of the slabs of
 // one run stay in step); while some obstacle moves, their _moving forms with the step's motion clock,
-// which a slab's early pack has already taken (an integrate without particles advances it too)
+// which a slab's early pack has already taken (an integrate without particles advances it too); while
+// some obstacle is a free body, k_bodies_advance and k_integrate_bodies (with zero particles the advance alone)
 int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
 {
    const int n = ctx->n;
@@ -559,11 +560,31 @@ int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
    if (moving && !ctx->step_tau_taken) motion_tick(ctx, ctx->step_tau);
    ctx->step_tau_taken = 0;
    const float tau0 = ctx->step_tau[0], tau1 = ctx->step_tau[1];
+   // free bodies: the advance from the row the last integrate filled, then an integrate that always
+   // records - into the caller's row, or into the internal row the advance has just zeroed
+   const bool bodies = use_body_kernels(ctx->n_obst, ctx->n_bodies);
+   if (bodies) {
+      unsigned long long* clear = nullptr;
+      if (!load_row) {
+         ctx->body_flip ^= 1;
+         load_row = clear = ctx->body_rows.get() + (size_t)ctx->body_flip * LOAD_ROW_WORDS;
+      }
+      hipLaunchKernelGGL(k_bodies_advance, dim3(1), dim3(SPH_WAVE), 0, ctx->stream, ctx->bodies_dev, ctx->body_state_dev,
+                         ctx->n_obst, ctx->body_last_row, ctx->body_quantum, ctx->prm.time_step, clear);
+      ctx->body_last_row = load_row;
+      if (n == 0) SPH_TRY(hipGetLastError());
+   }
    if (n == 0) return SPH_HIP_OK;
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const int blocks = div_up(n, RED_THREADS);
    bind_flags([&](auto U, auto H) {
-      if (moving && load_row)
+      if (bodies)
+         hipLaunchKernelGGL((k_integrate_bodies<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,
+                            load_row, ctx->body_quantum, ctx->n_motion > 0 ? ctx->motion_dev.get() : nullptr, tau0, tau1,
+                            ctx->bodies_dev, ctx->body_state_dev);
+      else if (moving && load_row)
          hipLaunchKernelGGL((k_integrate_loads_moving<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
                             ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
                             ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,

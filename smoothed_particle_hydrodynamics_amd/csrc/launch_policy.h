@@ -280,6 +280,13 @@ inline bool fuse_slab_step(bool no_fused_slab, int n_obstacles, bool record_load
 // always launched.  (n_obstacles > 0 then also keeps the step off the fused routes above.)
 inline bool use_moving_kernels(int n_obstacles, int n_moving) { return n_obstacles > 0 && n_moving > 0; }
 
+// Whether a step's integrate is k_bodies_advance followed by k_integrate_bodies (free bodies,
+// body_policy.h): some entry of the body list is a body.  Such a step always records, into the caller's
+// row or an internal one, and it is launched with zero particles too (the bodies still advance).  A
+// context without bodies launches what it always launched, with the same arguments.  (n_obstacles > 0
+// keeps the step off the fused routes above; the motion clock advances as use_moving_kernels says.)
+inline bool use_body_kernels(int n_obstacles, int n_bodies) { return n_obstacles > 0 && n_bodies > 0; }
+
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
 // slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary

@@ -15,11 +15,19 @@ extern "C" __global__ void k_msg_fill(const SlabMsg* __restrict__ left, const Sl
 
 namespace {
 
+// free bodies (body_policy.h) are advanced from one context's rows: a context that holds some cannot be a slab
+int refuse_bodies(sph_hip_context* ctx)
+{
+   ctx->err = "a context with bodies (sph_hip_set_bodies) cannot exchange with neighbouring slabs";
+   return SPH_HIP_ERR_INVALID;
+}
+
 int slab_pack(sph_hip_context* ctx, void* left_device, void* right_device,
                       int capacity_records)
 {
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
+   if (ctx->n_bodies > 0) return refuse_bodies(ctx);
    hipStream_t st = ctx->stream;
    ctx->had_exchange = 1;
    if ((rc = drop_prehash(ctx))) return rc;
@@ -40,6 +48,7 @@ int slab_unpack(sph_hip_context* ctx, const void* left_device, const void* right
 {
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
+   if (ctx->n_bodies > 0) return refuse_bodies(ctx);
    ctx->had_exchange = 1;
    // (a slab's fused step has hashed its owned entries for the next build, which hashes what is
    // unpacked here: that stays; a whole-grid prehash knows nothing of new entries)
@@ -58,6 +67,7 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
 {
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
+   if (ctx->n_bodies > 0) return refuse_bodies(ctx);
    if (!ctx->use_tiled) {
       ctx->err = "sph_hip_slab_step_begin: needs the tiled kernels (SPH_HIP_UNTILED is set)";
       return SPH_HIP_ERR_INVALID;

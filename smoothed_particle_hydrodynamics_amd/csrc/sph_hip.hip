@@ -801,6 +801,23 @@ int sph_hip_integrate(sph_hip_context* ctx)
 
 // ---- static obstacles (obstacle_policy.h; routes: launch_policy.h fuse_integrate / fuse_slab_step) ----
 
+namespace {
+void clear_bodies(sph_hip_context* ctx)
+{
+   ctx->n_body_entries = ctx->n_bodies = 0;
+   ctx->body_last_row = nullptr;
+}
+
+// the device state of every body entry, after everything enqueued so far (synchronises)
+int read_body_states(sph_hip_context* ctx, BodyState* out)
+{
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (ctx->n_body_entries > 0)
+      SPH_TRY(hipMemcpy(out, ctx->body_state_dev, sizeof(BodyState) * (size_t)ctx->n_body_entries, hipMemcpyDeviceToHost));
+   return SPH_HIP_OK;
+}
+} // namespace
+
 int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, int n)
 {
    int rc = check_ctx(ctx);
@@ -821,6 +838,7 @@ int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, in
    ctx->n_obst = n;   // the steps enqueued from here on take the routes of this count
    ctx->n_motion = ctx->n_moving = 0;   // a new list stands still
    ctx->motion_tau = 0.0f;
+   clear_bodies(ctx);                   // ... and is nobody's body
    return SPH_HIP_OK;
 }
 
@@ -843,6 +861,10 @@ int sph_hip_set_obstacle_motion(sph_hip_context* ctx, const sph_hip_obstacle_mot
    int rc = check_ctx(ctx);
    if (rc) return rc;
    if (const char* why = obstacle_motion_check(list, n, ctx->n_obst)) {
+      ctx->err = std::string("sph_hip_set_obstacle_motion: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (const char* why = body_motion_check(list, n, ctx->bodies_host, ctx->n_body_entries)) {
       ctx->err = std::string("sph_hip_set_obstacle_motion: ") + why;
       return SPH_HIP_ERR_INVALID;
    }
@@ -885,7 +907,74 @@ int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int c
    const int k = capacity < ctx->n_obst ? capacity : ctx->n_obst;
    for (int i = 0; i < k; i++)
       out[i] = obstacle_at(ctx->obst_host[i], i < ctx->n_motion ? &ctx->motion_host[i] : nullptr, ctx->motion_tau);
+   if (ctx->n_bodies > 0 && k > 0) {   // a body stands where the device has moved it to
+      BodyState st[SPH_HIP_MAX_OBSTACLES];
+      int rc = check_ctx(ctx);
+      if (rc) return rc;
+      if ((rc = read_body_states(ctx, st))) return rc;
+      for (int i = 0; i < k; i++)
+         if (body_is(ctx->bodies_host[i])) out[i] = obstacle_shifted(ctx->obst_host[i], st[i].D);
+   }
    return ctx->n_obst;
+}
+
+// ---- free bodies (body_policy.h; routes: launch_policy.h use_body_kernels) --------------------------
+
+int sph_hip_set_bodies(sph_hip_context* ctx, const sph_hip_body* list, int n, int quantum_log2)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* why = body_check(list, n, ctx->n_obst, ctx->motion_host, ctx->n_motion, quantum_log2);
+   const int n_bodies = why ? 0 : bodies_count(list, n);
+   if (!why)
+      why = recording_refuses_bodies(ctx->loads_rows - ctx->loads_next, ctx->loads_quantum, n_bodies, quantum_log2);
+   if (!why && n_bodies > 0 &&
+       (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange || ctx->comm))
+      why = "slab contexts (with neighbours, or that have exchanged) cannot hold bodies";
+   if (!why && ctx->slab_step_open) why = "not between sph_hip_slab_step_begin and sph_hip_slab_step_end";
+   if (why) {
+      ctx->err = std::string("sph_hip_set_bodies: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (n > 0) {
+      BodyState initial[SPH_HIP_MAX_OBSTACLES];
+      for (int i = 0; i < n; i++) initial[i] = body_initial(list[i]);
+      if ((rc = stage_list(ctx, list, n, ctx->bodies_stage, ctx->bodies_dev, ctx->ev_bodies_copied,
+                           ctx->bodies_copy_pending)))
+         return rc;
+      if ((rc = stage_list(ctx, initial, n, ctx->body_state_stage, ctx->body_state_dev, ctx->ev_body_state_copied,
+                           ctx->body_state_copy_pending)))
+         return rc;
+      memcpy(ctx->bodies_host, list, sizeof(sph_hip_body) * (size_t)n);
+   }
+   ctx->n_body_entries = n;   // the steps enqueued from here on take the routes of these bodies
+   ctx->n_bodies = n_bodies;
+   ctx->body_quantum = quantum_log2;
+   ctx->body_last_row = nullptr;   // the first advance takes a zero impulse
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_bodies(sph_hip_context* ctx, sph_hip_body* list, sph_hip_body_state* state, int capacity)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (capacity < 0) {
+      ctx->err = "sph_hip_get_bodies: capacity must be >= 0";
+      return SPH_HIP_ERR_INVALID;
+   }
+   const int k = capacity < ctx->n_body_entries ? capacity : ctx->n_body_entries;
+   BodyState st[SPH_HIP_MAX_OBSTACLES];
+   if ((rc = read_body_states(ctx, st))) return rc;
+   if (list && k > 0) memcpy(list, ctx->bodies_host, sizeof(sph_hip_body) * (size_t)k);
+   for (int i = 0; state && i < k; i++) {
+      for (int c = 0; c < 3; c++) {
+         state[i].displacement[c] = st[i].D[c];
+         state[i].velocity[c] = st[i].V[c];
+      }
+      state[i].skipped = st[i].skipped;
+      state[i].steps = st[i].steps;
+   }
+   return ctx->n_body_entries;
 }
 
 // ---- loads on walls and obstacles (load_policy.h; kernel: k_integrate_loads) ----------------------
@@ -895,6 +984,10 @@ int sph_hip_record_loads(sph_hip_context* ctx, int rows, int quantum_log2)
    int rc = check_ctx(ctx);
    if (rc) return rc;
    if (const char* why = load_check(rows, quantum_log2)) {
+      ctx->err = std::string("sph_hip_record_loads: ") + why;
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (const char* why = body_refuses_recording(ctx->n_bodies, ctx->body_quantum, rows, quantum_log2)) {
       ctx->err = std::string("sph_hip_record_loads: ") + why;
       return SPH_HIP_ERR_INVALID;
    }
@@ -911,6 +1004,16 @@ int sph_hip_record_loads(sph_hip_context* ctx, int rows, int quantum_log2)
          return SPH_HIP_ERR_CAPACITY;
       }
       SPH_TRY(hipMemsetAsync(fresh, 0, words * sizeof(unsigned long long), ctx->stream));
+   }
+   // the bodies' next advance reads the row the last integrate filled: when that is a row of the recording
+   // this call replaces, it moves to the internal row that is free
+   if (ctx->n_bodies > 0 && ctx->loads_dev && ctx->body_last_row >= ctx->loads_dev.get() &&
+       ctx->body_last_row < ctx->loads_dev.get() + (size_t)ctx->loads_rows * LOAD_ROW_WORDS) {
+      ctx->body_flip ^= 1;
+      unsigned long long* keep = ctx->body_rows.get() + (size_t)ctx->body_flip * LOAD_ROW_WORDS;
+      SPH_TRY(hipMemcpyAsync(keep, ctx->body_last_row, LOAD_ROW_WORDS * sizeof(unsigned long long),
+                             hipMemcpyDeviceToDevice, ctx->stream));
+      ctx->body_last_row = keep;
    }
    // steps already queued may still be adding to the rows this call replaces
    if (ctx->loads_dev) SPH_TRY(hipStreamSynchronize(ctx->stream));

@@ -1,4 +1,5 @@
 """ctypes binding of include/sph_hip.h.  Fails loudly when the HIP library is absent."""
+import collections
 import ctypes as C
 import os
 
@@ -73,7 +74,7 @@ class SphRenderParams(C.Structure):
 
 
 from . import obstacles as _obstacles  # noqa: E402
-from .obstacles import SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of sph_hip_obstacle[_motion])
+from .obstacles import SphBody, SphBodyState, SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of the C structs)
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -127,6 +128,8 @@ PROTOTYPES = {
     "sph_hip_set_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int]),
     "sph_hip_get_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int, _P(C.c_float)]),
     "sph_hip_get_obstacles_now": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
+    "sph_hip_set_bodies": (C.c_int, [_ctx, _P(SphBody), C.c_int, C.c_int]),
+    "sph_hip_get_bodies": (C.c_int, [_ctx, _P(SphBody), _P(SphBodyState), C.c_int]),
     "sph_hip_record_loads": (C.c_int, [_ctx, C.c_int, C.c_int]),
     "sph_hip_get_loads": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
@@ -247,6 +250,11 @@ class Loads:
                      self.quantum_log2)
 
 
+# sph_hip_get_bodies' answer: bodies [Body or None per obstacle], displacement and velocity float32 (n, 3),
+# skipped and steps int64 (n,); n = 0 when no bodies are set
+Bodies = collections.namedtuple("Bodies", ["bodies", "displacement", "velocity", "skipped", "steps"])
+
+
 class Context:
     """Owner of one sph_hip_context handle: creation, destruction, the checked call, and the
     operations that need nothing but the handle.  SPH (sph.py) and HipSlab (slab.py) derive from it."""
@@ -342,7 +350,8 @@ class Context:
 
     def get_obstacles(self, now=False):
         """The context's obstacles, in list order: as they were set, or (now=True) displaced by their
-        motions to the current motion clock (sph_hip_get_obstacles_now)."""
+        motions to the current motion clock and, free bodies, to where the device has moved them
+        (sph_hip_get_obstacles_now)."""
         arr = (SphObstacle * _obstacles.MAX_OBSTACLES)()
         n = self.call("sph_hip_get_obstacles_now" if now else "sph_hip_get_obstacles", arr, _obstacles.MAX_OBSTACLES)
         return [_obstacles.from_struct(arr[i]) for i in range(n)]

@@ -4,8 +4,8 @@
 gives the C ABI's sph_hip_obstacle, `signed_distance(points)` the numpy distance to the surface
 (negative inside), for placing obstacles and checking results.  `Motion` is the constant velocity an
 obstacle is driven at between two readings of the context's motion clock
-(sph_hip_set_obstacle_motion).  The collision response itself is csrc/obstacle_policy.h and runs on
-the GPU.
+(sph_hip_set_obstacle_motion); `Body` makes it a free body that the fluid's own loads move
+(sph_hip_set_bodies).  The collision response itself is csrc/obstacle_policy.h and runs on the GPU.
 """
 import ctypes as C
 import math
@@ -188,6 +188,76 @@ def as_motion_array(motions):
             m = Motion((0.0, 0.0, 0.0))
         arr[i] = m if isinstance(m, SphObstacleMotion) else m.as_struct()
     return arr, len(motions)
+
+
+class SphBody(C.Structure):
+    """Mirror of sph_hip_body (include/sph_hip.h): 56 bytes, field order is ABI."""
+
+    _fields_ = [("mass", C.c_float), ("velocity", C.c_float * 3), ("accel", C.c_float * 3), ("free_axes", C.c_uint32),
+                ("travel_lo", C.c_float * 3), ("travel_hi", C.c_float * 3)]
+
+
+class SphBodyState(C.Structure):
+    """Mirror of sph_hip_body_state (include/sph_hip.h): 40 bytes, field order is ABI."""
+
+    _fields_ = [("displacement", C.c_float * 3), ("velocity", C.c_float * 3), ("skipped", C.c_int64),
+                ("steps", C.c_int64)]
+
+
+class Body:
+    """An obstacle that the fluid's loads move (sph_hip_set_bodies): `mass`, the initial `velocity`
+    (position units per unit of time_step), `accel` (body force per unit mass, gravity say), `free` (which
+    components may move) and the limits of its displacement, travel_lo <= 0 <= travel_hi per component -
+    the stops that stand in for walls and floor.  The coupling lags one step and treats the solid as
+    infinitely heavy within a step: use bodies several times heavier than the fluid they displace."""
+
+    def __init__(self, mass, velocity=(0.0, 0.0, 0.0), accel=(0.0, 0.0, 0.0), free=(True, True, True),
+                 travel_lo=(-math.inf,) * 3, travel_hi=(math.inf,) * 3):
+        self.mass = np.float32(mass)
+        self.velocity, self.accel = _vec3(velocity), _vec3(accel)
+        self.free = tuple(bool(f) for f in free)
+        if len(self.free) != 3:
+            raise ValueError("free takes three values")
+        self.travel_lo, self.travel_hi = _vec3(travel_lo), _vec3(travel_hi)
+
+    @property
+    def free_axes(self):
+        return sum(1 << c for c in range(3) if self.free[c])
+
+    def as_struct(self):
+        s = SphBody()
+        s.mass = float(self.mass)
+        s.velocity[:] = [float(v) for v in self.velocity]
+        s.accel[:] = [float(v) for v in self.accel]
+        s.free_axes = self.free_axes
+        s.travel_lo[:] = [float(v) for v in self.travel_lo]
+        s.travel_hi[:] = [float(v) for v in self.travel_hi]
+        return s
+
+    def __eq__(self, other):
+        return isinstance(other, Body) and bytes(self.as_struct()) == bytes(other.as_struct())
+
+    def __repr__(self):
+        return "Body(%g, %s, %s, %s, %s, %s)" % (self.mass, list(self.velocity), list(self.accel), self.free,
+                                                 list(self.travel_lo), list(self.travel_hi))
+
+
+def body_from_struct(s):
+    """The Body an sph_hip_body describes; None for an entry that is not a body (mass == 0)."""
+    if s.mass == 0:
+        return None
+    return Body(s.mass, list(s.velocity), list(s.accel), [bool(s.free_axes >> c & 1) for c in range(3)],
+                list(s.travel_lo), list(s.travel_hi))
+
+
+def as_body_array(bodies):
+    """A ctypes array of sph_hip_body for a list of Body, struct or None (not a body: all zero)."""
+    bodies = list(bodies)
+    arr = (SphBody * max(1, len(bodies)))()
+    for i, b in enumerate(bodies):
+        if b is not None:
+            arr[i] = b if isinstance(b, SphBody) else b.as_struct()
+    return arr, len(bodies)
 
 
 def inside_any(points, obstacles):

@@ -205,3 +205,33 @@ def dam_break_gate(n, lift_speed, thickness=2.0, surge=0.7, box=(1.0, 1.0, 1.0),
     pos, vel, mass = carve(pos, vel, mass, [gate])
     travel = top + 2.0 * h
     return p, pos, vel, mass, [gate], [Motion((0.0, lift_speed, 0.0), 0.0, travel / lift_speed)]
+
+
+def dam_break_debris(n, size=(0.12, 0.12, 0.3), gap=3.0, density_ratio=6.0, surge=0.7, box=(1.0, 1.0, 1.0),
+                     fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42, gravity=-9.81):
+    """The surging dam column of dam_break_pillar (gravity along -y, the walls on, the surge along +x) with a
+    piece of debris downstream of it: a Box of `size` standing on the floor, centred along z, its upstream
+    face `gap` kernel radii from the column's face.  It is a free body (obstacles.Body) along the surge axis
+    only - the floor carries it - whose mass is `density_ratio` (at least 4: the coupling treats the solid as
+    infinitely heavy within a step) times the mass of the fluid it displaces at the column's density, and
+    whose travel ends one kernel radius before the downstream wall, so that it stays inside the domain.
+    Returns (params, pos, vel, mass, [Box], [Body]): setObstacles, then setBodies."""
+    from .obstacles import Body, Box
+    if density_ratio < 4.0:
+        raise ValueError("density_ratio must be at least 4")
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    vel.reshape(-1, 3)[:, 0] = np.float32(surge)
+    h = float(p.h)
+    x0 = box[0] * fill[0] + gap * h
+    z0 = 0.5 * (float(p.max_z) - size[2])
+    debris = Box((x0, 0.0, z0), (x0 + size[0], size[1], z0 + size[2]))
+    column = box[0] * fill[0] * box[1] * fill[1] * box[2] * fill[2]
+    displaced = float(mass.sum()) / column * size[0] * size[1] * size[2]
+    travel = float(p.max_x) - h - float(debris.hi[0])
+    body = Body(density_ratio * displaced, free=(True, False, False), travel_lo=(0.0, 0.0, 0.0),
+                travel_hi=(travel, 0.0, 0.0))
+    pos, vel, mass = carve(pos, vel, mass, [debris])
+    return p, pos, vel, mass, [debris], [body]

@@ -14,7 +14,8 @@ import zlib
 
 import numpy as np
 
-from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Context, SphCamera, SphRenderParams, _ptr, default_params
+from . import obstacles as _O
+from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
@@ -227,6 +228,26 @@ class SPH(Context):
     setObstacles, getObstacles = Context.set_obstacles, Context.get_obstacles
     setObstacleMotion, getObstacleMotion = Context.set_obstacle_motion, Context.get_obstacle_motion
     recordLoads, getLoads = Context.record_loads, Context.get_loads
+
+    def setBodies(self, bodies, quantum_log2=-24):
+        """Make obstacles free bodies that the fluid's loads move (sph_hip_set_bodies): one obstacles.Body per
+        obstacle, None for one that is not a body; an empty list clears the bodies.  quantum_log2 is the
+        quantum of the load rows the bodies consume: a recording made meanwhile must use the same.  Single
+        contexts only: a body needs the sum of all slabs' rows before any slab may advance it."""
+        arr, n = _O.as_body_array(bodies)
+        self.call("sph_hip_set_bodies", arr, n, int(quantum_log2))
+
+    def getBodies(self):
+        """The bodies and their state after every step enqueued so far, as a Bodies (sph_hip_get_bodies;
+        synchronises)."""
+        lst = (_O.SphBody * _O.MAX_OBSTACLES)()
+        st = (_O.SphBodyState * _O.MAX_OBSTACLES)()
+        n = self.call("sph_hip_get_bodies", lst, st, _O.MAX_OBSTACLES)
+        return Bodies([_O.body_from_struct(lst[i]) for i in range(n)],
+                      np.array([list(st[i].displacement) for i in range(n)], np.float32).reshape(n, 3),
+                      np.array([list(st[i].velocity) for i in range(n)], np.float32).reshape(n, 3),
+                      np.array([st[i].skipped for i in range(n)], np.int64),
+                      np.array([st[i].steps for i in range(n)], np.int64))
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
