@@ -613,6 +613,62 @@ typedef struct sph_hip_body_state { /* field order is ABI: 40 bytes */
 int sph_hip_set_bodies(sph_hip_context* ctx, const sph_hip_body* list, int n, int quantum_log2);
 int sph_hip_get_bodies(sph_hip_context* ctx, sph_hip_body* list, sph_hip_body_state* state, int capacity);
 
+/* ---- tracers --------------------------------------------------------------------------------- *
+ *
+ * Massless markers the fluid carries: pathlines, a dye front, residence times.  FULL mode keeps the
+ * particles cell-sorted, so a particle's place in memory says nothing about its path; a tracer is a point
+ * of its own - x[3], int32 wet_steps, int32 dry_steps - that lives on the device and is advanced inside
+ * every step, so that queued steps stay queued.  No counterpart in the reference.  The operation-by-
+ * operation contract is in csrc/tracer_policy.h; all arithmetic is fp32, unfused, in the order written.
+ *   contexts   FULL and FULL_FAST contexts that hold the whole grid: what the field sampler accepts, with
+ *              the sampler's refusals for REF and slab contexts.
+ *   advance    step k advances every tracer once, after that step's cell build and before anything moves
+ *              the particles, in the state S_k the sampler would see at that moment, with dt = time_step as
+ *              in force when the step is enqueued (by value: a later setter does not reach queued steps).
+ *              sample(S, p) is sph_hip_sample_points at p: Shepard velocity u and member count c.
+ *                1  (u1, c1) = sample(S_k, x)
+ *                2  c1 == 0: the tracer is dry this step - x unchanged, dry_steps += 1, done
+ *                3  half = 0.5f * dt; xm_c = x_c + u1_c * half; (u2, c2) = sample(S_k, xm);
+ *                   u = c2 > 0 ? u2 : u1
+ *                4  y_c = x_c + u_c * dt; if any y_c is not finite the tracer is dry as in 2
+ *                5  apply_walls: y_c < 0 gives y_c = 0, y_c > max_c gives y_c = max_c - a clamp, not the
+ *                   particles' reflection: a marker has no momentum
+ *                6  x = y; wet_steps += 1
+ *              The midpoint rule in the velocity field frozen at the start of the step.  Tracers read
+ *              positions, masses and velocities of S_k only and never write anything a particle kernel
+ *              reads: every particle, density, acceleration and energy is bit-identical to a run without
+ *              tracers.  sph_hip_step, sph_hip_run and the phase calls give the same tracer bits: the
+ *              stand-alone sph_hip_integrate advances the tracers first, after bringing the cell structure
+ *              up to date as the sampler does.  With no particle resident every tracer is dry.
+ *   order      the device keeps the tracers in slots that carry their ids and re-sorts the slots by FULL
+ *              cell id now and then (SPH_HIP_TRACER_SORT=n, read at creation: every n steps, 0 never); no
+ *              result depends on the slot order, and every array below is in the order given to
+ *              sph_hip_set_tracers.
+ *   not done   solids do not stop a tracer: one that ends inside an obstacle finds no members there and
+ *              stays dry.  Slab contexts and REF mode are refused.  Tracers do not interact.
+ * sph_hip_set_tracers replaces the set (n = 0 clears it) with zeroed counts, ends a recording and waits
+ * for the steps already queued.  SPH_HIP_ERR_INVALID, the old set kept, for n < 0, a null array with
+ * n > 0, a coordinate that is not finite, and a REF or slab context.  The set survives sph_hip_upload,
+ * sph_hip_set_params and sph_hip_set_arithmetic.
+ * sph_hip_get_tracers synchronises and copies tracers [first, first + n); any output may be NULL.
+ * sph_hip_tracer_count returns how many tracers are set.
+ * sph_hip_record_tracers keeps the positions after recorded steps on the device: steps are numbered
+ * 1, 2, ... from this call, row r holds the positions after step 1 + r * every, for r < rows - the next
+ * step, then every every-th.  rows = 0 stops and frees the recording.  SPH_HIP_ERR_INVALID, the previous
+ * recording kept, for rows < 0, every < 1, and rows * count * 12 bytes above the 64 MiB scratch budget of
+ * the sampler and the extractor.
+ * sph_hip_get_tracer_path synchronises, copies rows [first_row, first_row + n_rows) of the rows filled so
+ * far - xyz[n_rows][count][3] by tracer id, step_index[n_rows] the step numbers; either may be NULL - and
+ * returns how many rows are filled (n_rows = 0 asks just that).  SPH_HIP_ERR_INVALID for a range that
+ * leaves the filled rows.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no struct and no existing
+ * prototype changed. */
+int sph_hip_set_tracers(sph_hip_context* ctx, int n, const float* xyz);
+int sph_hip_get_tracers(sph_hip_context* ctx, int first, int n, float* xyz, int32_t* wet_steps, int32_t* dry_steps);
+int sph_hip_tracer_count(const sph_hip_context* ctx);
+int sph_hip_record_tracers(sph_hip_context* ctx, int rows, int every);
+int sph_hip_get_tracer_path(sph_hip_context* ctx, int first_row, int n_rows, float* xyz, int32_t* step_index);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -8,4 +8,5 @@ from .lib import SphParams, load_library, SphHipError, default_params  # noqa: F
 from .sph import SPH, Particle, SurfaceMesh, write_ply, Camera, RenderResult, write_png, MODE_REF, MODE_FULL, MODE_FULL_FAST, ARITH_EXACT, ARITH_FAST  # noqa: F401
 from .lib import TIMING_OFF, TIMING_SUMS, TIMING_PHASES  # noqa: F401
 from .lib import Loads, LOAD_SOLIDS  # noqa: F401
+from .lib import Tracers, TracerPath  # noqa: F401
 from . import obstacles, scenes  # noqa: F401

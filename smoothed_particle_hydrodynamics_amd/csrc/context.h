@@ -20,6 +20,7 @@
 #include "sample_kernels.h"
 #include "surface_kernels.h"
 #include "render_kernels.h"
+#include "tracer_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
 
@@ -341,6 +342,23 @@ struct sph_hip_context {
    DevBuf<unsigned long long> body_rows;
    int body_flip = 0;
    const unsigned long long* body_last_row = nullptr;
+
+   // tracers (sph_hip_set_tracers): n_tracers slots {x, y, z, id} and {wet, dry} in pair tr_cur of two (the
+   // sort moves them to the other pair); the sort's scratch - per-slot key and rank, the cells' counts padded
+   // to whole scan tiles, the tiles' totals - allocated with the set when it is kept sorted; advances since
+   // the last sort, counted here so that nothing is read back
+   int n_tracers = 0;
+   DevBuf<float4> tr_xi[2];
+   DevBuf<int2> tr_cnt[2];
+   int tr_cur = 0;
+   DevBuf<uint32_t> tr_key, tr_rank, tr_cells, tr_part;
+   int tracer_sort_switch = -1;    // SPH_HIP_TRACER_SORT (tracer_policy.h: tracer_sort_switch), read at creation
+   long long tr_since_sort = 0;
+   // recording (sph_hip_record_tracers): trec_rows rows of 3 * n_tracers floats; trec_step = steps advanced
+   // since the call, trec_filled = rows those steps have filled
+   DevBuf<float> trec_dev;
+   int trec_rows = 0, trec_every = 1, trec_filled = 0;
+   long long trec_step = 0;
 };
 
 namespace {
@@ -424,6 +442,7 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
                                                               : SAMPLE_ROUTE_DEFAULT;
    if (const char* v = getenv("SPH_HIP_SURFACE_PLANES")) ctx->surf_planes_forced = atoi(v) > 0 ? atoi(v) : 0;
    ctx->render_noskip = getenv_flag("SPH_HIP_RENDER_NOSKIP");
+   ctx->tracer_sort_switch = tracer_sort_switch(getenv("SPH_HIP_TRACER_SORT"));
    ctx->device = device;
    ctx->capacity = capacity;
 

@@ -614,6 +614,60 @@ int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
    return SPH_HIP_OK;
 }
 
+// ---- tracers (tracer_kernels.h; decisions: tracer_policy.h) -------------------------------------------
+// the counting sort of the slots by cell, into the other pair of arrays
+int launch_tracer_sort(sph_hip_context* ctx)
+{
+   const int n = ctx->n_tracers, blocks = div_up(n, 256), cur = ctx->tr_cur;
+   const CellGrid g = ctx->grid;
+   hipStream_t st = ctx->stream;
+   SPH_TRY(hipMemsetAsync(ctx->tr_cells, 0, ((size_t)ctx->scan_tiles * SCAN_TILE + 16) * sizeof(uint32_t), st));
+   hipLaunchKernelGGL(k_tracer_hash, dim3(blocks), dim3(256), 0, st, ctx->tr_xi[cur], n, g, ctx->tr_cells,
+                      ctx->tr_key, ctx->tr_rank);
+   hipLaunchKernelGGL(k_scan_reduce, dim3(ctx->scan_tiles), dim3(SCAN_THREADS), 0, st, ctx->tr_cells, g.ncells,
+                      ctx->tr_part);
+   hipLaunchKernelGGL(k_tracer_scan, dim3(ctx->scan_tiles), dim3(SCAN_THREADS), 0, st, ctx->tr_cells, g.ncells,
+                      ctx->tr_part);
+   hipLaunchKernelGGL(k_tracer_scatter, dim3(blocks), dim3(256), 0, st, ctx->tr_xi[cur], ctx->tr_cnt[cur], n,
+                      ctx->tr_key, ctx->tr_rank, ctx->tr_cells, ctx->tr_xi[cur ^ 1], ctx->tr_cnt[cur ^ 1]);
+   SPH_TRY(hipGetLastError());
+   ctx->tr_cur = cur ^ 1;
+   ctx->tr_since_sort = 0;
+   return SPH_HIP_OK;
+}
+
+// One advance of every tracer in the sorted state the cell build has just produced (posm / velp of
+// ctx->cur, cell_start), with the time step in force; the row of a recording it fills travels as a kernel
+// argument.  Nothing here synchronises.
+int launch_tracers(sph_hip_context* ctx)
+{
+   const int n = ctx->n_tracers;
+   if (n == 0) return SPH_HIP_OK;
+   if (tracer_sort_due(n, ctx->tracer_sort_switch, ctx->tr_since_sort)) {
+      int rc = launch_tracer_sort(ctx);
+      if (rc) return rc;
+   }
+   ctx->tr_since_sort++;
+   float* row = nullptr;
+   if (ctx->trec_rows > 0) {
+      const int r = tracer_record_row(++ctx->trec_step, ctx->trec_every, ctx->trec_rows);
+      if (r >= 0) {
+         row = ctx->trec_dev.get() + (size_t)r * 3 * (size_t)n;
+         ctx->trec_filled = r + 1;
+      }
+   }
+   const sph_hip_params& p = ctx->prm;
+   const TracerStep ts = {p.time_step, p.apply_walls, {p.max_x, p.max_y, p.max_z}, ctx->n > 0 ? 1 : 0};
+   const PairConsts k = pair_consts(p, ctx->fast != 0);
+   bind_flags([&](auto U) {
+      hipLaunchKernelGGL((k_tracers_advance<U.value>), dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,
+                         ctx->tr_xi[ctx->tr_cur], ctx->tr_cnt[ctx->tr_cur], n, ctx->posm[ctx->cur], ctx->velp[ctx->cur],
+                         ctx->cell_start, ctx->grid, k, ts, row);
+   }, unit_scale(p));
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
 // buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
 // (prehashed: 1 whole grid, 2 a slab's owned entries).
@@ -690,6 +744,7 @@ int step_impl(sph_hip_context* ctx, bool timed)
    if ((rc = open_step(ctx, timed, se))) return rc;
    if ((rc = mark_phase(ctx, se, 0, st))) return rc;
    if ((rc = launch_cell_build(ctx))) return rc;
+   if (ctx->n_tracers > 0 && (rc = launch_tracers(ctx))) return rc;   // in S_k, before anything moves
    if ((rc = mark_phase(ctx, se, 1, st))) return rc;
    if ((rc = launch_find_neighbors(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 2, st))) return rc;

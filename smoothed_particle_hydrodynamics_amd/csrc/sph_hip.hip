@@ -795,8 +795,154 @@ int sph_hip_integrate(sph_hip_context* ctx)
 {
    int rc = check_ctx(ctx);
    if (rc) return rc;
+   // tracers advance first, in the state the integrate is about to move: the cell structure is brought up to
+   // date the way the sampler does it (the build consumes a pending prehash and moves the sums along)
+   if (ctx->n_tracers > 0) {
+      if (ctx->n > 0 && (rc = sample_prepare(ctx))) return rc;
+      if ((rc = launch_tracers(ctx))) return rc;
+   }
    if ((rc = drop_prehash(ctx))) return rc;   // the state moves on without a new hash
    return launch_integrate(ctx);
+}
+
+// ---- tracers (tracer_kernels.h; contract and decisions: tracer_policy.h) ----------------------------
+
+namespace {
+void stop_tracer_recording(sph_hip_context* ctx)
+{
+   ctx->trec_dev.reset();
+   ctx->trec_rows = ctx->trec_filled = 0;
+   ctx->trec_every = 1;
+   ctx->trec_step = 0;
+}
+} // namespace
+
+int sph_hip_set_tracers(sph_hip_context* ctx, int n, const float* xyz)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = tracer_check(n, xyz)) return refuse(ctx, "sph_hip_set_tracers", why);
+   if ((rc = sample_check(ctx, "sph_hip_set_tracers"))) return rc;
+   // the new set's arrays first: a failure keeps the old set
+   DevBuf<float4> xi[2];
+   DevBuf<int2> cnt[2];
+   DevBuf<uint32_t> key, rank, cells, part;
+   const bool sorted = tracer_use_sort(n, ctx->tracer_sort_switch);
+   std::unique_ptr<float4[]> host;
+   if (n > 0) {
+      host.reset(new (std::nothrow) float4[(size_t)n]);
+      bool ok = host != nullptr;
+      for (int b = 0; ok && b < (sorted ? 2 : 1); b++)
+         ok = dev_alloc(xi[b], (size_t)n) == hipSuccess && dev_alloc(cnt[b], (size_t)n) == hipSuccess;
+      if (ok && sorted)
+         ok = dev_alloc(key, (size_t)n) == hipSuccess && dev_alloc(rank, (size_t)n) == hipSuccess &&
+              dev_alloc(cells, (size_t)ctx->scan_tiles * SCAN_TILE + 16) == hipSuccess &&
+              dev_alloc(part, (size_t)ctx->scan_tiles + 1) == hipSuccess;
+      if (!ok) {
+         (void)hipGetLastError();
+         ctx->err = "sph_hip_set_tracers: cannot allocate " + std::to_string(n) + " tracers";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      for (int i = 0; i < n; i++) {
+         const uint32_t id = (uint32_t)i;
+         float w;
+         memcpy(&w, &id, sizeof(w));
+         host[i] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], w);
+      }
+   }
+   // steps already queued advance the old set: wait for them before it goes
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (n > 0) {
+      SPH_TRY(hipMemcpy(xi[0], host.get(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+      SPH_TRY(hipMemset(cnt[0], 0, sizeof(int2) * (size_t)n));
+   }
+   for (int b = 0; b < 2; b++) {
+      ctx->tr_xi[b] = std::move(xi[b]);
+      ctx->tr_cnt[b] = std::move(cnt[b]);
+   }
+   ctx->tr_key = std::move(key);
+   ctx->tr_rank = std::move(rank);
+   ctx->tr_cells = std::move(cells);
+   ctx->tr_part = std::move(part);
+   ctx->n_tracers = n;
+   ctx->tr_cur = 0;
+   ctx->tr_since_sort = 0;
+   stop_tracer_recording(ctx);
+   if (sorted && (rc = launch_tracer_sort(ctx))) return rc;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_tracer_count(const sph_hip_context* ctx) { return ctx ? ctx->n_tracers : SPH_HIP_ERR_INVALID; }
+
+int sph_hip_get_tracers(sph_hip_context* ctx, int first, int n, float* xyz, int32_t* wet_steps, int32_t* dry_steps)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = tracer_range_check(first, n, ctx->n_tracers)) return refuse(ctx, "sph_hip_get_tracers", why);
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   const int total = ctx->n_tracers;
+   if (n == 0 || total == 0) return SPH_HIP_OK;
+   std::unique_ptr<float4[]> x(new (std::nothrow) float4[(size_t)total]);
+   std::unique_ptr<int2[]> c(new (std::nothrow) int2[(size_t)total]);
+   if (!x || !c) {
+      ctx->err = "sph_hip_get_tracers: out of host memory";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   SPH_TRY(hipMemcpy(x.get(), ctx->tr_xi[ctx->tr_cur], sizeof(float4) * (size_t)total, hipMemcpyDeviceToHost));
+   SPH_TRY(hipMemcpy(c.get(), ctx->tr_cnt[ctx->tr_cur], sizeof(int2) * (size_t)total, hipMemcpyDeviceToHost));
+   // slots -> the caller's rows: by id
+   for (int s = 0; s < total; s++) {
+      uint32_t id;
+      memcpy(&id, &x[s].w, sizeof(id));
+      if (id < (uint32_t)first || id >= (uint32_t)(first + n)) continue;
+      const size_t o = (size_t)id - (size_t)first;
+      if (xyz) {
+         xyz[3 * o + 0] = x[s].x;
+         xyz[3 * o + 1] = x[s].y;
+         xyz[3 * o + 2] = x[s].z;
+      }
+      if (wet_steps) wet_steps[o] = c[s].x;
+      if (dry_steps) dry_steps[o] = c[s].y;
+   }
+   return SPH_HIP_OK;
+}
+
+int sph_hip_record_tracers(sph_hip_context* ctx, int rows, int every)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = tracer_record_check(rows, every, ctx->n_tracers)) return refuse(ctx, "sph_hip_record_tracers", why);
+   DevBuf<float> fresh;
+   const size_t words = (size_t)rows * 3 * (size_t)ctx->n_tracers;
+   if (words > 0 && dev_alloc(fresh, words) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "sph_hip_record_tracers: cannot allocate " + std::to_string(rows) + " rows";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   // steps already queued may still be writing the rows this call replaces
+   if (ctx->trec_dev) SPH_TRY(hipStreamSynchronize(ctx->stream));
+   stop_tracer_recording(ctx);
+   if (words > 0) {
+      ctx->trec_dev = std::move(fresh);
+      ctx->trec_rows = rows;
+      ctx->trec_every = every;
+   }
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_tracer_path(sph_hip_context* ctx, int first_row, int n_rows, float* xyz, int32_t* step_index)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = tracer_range_check(first_row, n_rows, ctx->trec_filled))
+      return refuse(ctx, "sph_hip_get_tracer_path", why);
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   const size_t row = 3 * (size_t)ctx->n_tracers;
+   if (xyz && n_rows > 0)
+      SPH_TRY(hipMemcpy(xyz, ctx->trec_dev.get() + (size_t)first_row * row, sizeof(float) * row * (size_t)n_rows,
+                        hipMemcpyDeviceToHost));
+   for (int r = 0; step_index && r < n_rows; r++) step_index[r] = tracer_record_step(first_row + r, ctx->trec_every);
+   return ctx->trec_filled;
 }
 
 // ---- static obstacles (obstacle_policy.h; routes: launch_policy.h fuse_integrate / fuse_slab_step) ----

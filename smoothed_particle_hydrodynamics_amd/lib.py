@@ -132,6 +132,11 @@ PROTOTYPES = {
     "sph_hip_get_bodies": (C.c_int, [_ctx, _P(SphBody), _P(SphBodyState), C.c_int]),
     "sph_hip_record_loads": (C.c_int, [_ctx, C.c_int, C.c_int]),
     "sph_hip_get_loads": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "sph_hip_set_tracers": (C.c_int, [_ctx, C.c_int, C.c_void_p]),
+    "sph_hip_get_tracers": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_tracer_count": (C.c_int, [_ctx]),
+    "sph_hip_record_tracers": (C.c_int, [_ctx, C.c_int, C.c_int]),
+    "sph_hip_get_tracer_path": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -253,6 +258,14 @@ class Loads:
 # sph_hip_get_bodies' answer: bodies [Body or None per obstacle], displacement and velocity float32 (n, 3),
 # skipped and steps int64 (n,); n = 0 when no bodies are set
 Bodies = collections.namedtuple("Bodies", ["bodies", "displacement", "velocity", "skipped", "steps"])
+
+
+# sph_hip_get_tracers' answer, in the order given to set_tracers: position float32 (n, 3), wet_steps and
+# dry_steps int32 (n,)
+Tracers = collections.namedtuple("Tracers", ["position", "wet_steps", "dry_steps"])
+# sph_hip_get_tracer_path's answer: steps int32 (rows,), the step numbers since record_tracers; positions
+# float32 (rows, n, 3) by tracer id
+TracerPath = collections.namedtuple("TracerPath", ["steps", "positions"])
 
 
 class Context:

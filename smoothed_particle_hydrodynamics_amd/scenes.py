@@ -235,3 +235,38 @@ def dam_break_debris(n, size=(0.12, 0.12, 0.3), gap=3.0, density_ratio=6.0, surg
                 travel_hi=(travel, 0.0, 0.0))
     pos, vel, mass = carve(pos, vel, mass, [debris])
     return p, pos, vel, mass, [debris], [body]
+
+
+def tracer_lattice(lo, hi, spacing):
+    """Tracer start points on the lattice lo + i * spacing per axis (fp32, unfused, x fastest), every i with
+    lo + i * spacing <= hi: (n, 3) float32.  `spacing` is one value or one per axis."""
+    f = np.float32
+    lo = np.asarray(lo, f).reshape(3)
+    hi = np.asarray(hi, f).reshape(3)
+    sp = np.broadcast_to(np.asarray(spacing, f), (3,))
+    if not (sp > 0).all():
+        raise ValueError("spacing must be positive")
+    ax = []
+    for a in range(3):
+        m = max(0, int(math.floor((float(hi[a]) - float(lo[a])) / float(sp[a]))) + 2)
+        x = lo[a] + np.arange(m, dtype=np.int64).astype(f) * sp[a]
+        ax.append(x[x <= hi[a]])
+    z, y, x = np.meshgrid(ax[2], ax[1], ax[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x, y, z], -1).astype(f).reshape(-1, 3))
+
+
+def dam_break_dye(n, spacing=1.0, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42,
+                  gravity=-9.81):
+    """The breaking dam of dam_break_pillar without the pillar - gravity along -y, the walls on, the surge
+    along +x - with dye through the column: a lattice of tracers `spacing` kernel radii apart, half a spacing
+    inside the column's faces.  Returns (params, pos, vel, mass, tracers[m, 3]): setParticles, then
+    setTracers."""
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    vel.reshape(-1, 3)[:, 0] = np.float32(surge)
+    s = float(spacing) * float(p.h)
+    top = [box[c] * fill[c] for c in range(3)]
+    tracers = tracer_lattice([0.5 * s] * 3, [t - 0.5 * s for t in top], s)
+    return p, pos, vel, mass, tracers

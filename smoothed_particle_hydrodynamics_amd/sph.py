@@ -15,9 +15,9 @@ import zlib
 import numpy as np
 
 from . import obstacles as _O
-from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, _ptr, default_params
+from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, TracerPath, Tracers, _ptr, default_params
 
-__all__ = ["SPH", "Particle", "SurfaceMesh", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
+__all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
 
 class Particle:
@@ -248,6 +248,43 @@ class SPH(Context):
                       np.array([list(st[i].velocity) for i in range(n)], np.float32).reshape(n, 3),
                       np.array([st[i].skipped for i in range(n)], np.int64),
                       np.array([st[i].steps for i in range(n)], np.int64))
+
+    # ---- tracers (sph_hip_set_tracers) ------------------------------------------------------------
+    def setTracers(self, points):
+        """Replace the tracers with markers at `points` ((n, 3) float32; an empty list clears them): massless
+        points that every step from here on advances on the device by the midpoint rule in the fluid's
+        Shepard velocity (include/sph_hip.h: tracers).  Counts start at zero; a recording ends."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        self.call("sph_hip_set_tracers", pts.shape[0], _ptr(pts))
+
+    def tracerCount(self):
+        return self.call("sph_hip_tracer_count")
+
+    def getTracers(self):
+        """The tracers after every step enqueued so far, in the order given to setTracers, as a Tracers
+        (sph_hip_get_tracers; synchronises)."""
+        n = self.tracerCount()
+        pos = np.zeros((n, 3), np.float32)
+        wet = np.zeros(n, np.int32)
+        dry = np.zeros(n, np.int32)
+        self.call("sph_hip_get_tracers", 0, n, _ptr(pos), _ptr(wet), _ptr(dry))
+        return Tracers(pos, wet, dry)
+
+    def recordTracers(self, rows, every=1):
+        """Keep the tracers' positions after the next step and every `every`-th after it, `rows` times, on
+        the device (sph_hip_record_tracers); rows = 0 stops and frees the recording."""
+        self.call("sph_hip_record_tracers", int(rows), int(every))
+
+    def getTracerPath(self):
+        """The rows recorded so far, as a TracerPath: steps[rows] (numbered from recordTracers, the first
+        step is 1) and positions[rows, n, 3] (sph_hip_get_tracer_path; synchronises)."""
+        rows = self.call("sph_hip_get_tracer_path", 0, 0, None, None)
+        n = self.tracerCount()
+        steps = np.zeros(rows, np.int32)
+        pos = np.zeros((rows, n, 3), np.float32)
+        if rows:
+            self.call("sph_hip_get_tracer_path", 0, rows, _ptr(pos), _ptr(steps))
+        return TracerPath(steps, pos)
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
