@@ -669,6 +669,93 @@ int sph_hip_tracer_count(const sph_hip_context* ctx);
 int sph_hip_record_tracers(sph_hip_context* ctx, int rows, int every);
 int sph_hip_get_tracer_path(sph_hip_context* ctx, int first_row, int n_rows, float* xyz, int32_t* step_index);
 
+/* ---- gauges ---------------------------------------------------------------------------------- *
+ *
+ * Fixed instruments that read the field inside the step: the water level at a station, the velocity at a
+ * point, the discharge through an opening - the time series a dam-break experiment publishes - without a
+ * host that samples once per step and drains the queue.  A gauge lives in the context; one wave of 64
+ * lanes evaluates its probe points on the device and reduces them to one reading, and a recording keeps
+ * one device row of readings per recorded step.  No counterpart in the reference.  The operation-by-
+ * operation contract is in csrc/gauge_policy.h; all arithmetic is fp32, unfused, in the order written.
+ * walk(S, p) is the field sampler's walk at p over the state S: the raw sums rho, vx, vy, vz (each member's
+ * term t_j and t_j * v_j, in canonical order) and the member count, before any normalisation.
+ *   kinds      POINT    one probe at origin.  v = {rho, ux, uy, uz} with the sampler's normalisation
+ *                       (rho > 0 ? vx / rho : 0), n = count, k = 0: sph_hip_sample_points there, bit for bit.
+ *              COLUMN   count[0] = m probes up `axis` from the base: probe k is the origin with coordinate
+ *                       `axis` replaced by p_k = origin[axis] + (float)k * spacing[0].  A probe is wet when
+ *                       rho > iso (strictly; NaN is dry).  n = the wet probes, k = the largest wet index or
+ *                       -1, v[1] = (float)n * spacing[0] (the wet depth), v[0] the level:
+ *                         k == -1:    v[0] = origin[axis], v[2] = 0, v[3] = rho_0
+ *                         k == m - 1: v[0] = p_k, v[2] = rho_k, v[3] = 0
+ *                         otherwise   fa = rho_k, fb = rho_(k+1), t = (iso - fa) / (fb - fa) clamped to
+ *                                     [0, 1] by fminf(fmaxf(t, 0), 1) (NaN becomes 0, the extractor's rule),
+ *                                     v[0] = p_k + t * (p_(k+1) - p_k), v[2] = fa, v[3] = fb
+ *              SECTION  count = {nu, nv} probes on the rectangle with normal `axis` through origin: probe
+ *                       q = j * nu + i has the first other axis (ascending axis order) at origin[u] +
+ *                       (float)i * spacing[0] and the second at origin[v] + (float)j * spacing[1].  Lane l of
+ *                       the wave takes the probes l, l + 64, ... in order into two accumulators that start
+ *                       at 0.0f: a = a + (the raw velocity sum of the normal axis, the momentum density
+ *                       sum of t_j v_j), r = r + rho; the 64 lane values are summed by the butterfly
+ *                       x = x + x[lane ^ d], d = 1, 2, 4, 8, 16, 32.  area = spacing[0] * spacing[1];
+ *                       v = {a_sum * area (the mass flow along the normal), (float)n * area (the wetted
+ *                       area), r_sum, 0}, n = the wet probes, k = 0.
+ *   contexts   FULL and FULL_FAST contexts that hold the whole grid, with the sampler's refusals for REF
+ *              and slab contexts.  With no particle resident every walk gives zeros: columns are dry.
+ *   when       while a recording is set, step k evaluates the gauges once, after that step's cell build and
+ *              before anything moves the particles, in the state S_k the sampler would see.  Gauges read
+ *              positions, masses and velocities only and write nothing a particle kernel reads: every
+ *              particle, density, acceleration and energy is bit-identical to a run without gauges.
+ *              sph_hip_step, sph_hip_run and the phase calls give the same bits: the stand-alone
+ *              sph_hip_integrate reads the gauges first, after bringing the cell structure up to date as
+ *              the sampler does.  With no recording a step launches nothing for gauges.
+ *   not done   slab contexts and REF mode are refused; there is no pressure reading; gauges do not move with
+ *              an obstacle or a body, and solids do not shade a probe.
+ * sph_hip_set_gauges replaces the set (n = 0 clears it), ends a recording and waits for the steps already
+ * queued.  SPH_HIP_ERR_INVALID, the previous set and recording kept, for a REF or slab context, n < 0,
+ * n > SPH_HIP_MAX_GAUGES, a null list with n > 0, an unknown kind, an axis outside 0..2, any float field
+ * that is not finite (unused fields included), a used spacing that is not > 0, a used count < 1, more than
+ * SPH_HIP_MAX_GAUGE_PROBES probes in one gauge, and an iso that is not > 0 for COLUMN and SECTION.  The
+ * set survives sph_hip_upload, sph_hip_set_params and sph_hip_set_arithmetic, and a recording goes on
+ * across them.
+ * sph_hip_get_gauges copies up to `capacity` gauges and returns how many are set.
+ * sph_hip_read_gauges evaluates the gauges now, in the current state, into out[count]: the sampler's kind
+ * of call - it brings the cell structure up to date, synchronises and changes nothing a caller can read or
+ * a later step computes.  With no gauges set it does nothing.
+ * sph_hip_record_gauges keeps `rows` rows of readings on the device: steps are numbered 1, 2, ... from this
+ * call, and step s fills row (s - 1) / every when every divides s - 1 and that row exists.  Row r is the
+ * state after r * every steps; row 0 is the state at the call.  rows = 0 stops and frees the recording.
+ * SPH_HIP_ERR_INVALID, the previous recording kept, for rows < 0, every < 1, rows * gauges * 24 bytes above
+ * the 64 MiB scratch budget of the sampler and the extractor, and rows > 0 with no gauges set.
+ * sph_hip_get_gauge_record synchronises, copies rows [first_row, first_row + n_rows) of the rows filled so
+ * far - out[n_rows][gauges], steps_done[n_rows] = row * every; either may be NULL - and returns how many
+ * rows are filled (n_rows = 0 asks just that).  SPH_HIP_ERR_INVALID for a range that leaves the filled rows.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no struct and no existing
+ * prototype changed. */
+#define SPH_HIP_GAUGE_POINT   0
+#define SPH_HIP_GAUGE_COLUMN  1
+#define SPH_HIP_GAUGE_SECTION 2
+#define SPH_HIP_MAX_GAUGES        4096
+#define SPH_HIP_MAX_GAUGE_PROBES  4096
+typedef struct sph_hip_gauge {      /* field order is ABI: 40 bytes */
+   int32_t kind;
+   int32_t axis;        /* COLUMN: the axis it climbs; SECTION: its normal; POINT: 0 */
+   float origin[3];     /* POINT: the point; COLUMN: the base; SECTION: the corner, origin[axis] = the plane */
+   float spacing[2];    /* COLUMN: [0]; SECTION: along the two other axes, ascending axis order */
+   int32_t count[2];    /* COLUMN: count[0] = m; SECTION: nu, nv */
+   float iso;           /* COLUMN, SECTION: a probe is wet when rho > iso (strictly; NaN is dry) */
+} sph_hip_gauge;
+typedef struct sph_hip_gauge_reading {   /* 24 bytes */
+   float v[4];
+   int32_t n;
+   int32_t k;
+} sph_hip_gauge_reading;
+int sph_hip_set_gauges(sph_hip_context* ctx, const sph_hip_gauge* list, int n);
+int sph_hip_get_gauges(sph_hip_context* ctx, sph_hip_gauge* out, int capacity);
+int sph_hip_read_gauges(sph_hip_context* ctx, sph_hip_gauge_reading* out);
+int sph_hip_record_gauges(sph_hip_context* ctx, int rows, int every);
+int sph_hip_get_gauge_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_gauge_reading* out,
+                             int32_t* steps_done);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -9,4 +9,5 @@ from .sph import SPH, Particle, SurfaceMesh, write_ply, Camera, RenderResult, wr
 from .lib import TIMING_OFF, TIMING_SUMS, TIMING_PHASES  # noqa: F401
 from .lib import Loads, LOAD_SOLIDS  # noqa: F401
 from .lib import Tracers, TracerPath  # noqa: F401
-from . import obstacles, scenes  # noqa: F401
+from .gauges import PointGauge, ColumnGauge, SectionGauge, GaugeReadings, GaugeRecord  # noqa: F401
+from . import gauges, obstacles, scenes  # noqa: F401

@@ -15,6 +15,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "context.h", "launch.h", "slab_comm.h", "sample_kernels.h", "sample_policy.h",
            "surface_kernels.h", "surface_policy.h", "render_kernels.h", "render_policy.h", "obstacle_policy.h",
            "load_policy.h", "body_policy.h", "tracer_kernels.h", "tracer_policy.h",
+           "gauge_kernels.h", "gauge_policy.h",
            os.path.join("..", "..", "include", "sph_hip.h")]
 
 # -ffp-contract=off: the reference's x86-64 IEEE build has no FMA contraction; neighbour

@@ -21,6 +21,7 @@
 #include "surface_kernels.h"
 #include "render_kernels.h"
 #include "tracer_kernels.h"
+#include "gauge_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
 
@@ -359,6 +360,18 @@ struct sph_hip_context {
    DevBuf<float> trec_dev;
    int trec_rows = 0, trec_every = 1, trec_filled = 0;
    long long trec_step = 0;
+
+   // gauges (sph_hip_set_gauges): the descriptors as given (gauges_host) and on the device, and the row
+   // sph_hip_read_gauges evaluates into
+   int n_gauges = 0;
+   std::unique_ptr<sph_hip_gauge[]> gauges_host;
+   DevBuf<sph_hip_gauge> gauges_dev;
+   DevBuf<sph_hip_gauge_reading> gauge_now;
+   // recording (sph_hip_record_gauges): grec_rows rows of one reading per gauge; grec_step = steps enqueued
+   // since the call, grec_filled = rows those steps have filled
+   DevBuf<sph_hip_gauge_reading> grec_dev;
+   int grec_rows = 0, grec_every = 1, grec_filled = 0;
+   long long grec_step = 0;
 };
 
 namespace {

@@ -668,6 +668,33 @@ int launch_tracers(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- gauges (gauge_kernels.h; decisions: gauge_policy.h) -------------------------------------------------
+// Every gauge evaluated once in the sorted state a cell build has just produced, into `row` (one reading per
+// gauge).  Nothing here synchronises.
+int launch_gauges_into(sph_hip_context* ctx, sph_hip_gauge_reading* row)
+{
+   const int n = ctx->n_gauges;
+   const sph_hip_params& p = ctx->prm;
+   const PairConsts k = pair_consts(p, ctx->fast != 0);
+   bind_flags([&](auto U) {
+      hipLaunchKernelGGL((k_gauges_read<U.value>), dim3(div_up(n, GAUGES_PER_BLOCK)), dim3(256), 0, ctx->stream,
+                         ctx->gauges_dev, n, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid, k,
+                         ctx->n > 0 ? 1 : 0, row);
+   }, unit_scale(p));
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// One step of a gauge recording: the step is counted, and where it fills a row the gauges are read into it.
+int launch_gauges(sph_hip_context* ctx)
+{
+   if (ctx->grec_rows == 0) return SPH_HIP_OK;
+   const int r = gauge_record_row(++ctx->grec_step, ctx->grec_every, ctx->grec_rows);
+   if (r < 0) return SPH_HIP_OK;
+   ctx->grec_filled = r + 1;
+   return launch_gauges_into(ctx, ctx->grec_dev.get() + (size_t)r * (size_t)ctx->n_gauges);
+}
+
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
 // buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
 // (prehashed: 1 whole grid, 2 a slab's owned entries).
@@ -745,6 +772,7 @@ int step_impl(sph_hip_context* ctx, bool timed)
    if ((rc = mark_phase(ctx, se, 0, st))) return rc;
    if ((rc = launch_cell_build(ctx))) return rc;
    if (ctx->n_tracers > 0 && (rc = launch_tracers(ctx))) return rc;   // in S_k, before anything moves
+   if (ctx->grec_rows > 0 && (rc = launch_gauges(ctx))) return rc;    // likewise
    if ((rc = mark_phase(ctx, se, 1, st))) return rc;
    if ((rc = launch_find_neighbors(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 2, st))) return rc;

@@ -797,9 +797,11 @@ int sph_hip_integrate(sph_hip_context* ctx)
    if (rc) return rc;
    // tracers advance first, in the state the integrate is about to move: the cell structure is brought up to
    // date the way the sampler does it (the build consumes a pending prehash and moves the sums along)
-   if (ctx->n_tracers > 0) {
+   // and a gauge recording reads the same state behind the same build
+   if (ctx->n_tracers > 0 || ctx->grec_rows > 0) {
       if (ctx->n > 0 && (rc = sample_prepare(ctx))) return rc;
-      if ((rc = launch_tracers(ctx))) return rc;
+      if (ctx->n_tracers > 0 && (rc = launch_tracers(ctx))) return rc;
+      if (ctx->grec_rows > 0 && (rc = launch_gauges(ctx))) return rc;
    }
    if ((rc = drop_prehash(ctx))) return rc;   // the state moves on without a new hash
    return launch_integrate(ctx);
@@ -943,6 +945,112 @@ int sph_hip_get_tracer_path(sph_hip_context* ctx, int first_row, int n_rows, flo
                         hipMemcpyDeviceToHost));
    for (int r = 0; step_index && r < n_rows; r++) step_index[r] = tracer_record_step(first_row + r, ctx->trec_every);
    return ctx->trec_filled;
+}
+
+// ---- gauges (gauge_kernels.h; contract and decisions: gauge_policy.h) --------------------------------
+
+namespace {
+void stop_gauge_recording(sph_hip_context* ctx)
+{
+   ctx->grec_dev.reset();
+   ctx->grec_rows = ctx->grec_filled = 0;
+   ctx->grec_every = 1;
+   ctx->grec_step = 0;
+}
+} // namespace
+
+int sph_hip_set_gauges(sph_hip_context* ctx, const sph_hip_gauge* list, int n)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if ((rc = sample_check(ctx, "sph_hip_set_gauges"))) return rc;
+   if (const char* why = gauge_check(list, n)) return refuse(ctx, "sph_hip_set_gauges", why);
+   // the new set's arrays first: a failure keeps the old set
+   std::unique_ptr<sph_hip_gauge[]> host;
+   DevBuf<sph_hip_gauge> dev;
+   DevBuf<sph_hip_gauge_reading> now;
+   if (n > 0) {
+      host.reset(new (std::nothrow) sph_hip_gauge[(size_t)n]);
+      if (!host || dev_alloc(dev, (size_t)n) != hipSuccess || dev_alloc(now, (size_t)n) != hipSuccess) {
+         (void)hipGetLastError();
+         ctx->err = "sph_hip_set_gauges: cannot allocate " + std::to_string(n) + " gauges";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      memcpy(host.get(), list, sizeof(sph_hip_gauge) * (size_t)n);
+   }
+   // steps already queued read the old set: wait for them before it goes
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (n > 0) SPH_TRY(hipMemcpy(dev, host.get(), sizeof(sph_hip_gauge) * (size_t)n, hipMemcpyHostToDevice));
+   ctx->gauges_host = std::move(host);
+   ctx->gauges_dev = std::move(dev);
+   ctx->gauge_now = std::move(now);
+   ctx->n_gauges = n;
+   stop_gauge_recording(ctx);
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_gauges(sph_hip_context* ctx, sph_hip_gauge* out, int capacity)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (capacity < 0 || (capacity > 0 && !out)) return refuse(ctx, "sph_hip_get_gauges", "negative capacity or null array");
+   const int m = ctx->n_gauges < capacity ? ctx->n_gauges : capacity;
+   if (m > 0) memcpy(out, ctx->gauges_host.get(), sizeof(sph_hip_gauge) * (size_t)m);
+   return ctx->n_gauges;
+}
+
+int sph_hip_read_gauges(sph_hip_context* ctx, sph_hip_gauge_reading* out)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const int n = ctx->n_gauges;
+   if (n == 0) return SPH_HIP_OK;
+   if (!out) return refuse(ctx, "sph_hip_read_gauges", "null output array");
+   if (ctx->n > 0 && (rc = sample_prepare(ctx))) return rc;
+   if ((rc = launch_gauges_into(ctx, ctx->gauge_now))) return rc;
+   SPH_TRY(hipMemcpyAsync(out, ctx->gauge_now, sizeof(sph_hip_gauge_reading) * (size_t)n, hipMemcpyDeviceToHost,
+                          ctx->stream));
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   return SPH_HIP_OK;
+}
+
+int sph_hip_record_gauges(sph_hip_context* ctx, int rows, int every)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = gauge_record_check(rows, every, ctx->n_gauges)) return refuse(ctx, "sph_hip_record_gauges", why);
+   DevBuf<sph_hip_gauge_reading> fresh;
+   const size_t cells = (size_t)rows * (size_t)ctx->n_gauges;
+   if (cells > 0 && dev_alloc(fresh, cells) != hipSuccess) {
+      (void)hipGetLastError();
+      ctx->err = "sph_hip_record_gauges: cannot allocate " + std::to_string(rows) + " rows";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   // steps already queued may still be writing the rows this call replaces
+   if (ctx->grec_dev) SPH_TRY(hipStreamSynchronize(ctx->stream));
+   stop_gauge_recording(ctx);
+   if (cells > 0) {
+      ctx->grec_dev = std::move(fresh);
+      ctx->grec_rows = rows;
+      ctx->grec_every = every;
+   }
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_gauge_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_gauge_reading* out,
+                             int32_t* steps_done)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = gauge_range_check(first_row, n_rows, ctx->grec_filled))
+      return refuse(ctx, "sph_hip_get_gauge_record", why);
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   const size_t row = (size_t)ctx->n_gauges;
+   if (out && n_rows > 0)
+      SPH_TRY(hipMemcpy(out, ctx->grec_dev.get() + (size_t)first_row * row,
+                        sizeof(sph_hip_gauge_reading) * row * (size_t)n_rows, hipMemcpyDeviceToHost));
+   for (int r = 0; steps_done && r < n_rows; r++) steps_done[r] = gauge_record_steps_done(first_row + r, ctx->grec_every);
+   return ctx->grec_filled;
 }
 
 // ---- static obstacles (obstacle_policy.h; routes: launch_policy.h fuse_integrate / fuse_slab_step) ----

@@ -75,6 +75,7 @@ class SphRenderParams(C.Structure):
 
 from . import obstacles as _obstacles  # noqa: E402
 from .obstacles import SphBody, SphBodyState, SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of the C structs)
+from .gauges import GaugeReadings, GaugeRecord, SphGauge  # noqa: E402,F401
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -137,6 +138,11 @@ PROTOTYPES = {
     "sph_hip_tracer_count": (C.c_int, [_ctx]),
     "sph_hip_record_tracers": (C.c_int, [_ctx, C.c_int, C.c_int]),
     "sph_hip_get_tracer_path": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sph_hip_set_gauges": (C.c_int, [_ctx, _P(SphGauge), C.c_int]),
+    "sph_hip_get_gauges": (C.c_int, [_ctx, _P(SphGauge), C.c_int]),
+    "sph_hip_read_gauges": (C.c_int, [_ctx, C.c_void_p]),
+    "sph_hip_record_gauges": (C.c_int, [_ctx, C.c_int, C.c_int]),
+    "sph_hip_get_gauge_record": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -270,3 +270,34 @@ def dam_break_dye(n, spacing=1.0, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.7
     top = [box[c] * fill[c] for c in range(3)]
     tracers = tracer_lattice([0.5 * s] * 3, [t - 0.5 * s for t in top], s)
     return p, pos, vel, mass, tracers
+
+
+def dam_break_gauged(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42, gravity=-9.81):
+    """The surging dam of dam_break_dye without the dye, with the instruments of a dam-break experiment: four
+    column gauges up y at x = 0.05, 0.3, 0.6 and 0.9 of the box on the mid-plane in z, h/2 between probes from
+    the floor to the lid; one section across the box at x = 0.2 (normal x, h/2 between probes); one point probe
+    at mid-height of the column, at its centre.  iso is half the sampler's density deep inside the column - the
+    number density times the integral of the kernel over its support, kernel1 * sim_scale^6 * h^9 * 64 pi / 315 -
+    and does not involve rho0.  Returns (params, pos, vel, mass, gauges): setParticles, then setGauges."""
+    from .gauges import ColumnGauge, PointGauge, SectionGauge
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    vel.reshape(-1, 3)[:, 0] = np.float32(surge)
+    h = float(p.h)
+    column = [box[c] * fill[c] for c in range(3)]
+    bulk = n / (column[0] * column[1] * column[2]) * float(p.kernel1) * float(p.sim_scale) ** 6 * h ** 9 * 64.0 * math.pi / 315.0
+    iso = 0.5 * bulk
+    s = 0.5 * h
+    up = min(int(math.floor(box[1] / s)) + 1, 4096)
+    gauges = [ColumnGauge((f * box[0], 0.0, 0.5 * box[2]), 1, s, up, iso) for f in (0.05, 0.3, 0.6, 0.9)]
+    nu = int(math.floor(box[1] / s)) + 1
+    nv = int(math.floor(box[2] / s)) + 1
+    while nu * nv > 4096:   # (a finer h than a section's probe limit allows: a coarser lattice over the same rectangle)
+        s *= 2.0
+        nu = int(math.floor(box[1] / s)) + 1
+        nv = int(math.floor(box[2] / s)) + 1
+    gauges.append(SectionGauge((0.2 * box[0], 0.0, 0.0), 0, (s, s), (nu, nv), iso))
+    gauges.append(PointGauge((0.5 * column[0], 0.5 * column[1], 0.5 * column[2])))
+    return p, pos, vel, mass, gauges

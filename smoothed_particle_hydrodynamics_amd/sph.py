@@ -14,6 +14,7 @@ import zlib
 
 import numpy as np
 
+from . import gauges as _G
 from . import obstacles as _O
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, TracerPath, Tracers, _ptr, default_params
 
@@ -285,6 +286,48 @@ class SPH(Context):
         if rows:
             self.call("sph_hip_get_tracer_path", 0, rows, _ptr(pos), _ptr(steps))
         return TracerPath(steps, pos)
+
+    # ---- gauges (sph_hip_set_gauges) -------------------------------------------------------------
+    def setGauges(self, gauges):
+        """Replace the gauges with `gauges` (gauges.PointGauge / ColumnGauge / SectionGauge; an empty list clears
+        them): fixed instruments evaluated on the device (include/sph_hip.h: gauges).  A recording ends."""
+        arr, n = _G.as_array(gauges)
+        self.call("sph_hip_set_gauges", arr, n)
+
+    def getGauges(self):
+        """The gauges as they were set, in list order."""
+        n = self.call("sph_hip_get_gauges", None, 0)
+        if n == 0:
+            return []
+        arr = (_G.SphGauge * n)()
+        self.call("sph_hip_get_gauges", arr, n)
+        return [_G.from_struct(arr[i]) for i in range(n)]
+
+    def readGauges(self):
+        """Every gauge evaluated now, in the current state, as a GaugeReadings (sph_hip_read_gauges; synchronises;
+        the simulation is not changed by the call)."""
+        n = self.call("sph_hip_get_gauges", None, 0)
+        out = np.zeros(n, _G.READING)
+        if n:
+            self.call("sph_hip_read_gauges", _ptr(out))
+        return _G.GaugeReadings(out["v"].copy(), out["n"].copy(), out["k"].copy())
+
+    def recordGauges(self, rows, every=1):
+        """Keep the gauges' readings in the state at this call and after every `every`-th step from it, `rows`
+        times, on the device (sph_hip_record_gauges); rows = 0 stops and frees the recording."""
+        self.call("sph_hip_record_gauges", int(rows), int(every))
+
+    def getGaugeRecord(self):
+        """The rows recorded so far, as a GaugeRecord: steps[rows] (the steps completed since recordGauges when
+        the row was read) and the readings v[rows, n, 4], n[rows, n], k[rows, n] (sph_hip_get_gauge_record;
+        synchronises)."""
+        rows = self.call("sph_hip_get_gauge_record", 0, 0, None, None)
+        n = self.call("sph_hip_get_gauges", None, 0)
+        steps = np.zeros(rows, np.int32)
+        out = np.zeros((rows, n), _G.READING)
+        if rows:
+            self.call("sph_hip_get_gauge_record", 0, rows, _ptr(out), _ptr(steps))
+        return _G.GaugeRecord(steps, out["v"].copy(), out["n"].copy(), out["k"].copy())
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
