@@ -248,13 +248,16 @@ void oracle_find_neighbors(const sph_oracle_params* p, int n, const float* pos,
 /* A3 — reference src/sph.cpp:204-232: integer-division average, max from -1, min from 34 */
 void oracle_neighbor_stats(int n, const int32_t* counts, int32_t* avg, int32_t* mx, int32_t* mn)
 {
-   int sum = 0, hi = -1, lo = 34;
+   /* the reference adds into an int (src/sph.cpp:204): exact while the sum stays below 2^31, which its
+    * own counts (at most examine_count each) always do; complete neighbourhoods need 64 bits */
+   long long sum = 0;
+   int hi = -1, lo = 34;
    for (int i = 0; i < n; i++) {
       sum += counts[i];
       if (counts[i] > hi) hi = counts[i];
       if (counts[i] < lo) lo = counts[i];
    }
-   *avg = sum / n;
+   *avg = (int32_t)(sum / n);
    *mx = hi;
    *mn = lo;
 }

@@ -206,3 +206,45 @@ def nonfinite_scene(case, params_for_h=None):
     else:
         raise ValueError(case)
     return p, np.ascontiguousarray(pos.reshape(-1)), vel, mass
+
+
+READBACK_COUNTS = (1, 255, 256, 257, 6000)
+READBACK_NONFINITE_ROWS = (10, 20, 30, 40, 50)
+
+
+def readback_scene(n=6000, params_for_h=None):
+    """The first n rows of the scene the read-back tests share (test_readback_cpu.py,
+    test_gpu_readback.py): h = 0.1 on a 5 x 9 x 17 voxel grid (FULL grid 10 x 18 x 34: three distinct
+    extents on both grids, so an index formula with two axes swapped cannot pass), no point mass, unit
+    masses.  6000 positions uniform in [-0.3, 1.3) x the box's extent per axis - about three quarters lie
+    outside the box and are clamped into its edge cells -, rows 100-399 snapped onto REF voxel faces, and
+    the five non-finite rows of nonfinite_scene("particles"); velocities uniform in [-1, 1).  Rows that a
+    smaller n does not have are simply missing.  params_for_h as in nonfinite_scene."""
+    from smoothed_particle_hydrodynamics_amd import scenes
+    total = READBACK_COUNTS[-1]
+    cells = (5, 9, 17)
+    p = (params_for_h or scenes.default_params)(0.1, cells)
+    p.central_mass = 0.0
+    ext = np.float32(cells) * np.float32(p.htimes2)
+    pos = scenes.box_fill(total, tuple(np.float32(-0.3) * ext), tuple(np.float32(1.3) * ext), 61).reshape(-1, 3)
+    edge = np.float32(1.0) / np.float32(p.htimes2inv)
+    pos[100:400] = edge * np.round(pos[100:400] / edge)
+    pos[10, 0] = np.inf
+    pos[20, 1] = -np.inf
+    pos[30, 2] = np.inf
+    pos[40, 0] = np.nan
+    pos[50] = np.nan
+    vel = scenes.box_fill(total, (-1.0,) * 3, (1.0,) * 3, 62)
+    return (p, np.ascontiguousarray(pos[:n].reshape(-1)), np.ascontiguousarray(vel[:3 * n]),
+            np.ones(n, np.float32))
+
+
+def grid_occupancy(pos, inv, cells):
+    """Per-cell occupancy of a cells = (nx, ny, nz) grid with cell edge 1 / inv, restated in numpy: a
+    bincount of (cz * ny + cy) * nx + cx with sample_emulation.cell_coord (csrc/sph_device.h
+    cell_coord) per axis.  Returns (ids per particle, counts per cell)."""
+    from sample_emulation import cell_coord
+    pos = np.asarray(pos, np.float32).reshape(-1, 3)
+    c = [cell_coord(pos[:, a], inv, cells[a]) for a in range(3)]
+    ids = (c[2] * cells[1] + c[1]) * cells[0] + c[0]
+    return ids, np.bincount(ids, minlength=cells[0] * cells[1] * cells[2]).astype(np.int32)
