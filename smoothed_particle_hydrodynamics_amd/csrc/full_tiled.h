@@ -1277,12 +1277,47 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
    uint32_t entry[LIST_BLOCK_ENTRIES];
    uint4 next_blk = lr.block(0);      // (block 0 of every lane exists)
 
-   // the tile: first batch from the registers, then whatever is left
+   // the tile: first batch from the registers, then (below) whatever is left
 #pragma unroll
    for (int r = 0; r < BATCH; r++) {
       const int idx = tid + r * TILE_THREADS;
       if (idx < filled) xyzc[idx] = make_float4(buf[r].x, buf[r].y, buf[r].z, cbuf[r]);
    }
+
+   AccelState s;
+   int first_v = 0;
+   bool no_list = false;
+   // FAST: the viscous sum runs BEFORE the pressure loop (they accumulate into different registers and
+   // meet in accel_end: pair_math.h), and the two dependent round trips of its first trip start in the
+   // prologue: the list blocks that hold its first VISC_UNROLL entries here, behind the tile's first
+   // batch (its registers are free by now: the count returns after it), the {v, C} gathers by those
+   // entries behind the fill's last loads.  At the end of the lane's work the two round trips were 3.8 us
+   // of a 24 us workgroup that nothing could overlap; now the launch is 26 us (9 %) shorter at 4M
+   // (profiles/accel_viscous_first.txt).  The blocks requested are the ones that hold entries first_v ..
+   // first_v + 3 (the list's last two whenever visc_keep() is small, as it is in a fluid under
+   // pressure; any two neighbouring ones of a lane that keeps more), by 16-byte loads; the entries
+   // leave them through selects (list_entries_from), not through a register array indexed per lane.
+   // Nothing of this is live across the pressure loop.
+   float4 vpre[VISC_UNROLL];
+   int tpre[VISC_UNROLL], nvp = 0;
+   uint32_t ev[VISC_UNROLL];
+   if constexpr (FAST) {
+      static_assert(VISC_UNROLL == 4, "list_entries_from takes four entries");
+      accel_begin(k, s, pi, vi, rho_i);
+      first_v = visc_first(cnt, s.visc_scale);
+      // (a particle without a list has more neighbours than the lists hold - the blocks its count
+      // points at do not exist - and the marker in its first word, which travels ahead of these loads)
+      const int lcnt = cnt <= list_cap ? cnt : 0;
+      const int fv = lcnt > 0 ? first_v : 0;                 // (first_v < cnt wherever cnt > 0)
+      const int lb = lcnt > 0 ? (lcnt - 1) >> 3 : 0;
+      const int fb = fv >> 3;
+      const uint4 blk_a = lr.block(fb), blk_b = lr.block(min(fb + 1, lb));
+      if (gave_up == LISTS_SOME && cnt > 0) no_list = next_blk.x == NLIST_NO_LIST;
+      nvp = no_list ? 0 : lcnt - fv;
+      list_entries_from(blk_a, blk_b, (uint32_t)(fv & 7), ev);
+   }
+
+   // the rest of the tile
    for (int base = BATCH * TILE_THREADS; base < filled; base += BATCH * TILE_THREADS) {
 #pragma unroll
       for (int r = 0; r < BATCH; r++) {
@@ -1299,23 +1334,32 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          if (idx < filled) xyzc[idx] = make_float4(buf[r].x, buf[r].y, buf[r].z, cbuf[r]);
       }
    }
+   if constexpr (FAST) {
+      // (issued behind the fill's last loads: 16 registers that, in flight across a batch's 40, did not
+      // fit the budget of ACCEL_BLOCKS workgroups per CU)
+#pragma unroll
+      for (int u = 0; u < VISC_UNROLL; u++) {
+         tpre[u] = ListEntry<WIDE>::tile(ev[u]);
+         vpre[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+         // (only entries of the list itself are gathered by: sorted positions of this step)
+         if (u < nvp) vpre[u] = velB[tpre[u] - ListEntry<WIDE>::shift(L.desc, ev[u])];
+      }
+   }
    __syncthreads();
 
-   PHASE_MARK(17);   // tile, own loads, first list block
-   AccelState s;
-   accel_begin(k, s, pi, vi, rho_i);
+   PHASE_MARK(17);   // tile, own loads, first list block (FAST: first viscous entries, their gathers issued)
+   if constexpr (!FAST) accel_begin(k, s, pi, vi, rho_i);
    // every listed pair passed the exact d2 < h2 test: the division's range checks are uniform
    const bool in_range = accel_operands_in_range(k);
    // a particle without a list (marker in its first word; only in workgroups flagged 2): its lane
    // skips the list loop and walks its candidate ranges in the tile afterwards
-   bool no_list = false;
    // (the marker tested on the block already loaded: ListReader::no_list() loads it again, and a
-   // helper taking the word changed this kernel's code)
-   if (gave_up == LISTS_SOME && cnt > 0) no_list = next_blk.x == NLIST_NO_LIST;
+   // helper taking the word changed this kernel's code; FAST tested it in the prologue)
+   if constexpr (!FAST) {
+      if (gave_up == LISTS_SOME && cnt > 0) no_list = next_blk.x == NLIST_NO_LIST;
+   }
    // FAST: only the last visc_keep() neighbours take part in the viscous sum - and only they are
-   // gathered ({v, C}; what every pair needs, m B, is in the tile)
-   int first_v = 0;
-   if (FAST) first_v = visc_first(cnt, s.visc_scale);
+   // gathered ({v, C}; what every pair needs, m B, is in the tile): first_v, from the full count
    if (no_list) cnt = 0;
 #if defined(SPH_ABLATE) && (SPH_ABLATE == 21 || SPH_ABLATE == 23)
    cnt = 0;   // timing only: prologue and epilogue
@@ -1324,6 +1368,49 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
    // of its last block are zeros - list_pad - because the exact loop gathers by every entry it holds)
    const int lastb = cnt > 0 ? (cnt - 1) >> 3 : 0;
    if constexpr (FAST) {
+      TRIP(TripCounters trips; trips.wave(TRIP_A_WAVES - 16, true); trips.lane(TRIP_A_CNT_L - 16, (unsigned)cnt);
+           trips.lane(TRIP_A_LANES_L - 16, live ? 1u : 0u); trips.lane(TRIP_A_NV_L - 16, (unsigned)(cnt - first_v));)
+      // The viscous sum over the list's last visc_keep() entries (ascending, as everywhere): the
+      // only neighbours whose {v, C} is gathered, with the reference's stored distance.  Its first
+      // trip takes the entries and gathers the prologue requested; the trips after it - a particle
+      // whose pressure is not positive keeps more than VISC_UNROLL neighbours, all of them when
+      // |mu * rhoiInv| >= 1/2 - fetch theirs as they go.
+      const int nv = cnt - first_v;     // (a lane without a list: cnt = 0 by now, no trip)
+      if (__any(0 < nv)) {
+#pragma unroll
+         for (int u = 0; u < VISC_UNROLL; u++) {
+            if (u < nv) {
+               const float4 pj = xyzc[tpre[u]];
+               float dx, dy, dz;
+               float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
+               if (!UNIT_SCALE) d *= k.sim_scale;
+               accel_pair_fast_viscous(k, s, d, vpre[u].x, vpre[u].y, vpre[u].z, vpre[u].w);
+            }
+         }
+      }
+      for (int m0 = VISC_UNROLL; __any(m0 < nv); m0 += VISC_UNROLL) {
+         float4 vj[VISC_UNROLL];
+         int tj[VISC_UNROLL];
+#pragma unroll
+         for (int u = 0; u < VISC_UNROLL; u++) {
+            const int j = min(first_v + m0 + u, cnt > 0 ? cnt - 1 : 0);
+            const uint32_t e = lr.entry((uint32_t)j);
+            tj[u] = ListEntry<WIDE>::tile(e);
+            vj[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (m0 + u < nv) vj[u] = velB[tj[u] - ListEntry<WIDE>::shift(L.desc, e)];
+         }
+#pragma unroll
+         for (int u = 0; u < VISC_UNROLL; u++) {
+            if (m0 + u < nv) {
+               const float4 pj = xyzc[tj[u]];
+               float dx, dy, dz;
+               float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
+               if (!UNIT_SCALE) d *= k.sim_scale;
+               accel_pair_fast_viscous(k, s, d, vj[u].x, vj[u].y, vj[u].z, vj[u].w);
+            }
+         }
+      }
+      PHASE_MARK(18);   // viscous sum
       const int self_tile = live ? p + L.desc.D[4] : 0;   // (the lane's own entry of the tile)
       // The pressure sum over the whole list: everything it needs of a neighbour is in the tile
       // ({x, y, z, m B}), no gather.  The list entries of the NEXT trip are requested before this
@@ -1341,8 +1428,6 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
       const float self_c = (k.hscaled * k.hscaled) * (s.pi_div_rhoi2 * self.w) +
                            ((self.x - self.x) + (self.y - self.y) + (self.z - self.z));
       const bool odd_lane = __any(!__builtin_isfinite(s.pi_div_rhoi2) || !__builtin_isfinite(self_c));
-      TRIP(TripCounters trips; trips.wave(TRIP_A_WAVES - 16, true); trips.lane(TRIP_A_CNT_L - 16, (unsigned)cnt);
-           trips.lane(TRIP_A_LANES_L - 16, live ? 1u : 0u); trips.lane(TRIP_A_NV_L - 16, (unsigned)(cnt - first_v));)
       for (int j0 = 0; __any(j0 < cnt); j0 += LIST_BLOCK_ENTRIES) {
          TRIP(trips.wave(TRIP_A_PTRIPS_W - 16, true);)
          list_block_entries(next_blk, entry);
@@ -1378,34 +1463,8 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          }
 #endif
       }
-      // The viscous sum over the list's last visc_keep() entries (ascending, as everywhere): the
-      // only neighbours whose {v, C} is gathered, with the reference's stored distance.
-      PHASE_MARK(18);   // pressure loop
-      const int nv = cnt - first_v;
       TRIP(for (int m0 = 0; __any(m0 < nv); m0 += VISC_UNROLL) trips.wave(TRIP_A_VTRIPS_W - 16, true);
            trips.flush(16, 1u << (TRIP_A_CNT_L - 16) | 1u << (TRIP_A_NV_L - 16) | 1u << (TRIP_A_LANES_L - 16));)
-      for (int m0 = 0; __any(m0 < nv); m0 += VISC_UNROLL) {
-         float4 vj[VISC_UNROLL];
-         int tj[VISC_UNROLL];
-#pragma unroll
-         for (int u = 0; u < VISC_UNROLL; u++) {
-            const int j = min(first_v + m0 + u, cnt > 0 ? cnt - 1 : 0);
-            const uint32_t e = lr.entry((uint32_t)j);
-            tj[u] = ListEntry<WIDE>::tile(e);
-            vj[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (m0 + u < nv) vj[u] = velB[tj[u] - ListEntry<WIDE>::shift(L.desc, e)];
-         }
-#pragma unroll
-         for (int u = 0; u < VISC_UNROLL; u++) {
-            if (m0 + u < nv) {
-               const float4 pj = xyzc[tj[u]];
-               float dx, dy, dz;
-               float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
-               if (!UNIT_SCALE) d *= k.sim_scale;
-               accel_pair_fast_viscous(k, s, d, vj[u].x, vj[u].y, vj[u].z, vj[u].w);
-            }
-         }
-      }
    } else {
    // LIST_BLOCK_ENTRIES neighbours per trip: their {v,B} gathers are issued back to back before the
    // first pair's arithmetic, and the list entries of the NEXT trip are requested before it too,
@@ -1483,7 +1542,7 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
          }
       }
    }
-   PHASE_MARK(19);   // viscous loop (exact arithmetic: the one pair loop)
+   PHASE_MARK(19);   // pressure loop (exact arithmetic: the one pair loop), particles without a list
    if (FAST) accel_fast_finish(k, s);
    const float4 a_i = accel_end<UNIT_SCALE>(k, s);
    if (live) acc[p] = a_i;

@@ -75,6 +75,22 @@ __device__ __forceinline__ void list_block_entries(const uint4& blk, uint32_t (&
    entry[4] = blk.z & 0xffffu; entry[5] = blk.z >> 16;
    entry[6] = blk.w & 0xffffu; entry[7] = blk.w >> 16;
 }
+// Four consecutive entries that start at slot `first` (0 .. 7) of block `a` and run on into block `b`
+// (the block after it): a run of entries that begins anywhere in a list, taken out of two 16-byte
+// loads without a register array indexed per lane (which would live in scratch) - three 4-way word
+// selects and two funnel shifts.  (first + 3 <= 10: of `b` only its first two words can be needed.)
+__device__ __forceinline__ void list_entries_from(const uint4& a, const uint4& b, uint32_t first, uint32_t (&entry)[4])
+{
+   const uint32_t w = first >> 1;
+   const uint32_t w0 = w == 0u ? a.x : w == 1u ? a.y : w == 2u ? a.z : a.w;
+   const uint32_t w1 = w == 0u ? a.y : w == 1u ? a.z : w == 2u ? a.w : b.x;
+   const uint32_t w2 = w == 0u ? a.z : w == 1u ? a.w : w == 2u ? b.x : b.y;
+   const uint32_t sh = (first & 1u) * 16u;
+   const uint32_t lo = (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh);
+   const uint32_t hi = (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh);
+   entry[0] = lo & 0xffffu; entry[1] = lo >> 16;
+   entry[2] = hi & 0xffffu; entry[3] = hi >> 16;
+}
 // Zeroes the entries between a list's end and the end of its last block (0 is a valid tile index):
 // the bit-exact acceleration loop gathers by every entry of a fetched block before it looks at the
 // count, and what an earlier step left there need not be an index of this step's tile.

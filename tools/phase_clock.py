@@ -19,8 +19,8 @@ from smoothed_particle_hydrodynamics_amd import scenes
 
 DENSITY = ["descriptor, own position, row ranges", "tile", "TEST + append", "pad / particles without a list",
            "SUM", "results issued"]
-ACCEL = ["ranges, flags, descriptor", "tile, own loads, first list block", "pressure loop (exact: -)",
-         "viscous loop (exact: the pair loop)", "end of the sum, acceleration issued",
+ACCEL = ["ranges, flags, descriptor", "tile, own loads, first list block, first viscous gathers issued",
+         "viscous sum (exact: -)", "pressure loop (exact: the pair loop)", "end of the sum, acceleration issued",
          "integrate, hash, count, energy sums"]
 
 

@@ -93,7 +93,7 @@ def source_spans():
     a0 = find(ft, "k_full_accel_lists(const float4* __restrict__ posm")
     g0 = find(ft, "if ((int)blockIdx.x < tile_stats[TSTAT_GIVEUP_ACCEL]) {", a0)
     g1 = find(ft, "if (gave_up == LISTS_NONE) return;", a0)
-    p0 = find(ft, "if constexpr (FAST) {", a0)
+    p0 = find(ft, "if constexpr (FAST) {", find(ft, "PHASE_MARK(17);", a0))   # (the prologue has FAST blocks of its own)
     p1 = find(ft, "if (gave_up == LISTS_SOME && __any(no_list) && no_list) {", a0)
     e0 = find(ft, "if (FAST) accel_fast_finish(k, s);", p1)
     spans["a_pro"].append(("full_tiled.h", a0, g0 - 1))
