@@ -93,6 +93,19 @@ inline const char* body_motion_check(const sph_hip_obstacle_motion* motion, int 
    return nullptr;
 }
 
+// Why rotations and bodies do not go together (either list may be empty), or nullptr: posed entries and
+// bodies exclude each other within one list, so that k_integrate_bodies never meets a posed entry (one
+// function for both directions).
+inline const char* body_rotation_check(const sph_hip_obstacle_rotation* rot, int n_rot, const sph_hip_body* bodies,
+                                       int n_bodies)
+{
+   for (int i = 0; i < n_rot && i < n_bodies; i++)
+      if (obstacle_posed(rot[i]) && body_is(bodies[i])) return "a posed entry on an obstacle that is a body";
+   if (obstacles_posed(rot, n_rot) > 0 && bodies_count(bodies, n_bodies) > 0)
+      return "posed entries and bodies in one obstacle list";
+   return nullptr;
+}
+
 // The quantum rule, both directions.  n_bodies: bodies in force with quantum body_quantum_log2.
 inline const char* body_refuses_recording(int n_bodies, int body_quantum_log2, int rows, int quantum_log2)
 {

@@ -287,6 +287,19 @@ inline bool use_moving_kernels(int n_obstacles, int n_moving) { return n_obstacl
 // keeps the step off the fused routes above; the motion clock advances as use_moving_kernels says.)
 inline bool use_body_kernels(int n_obstacles, int n_bodies) { return n_obstacles > 0 && n_bodies > 0; }
 
+// Oriented and rotating obstacles (obstacle_policy.h, third part; no launch asks these two yet).  Whether a
+// step's integrate would take kernels for posed entries: some entry of the rotation list is posed.  Such a
+// list holds no body (body_policy.h: body_rotation_check), so the body kernels are no candidate for it; its
+// entries that move, or stand, take their usual turn beside the posed ones.
+inline bool use_posed_kernels(int n_obstacles, int n_posed) { return n_obstacles > 0 && n_posed > 0; }
+
+// Whether the motion clock advances with a step: some entry moves (use_moving_kernels) or rotates.  A list
+// that is only tilted leaves it standing.
+inline bool motion_clock_runs(int n_obstacles, int n_moving, int n_rotating)
+{
+   return n_obstacles > 0 && (n_moving > 0 || n_rotating > 0);
+}
+
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
 // slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary

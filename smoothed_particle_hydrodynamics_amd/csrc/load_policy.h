@@ -134,6 +134,23 @@ OBST_HD inline void load_obstacles_respond_moving(const sph_hip_obstacle* list, 
    }
 }
 
+// obstacles_respond_posed (obstacle_policy.h) with rec called at every obstacle's turn: a posed entry's
+// turn is recorded when q, taken to the solid's frame at the end of the step, is inside it, vb and va
+// being the world velocities before and after that turn.  Column, quantum and skip rules are unchanged.
+template <class Rec>
+OBST_HD inline void load_obstacles_respond_posed(const sph_hip_obstacle* list, const sph_hip_obstacle_motion* motion,
+                                                 const sph_hip_obstacle_rotation* rot, const ObstaclePose* pose, int n,
+                                                 const float p[3], float v[3], float q[3], float dt, float damping,
+                                                 float tau0, float tau1, float m, const Rec& rec)
+{
+   for (int i = 0; i < n; i++) {
+      const float vb[3] = {v[0], v[1], v[2]};
+      const bool in = obstacle_turn_any(list[i], motion ? motion + i : nullptr, rot[i], pose[i], p, v, q, dt, damping,
+                                        tau0, tau1);
+      rec(6 + i, in, m, vb, v);
+   }
+}
+
 // A recorder that adds term by term into one row (LOAD_ROW_WORDS int64): what the device's wave
 // reductions and atomic adds sum to.
 struct LoadRowAdder {

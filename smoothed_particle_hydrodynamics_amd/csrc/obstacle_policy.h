@@ -67,6 +67,37 @@
 //              moves with the solid and coincides with the world at the end of the step: a solid moving
 //              at u into a particle at rest leaves it at 2u along the normal.
 // Obstacles act in list order, moving or not, each on the v, q the one before it left.
+//
+// Oriented and rotating obstacles: the contract only (tests/test_rotating_obstacles_cpu.py against
+// tests/rotating_obstacle_emulation.py).  No entry point of include/sph_hip.h takes a rotation list and no
+// kernel calls these functions yet - DESIGN.md section 20 says why - so sph_hip_obstacle_rotation is
+// declared below, not in the public header.
+// Entry i of the rotation list belongs to obstacle i.  a = axis, u = (a+1)%3, w = (a+2)%3.
+//   posed      angle != 0 || rate != 0; rotates: rate != 0.  An entry that is not posed takes exactly the
+//              turn above (static, or obstacle_turn with its motion): nothing is added to it or rotated by
+//              zero.
+//   angle      theta(tau) = angle + rate * s(tau), s the clamp above with the rotation's start and stop.
+//   sincos     obstacle_sincos(theta, cs, sn): k = rintf(theta * 2/pi); r = ((theta - k*P1) - k*P2) - k*P3
+//              (P1 + P2 + P3 = pi/2: P1 has 8 significant bits, P2 11, so both products are exact up to
+//              |theta| = 8192); z = r*r; s = ((S3*z + S2)*z + S1), s = (s*z)*r + r;
+//              c = ((C3*z + C2)*z + C1), c = ((c*z)*z - 0.5*z) + 1; quadrant k & 3 (two's complement):
+//              0: (c, s), 1: (-s, c), 2: (-c, -s), 3: (s, -c) for (cs, sn).  No libm call: numpy float32
+//              operations restate it exactly.
+//   frames     to_body(cs, sn, x): y_a = x_a; du = x_u - pivot_u, dw = x_w - pivot_w;
+//              y_u = pivot_u + (cs*du + sn*dw); y_w = pivot_w + (cs*dw - sn*du).
+//              to_world(cs, sn, y): du, dw from y; x_u = pivot_u + (cs*du - sn*dw);
+//              x_w = pivot_w + (sn*du + cs*dw).  vec_to_body / vec_to_world: the same without the pivot.
+//   response   (cs0, sn0) at theta(tau0), (cs1, sn1) at theta(tau1), o the list entry as set.
+//              q1 = to_body(1, q); q1 not strictly inside o: the particle is untouched, bit for bit.
+//              p0 = to_body(0, p).  theta(tau1) == theta(tau0) (tilted at rest, not started, stopped,
+//              dt == 0): w = vec_to_body(1, v); the response above with (o, p0, w, q1);
+//              v = vec_to_world(1, w); q = to_world(1, q1); nothing is divided.  Otherwise
+//              pc = to_world(1, p0) - where the solid's material point at p ends up -, d = pc - p,
+//              ue = d / dt, wv = v - ue, w = vec_to_body(1, wv); the same response; wv = vec_to_world(1, w),
+//              v = wv + ue, q = to_world(1, q1).  The static response in the frame fixed to the solid that
+//              coincides with the world at the end of the step, with a per-particle displacement: a face
+//              moving at omega * r into fluid at rest leaves it at 2 * omega * r along the normal.
+//   excluded   a posed entry on an obstacle whose motion moves; posed entries and free bodies in one list.
 #pragma once
 
 #include <math.h>
@@ -403,4 +434,200 @@ OBST_HD inline void obstacles_respond_moving(const sph_hip_obstacle* list, const
                                              float damping, float tau0, float tau1)
 {
    for (int i = 0; i < n; i++) obstacle_turn(list[i], motion[i], p, v, q, dt, damping, tau0, tau1);
+}
+
+// ---- oriented and rotating obstacles (the contract's third part) ------------------------------------
+
+#define OBSTACLE_MAX_ANGLE 8192.0f
+
+typedef struct sph_hip_obstacle_rotation {   /* field order is fixed: 32 bytes */
+   int32_t axis;                    /* 0, 1 or 2: the coordinate axis the solid turns about */
+   float pivot[3];                  /* a point on that axis (the component along `axis` is unused) */
+   float angle;                     /* radians at the clock's start, right-handed about +axis */
+   float rate;                      /* radians per unit of time_step while start <= tau <= stop */
+   float start, stop;               /* on the motion clock; stop may be +INFINITY */
+} sph_hip_obstacle_rotation;
+
+OBST_HD inline bool obstacle_posed(const sph_hip_obstacle_rotation& r) { return r.angle != 0.0f || r.rate != 0.0f; }
+OBST_HD inline bool obstacle_rotates(const sph_hip_obstacle_rotation& r) { return r.rate != 0.0f; }
+
+// Why a rotation list for `n_obstacles` obstacles is refused, or nullptr.  n = 0 clears all rotations.
+inline const char* obstacle_rotation_check(const sph_hip_obstacle_rotation* list, int n, int n_obstacles)
+{
+   if (n != 0 && n != n_obstacles) return "the rotation count must be 0 or the obstacle count";
+   if (n > 0 && !list) return "null rotation list";
+   for (int i = 0; i < n; i++) {
+      const sph_hip_obstacle_rotation& r = list[i];
+      if (r.axis < 0 || r.axis > 2) return "a rotation's axis must be 0, 1 or 2";
+      if (!isfinite(r.pivot[0]) || !isfinite(r.pivot[1]) || !isfinite(r.pivot[2]))
+         return "a rotation's pivot must be finite";
+      if (!isfinite(r.angle) || !isfinite(r.rate)) return "a rotation's angle and rate must be finite";
+      if (!isfinite(r.start) || !(r.start >= 0.0f)) return "a rotation's start must be finite and >= 0";
+      if (!(r.stop >= r.start)) return "a rotation needs stop >= start";
+      if (fabs((double)r.angle) > (double)OBSTACLE_MAX_ANGLE) return "a rotation's angle must stay within 8192 radians";
+      if (isfinite(r.stop) &&
+          fabs((double)r.angle) + fabs((double)r.rate) * ((double)r.stop - (double)r.start) > (double)OBSTACLE_MAX_ANGLE)
+         return "a rotation's angle must stay within 8192 radians until its stop";
+   }
+   return nullptr;
+}
+
+// Why rotations and motions do not go together (either list may be empty), or nullptr: one function
+// for both directions.
+inline const char* obstacle_rotation_motion_check(const sph_hip_obstacle_rotation* rot, int n_rot,
+                                                  const sph_hip_obstacle_motion* motion, int n_motion)
+{
+   for (int i = 0; i < n_rot && i < n_motion; i++)
+      if (obstacle_posed(rot[i]) && obstacle_moves(motion[i])) return "a posed entry on an obstacle whose motion moves";
+   return nullptr;
+}
+
+// how many entries of a rotation list are posed / rotate
+inline int obstacles_posed(const sph_hip_obstacle_rotation* list, int n)
+{
+   int k = 0;
+   for (int i = 0; i < n; i++) k += obstacle_posed(list[i]) ? 1 : 0;
+   return k;
+}
+inline int obstacles_rotating(const sph_hip_obstacle_rotation* list, int n)
+{
+   int k = 0;
+   for (int i = 0; i < n; i++) k += obstacle_rotates(list[i]) ? 1 : 0;
+   return k;
+}
+
+OBST_HD inline float obstacle_theta(const sph_hip_obstacle_rotation& r, float tau)
+{
+   const float s = (tau < r.start ? r.start : tau > r.stop ? r.stop : tau) - r.start;
+   const float turned = r.rate * s;
+   return r.angle + turned;
+}
+
+// cos and sin of theta (see the contract: every operation is written out, one rounding each)
+OBST_HD inline void obstacle_sincos(float theta, float& cs, float& sn)
+{
+   const float k = rintf(theta * 0.636619772367581343f);
+   float r = theta - k * 1.5703125f;
+   r = r - k * 4.837512969970703125e-4f;
+   r = r - k * 7.54978995489188216e-8f;
+   const float z = r * r;
+   float s = -1.9515295891e-4f * z + 8.3321608736e-3f;
+   s = s * z + -1.6666654611e-1f;
+   s = (s * z) * r + r;
+   float c = 2.443315711809948e-5f * z + -1.388731625493765e-3f;
+   c = c * z + 4.166664568298827e-2f;
+   c = (c * z) * z - 0.5f * z;
+   c = c + 1.0f;
+   const int q = (int)k & 3;
+   cs = q == 0 ? c : q == 1 ? -s : q == 2 ? -c : s;
+   sn = q == 0 ? s : q == 1 ? c : q == 2 ? -s : -c;
+}
+
+// One entry's pose for a step: the frame at the start (0) and at the end (1) of the step; still: the
+// angle is the same at both.  24 bytes: formed once per obstacle and step, not once per particle.
+struct ObstaclePose {
+   float cs0, sn0, cs1, sn1;
+   int32_t posed, still;
+};
+
+OBST_HD inline ObstaclePose obstacle_pose_of_step(const sph_hip_obstacle_rotation& r, float tau0, float tau1)
+{
+   ObstaclePose ps = {1.0f, 0.0f, 1.0f, 0.0f, 0, 1};
+   if (!obstacle_posed(r)) return ps;
+   const float t0 = obstacle_theta(r, tau0), t1 = obstacle_theta(r, tau1);
+   obstacle_sincos(t0, ps.cs0, ps.sn0);
+   obstacle_sincos(t1, ps.cs1, ps.sn1);
+   ps.posed = 1;
+   ps.still = t1 == t0 ? 1 : 0;
+   return ps;
+}
+
+OBST_HD inline void obstacle_to_body(const sph_hip_obstacle_rotation& r, float cs, float sn, const float x[3], float y[3])
+{
+   const int a = r.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+   const float du = x[u] - r.pivot[u], dw = x[w] - r.pivot[w];
+   y[a] = x[a];
+   y[u] = r.pivot[u] + (cs * du + sn * dw);
+   y[w] = r.pivot[w] + (cs * dw - sn * du);
+}
+
+OBST_HD inline void obstacle_to_world(const sph_hip_obstacle_rotation& r, float cs, float sn, const float y[3], float x[3])
+{
+   const int a = r.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+   const float du = y[u] - r.pivot[u], dw = y[w] - r.pivot[w];
+   x[a] = y[a];
+   x[u] = r.pivot[u] + (cs * du - sn * dw);
+   x[w] = r.pivot[w] + (sn * du + cs * dw);
+}
+
+OBST_HD inline void obstacle_vec_to_body(const sph_hip_obstacle_rotation& r, float cs, float sn, const float x[3], float y[3])
+{
+   const int a = r.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+   const float xu = x[u], xw = x[w];
+   y[a] = x[a];
+   y[u] = cs * xu + sn * xw;
+   y[w] = cs * xw - sn * xu;
+}
+
+OBST_HD inline void obstacle_vec_to_world(const sph_hip_obstacle_rotation& r, float cs, float sn, const float y[3], float x[3])
+{
+   const int a = r.axis, u = (a + 1) % 3, w = (a + 2) % 3;
+   const float yu = y[u], yw = y[w];
+   x[a] = y[a];
+   x[u] = cs * yu - sn * yw;
+   x[w] = sn * yu + cs * yw;
+}
+
+// A posed entry's turn with its pose of this step (one obstacle_respond call site for both branches of
+// the contract).  Returns whether q was strictly inside the solid as it stands at the end of the step.
+OBST_HD inline bool obstacle_turn_posed(const sph_hip_obstacle& o, const sph_hip_obstacle_rotation& r,
+                                        const ObstaclePose& ps, const float p[3], float v[3], float q[3], float dt,
+                                        float damping)
+{
+   float q1[3];
+   obstacle_to_body(r, ps.cs1, ps.sn1, q, q1);
+   if (!obstacle_inside(o, q1)) return false;
+   float p0[3];
+   obstacle_to_body(r, ps.cs0, ps.sn0, p, p0);
+   const bool boost = !ps.still;
+   float ue[3] = {0.0f, 0.0f, 0.0f}, wv[3] = {v[0], v[1], v[2]};
+   if (boost) {
+      float pc[3];
+      obstacle_to_world(r, ps.cs1, ps.sn1, p0, pc);
+      for (int c = 0; c < 3; c++) {
+         const float d = pc[c] - p[c];
+         ue[c] = d / dt;
+         wv[c] = v[c] - ue[c];
+      }
+   }
+   float w[3];
+   obstacle_vec_to_body(r, ps.cs1, ps.sn1, wv, w);
+   obstacle_respond(o, p0, w, q1, dt, damping);
+   obstacle_vec_to_world(r, ps.cs1, ps.sn1, w, wv);
+   for (int c = 0; c < 3; c++) v[c] = boost ? wv[c] + ue[c] : wv[c];
+   obstacle_to_world(r, ps.cs1, ps.sn1, q1, q);
+   return true;
+}
+
+// One entry's turn in a list with rotations: obstacle_turn_posed for a posed one, otherwise the turn of
+// its motion (`motion` may be null: no motions set) or the static one.
+OBST_HD inline bool obstacle_turn_any(const sph_hip_obstacle& o, const sph_hip_obstacle_motion* motion,
+                                      const sph_hip_obstacle_rotation& r, const ObstaclePose& ps, const float p[3],
+                                      float v[3], float q[3], float dt, float damping, float tau0, float tau1)
+{
+   if (ps.posed) return obstacle_turn_posed(o, r, ps, p, v, q, dt, damping);
+   if (motion) return obstacle_turn(o, *motion, p, v, q, dt, damping, tau0, tau1);
+   const bool in = obstacle_inside(o, q);
+   obstacle_respond(o, p, v, q, dt, damping);
+   return in;
+}
+
+// Every obstacle of a list with rotations, in order, with the poses of this step (`pose`: one per obstacle).
+OBST_HD inline void obstacles_respond_posed(const sph_hip_obstacle* list, const sph_hip_obstacle_motion* motion,
+                                            const sph_hip_obstacle_rotation* rot, const ObstaclePose* pose, int n,
+                                            const float p[3], float v[3], float q[3], float dt, float damping,
+                                            float tau0, float tau1)
+{
+   for (int i = 0; i < n; i++)
+      obstacle_turn_any(list[i], motion ? motion + i : nullptr, rot[i], pose[i], p, v, q, dt, damping, tau0, tau1);
 }

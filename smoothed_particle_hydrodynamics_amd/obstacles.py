@@ -6,6 +6,9 @@ gives the C ABI's sph_hip_obstacle, `signed_distance(points)` the numpy distance
 obstacle is driven at between two readings of the context's motion clock
 (sph_hip_set_obstacle_motion); `Body` makes it a free body that the fluid's own loads move
 (sph_hip_set_bodies).  The collision response itself is csrc/obstacle_policy.h and runs on the GPU.
+`Rotation` tilts an obstacle, or turns it at a constant angular rate, about a coordinate axis through a
+pivot: the contract (csrc/obstacle_policy.h, third part), scene building and carving only - no context
+takes a rotation list yet.
 """
 import ctypes as C
 import math
@@ -190,6 +193,92 @@ def as_motion_array(motions):
     return arr, len(motions)
 
 
+class SphObstacleRotation(C.Structure):
+    """Mirror of sph_hip_obstacle_rotation (csrc/obstacle_policy.h): 32 bytes, field order is fixed."""
+
+    _fields_ = [("axis", C.c_int32), ("pivot", C.c_float * 3), ("angle", C.c_float), ("rate", C.c_float),
+                ("start", C.c_float), ("stop", C.c_float)]
+
+
+class Rotation:
+    """An obstacle turned about the coordinate axis `axis` (0 x, 1 y, 2 z) through `pivot`: by `angle` radians
+    (right-handed about +axis) at the motion clock's start, and on at `rate` radians per unit of time_step
+    while the clock is in [start, stop]; stop may be math.inf.  The obstacle's own fields describe it in the
+    frame that turns with it, which coincides with the world at angle 0."""
+
+    def __init__(self, axis, pivot, angle=0.0, rate=0.0, start=0.0, stop=math.inf):
+        if int(axis) not in (0, 1, 2):
+            raise ValueError("axis must be 0, 1 or 2")
+        self.axis = int(axis)
+        self.pivot = _vec3(pivot)
+        self.angle, self.rate = np.float32(angle), np.float32(rate)
+        self.start, self.stop = np.float32(start), np.float32(stop)
+
+    def as_struct(self):
+        s = SphObstacleRotation()
+        s.axis = self.axis
+        s.pivot[:] = [float(v) for v in self.pivot]
+        s.angle, s.rate = float(self.angle), float(self.rate)
+        s.start, s.stop = float(self.start), float(self.stop)
+        return s
+
+    def posed(self):
+        return bool(self.angle != 0 or self.rate != 0)
+
+    def rotates(self):
+        return bool(self.rate != 0)
+
+    def angle_at(self, clock):
+        """theta at motion clock `clock`, in the contract's fp32 arithmetic."""
+        tau = np.float32(clock)
+        s = np.float32((self.start if tau < self.start else self.stop if tau > self.stop else tau) - self.start)
+        with np.errstate(over="ignore", invalid="ignore"):
+            return np.float32(self.angle + np.float32(self.rate * s))
+
+    def _turn(self, points, theta, sign):
+        x = _points(points).copy()
+        a = self.axis
+        u, w = (a + 1) % 3, (a + 2) % 3
+        pv = self.pivot.astype(np.float64)
+        cs, sn = math.cos(float(theta)), sign * math.sin(float(theta))
+        du, dw = x[:, u] - pv[u], x[:, w] - pv[w]
+        x[:, u] = pv[u] + (cs * du + sn * dw)
+        x[:, w] = pv[w] + (cs * dw - sn * du)
+        return x
+
+    def to_body(self, points, clock=0.0):
+        """World points in the frame fixed to the solid at motion clock `clock` (float64, for building
+        scenes; the contract's fp32 form is csrc/obstacle_policy.h)."""
+        return self._turn(points, self.angle_at(clock), 1.0)
+
+    def to_world(self, points, clock=0.0):
+        """Points of the solid's frame in the world at motion clock `clock` (float64)."""
+        return self._turn(points, self.angle_at(clock), -1.0)
+
+    def __eq__(self, other):
+        return isinstance(other, Rotation) and bytes(self.as_struct()) == bytes(other.as_struct())
+
+    def __repr__(self):
+        return "Rotation(%d, %s, %g, %g, %g, %g)" % (self.axis, list(self.pivot), self.angle, self.rate, self.start,
+                                                     self.stop)
+
+
+def rotation_from_struct(s):
+    return Rotation(s.axis, list(s.pivot), s.angle, s.rate, s.start, s.stop)
+
+
+def as_rotation_array(rotations):
+    """A ctypes array of sph_hip_obstacle_rotation for a list of Rotation, struct or None (unposed: all
+    zero with stop = inf)."""
+    rotations = list(rotations)
+    arr = (SphObstacleRotation * max(1, len(rotations)))()
+    for i, r in enumerate(rotations):
+        if r is None:
+            r = Rotation(0, (0.0, 0.0, 0.0))
+        arr[i] = r if isinstance(r, SphObstacleRotation) else r.as_struct()
+    return arr, len(rotations)
+
+
 class SphBody(C.Structure):
     """Mirror of sph_hip_body (include/sph_hip.h): 56 bytes, field order is ABI."""
 
@@ -260,10 +349,16 @@ def as_body_array(bodies):
     return arr, len(bodies)
 
 
-def inside_any(points, obstacles):
-    """Boolean mask of the points strictly inside any of the obstacles (float64 distances)."""
+def inside_any(points, obstacles, rotations=None):
+    """Boolean mask of the points strictly inside any of the obstacles (float64 distances); with
+    `rotations` (a Rotation or None per obstacle), inside each as it stands at the motion clock's start."""
     p = _points(points)
     mask = np.zeros(p.shape[0], bool)
-    for o in obstacles:
-        mask |= o.signed_distance(p) < 0.0
+    obstacles = list(obstacles)
+    rotations = list(rotations) if rotations else [None] * len(obstacles)
+    if len(rotations) != len(obstacles):
+        raise ValueError("rotations must hold one entry (a Rotation or None) per obstacle")
+    for o, r in zip(obstacles, rotations):
+        x = p if r is None or not r.posed() else r.to_body(p)
+        mask |= o.signed_distance(x) < 0.0
     return mask

@@ -155,11 +155,12 @@ def reference_sphere(n, params=None):
     return p, pos, vel, np.ones(n, f32)
 
 
-def carve(pos, vel, mass, obstacles):
+def carve(pos, vel, mass, obstacles, rotations=None):
     """The scene without the particles that start strictly inside an obstacle (obstacles.Sphere /
-    Box / Cylinder): (pos[3m], vel[3m], mass[m]), the kept rows in their order."""
+    Box / Cylinder, each as its obstacles.Rotation of `rotations` poses it at the motion clock's start):
+    (pos[3m], vel[3m], mass[m]), the kept rows in their order."""
     from .obstacles import inside_any
-    keep = ~inside_any(np.asarray(pos, np.float32).reshape(-1, 3), obstacles)
+    keep = ~inside_any(np.asarray(pos, np.float32).reshape(-1, 3), obstacles, rotations)
     pos = np.ascontiguousarray(np.asarray(pos, np.float32).reshape(-1, 3)[keep].reshape(-1))
     vel = np.ascontiguousarray(np.asarray(vel, np.float32).reshape(-1, 3)[keep].reshape(-1))
     return pos, vel, np.ascontiguousarray(np.asarray(mass, np.float32)[keep])
@@ -205,6 +206,50 @@ def dam_break_gate(n, lift_speed, thickness=2.0, surge=0.7, box=(1.0, 1.0, 1.0),
     pos, vel, mass = carve(pos, vel, mass, [gate])
     travel = top + 2.0 * h
     return p, pos, vel, mass, [gate], [Motion((0.0, lift_speed, 0.0), 0.0, travel / lift_speed)]
+
+
+def dam_break_ramp(n, slope_deg=20.0, length=0.6, thickness=0.1, gap=0.25, surge=0.7, box=(1.0, 1.0, 1.0),
+                   fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42, gravity=-9.81):
+    """The surging dam column of dam_break_pillar (gravity along -y, the walls on, the surge along +x) running
+    up a ramp: a Box `length` long and `thickness` thick across the whole box along z, whose upper upstream
+    edge lies on the floor `gap` kernel radii from the column's face, tilted about z through that edge by
+    `slope_deg` degrees, so that its upper face rises downstream.  Particles that would start inside it are
+    dropped (carve).  Returns (params, pos, vel, mass, [Box], [Rotation]); the rotation is the contract's
+    (csrc/obstacle_policy.h, third part), which no context takes yet."""
+    from .obstacles import Box, Rotation
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    vel.reshape(-1, 3)[:, 0] = np.float32(surge)
+    h = float(p.h)
+    x0 = box[0] * fill[0] + gap * h
+    ramp = Box((x0, -thickness, -h), (x0 + length, 0.0, float(p.max_z) + h))
+    tilt = Rotation(2, (x0, 0.0, 0.0), math.radians(slope_deg))
+    pos, vel, mass = carve(pos, vel, mass, [ramp], [tilt])
+    return p, pos, vel, mass, [ramp], [tilt]
+
+
+def stirred_tank(n, rate, depth=0.5, blade=(0.6, 0.08), start=0.0, stop=math.inf, box=(1.0, 1.0, 1.0),
+                 neighbors=32.0, seed=42, gravity=-9.81):
+    """A block of fluid at rest filling the tank to `depth` of its height (gravity along -y, the walls on),
+    stirred by a paddle: a Box blade[0] of the tank's width long and blade[1] thick, from below the floor to
+    above the fluid, centred on the vertical axis through the tank's middle and turning about it at `rate`
+    radians per unit of time_step while the motion clock is in [start, stop].  Particles that would start
+    inside the paddle are dropped (carve).  Returns (params, pos, vel, mass, [Box], [Rotation]); the rotation
+    is the contract's (csrc/obstacle_policy.h, third part), which no context takes yet."""
+    from .obstacles import Box, Rotation
+    p, pos, vel, mass = dam_break(n, box, (1.0, depth, 1.0), neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    h = float(p.h)
+    cx, cz = 0.5 * float(p.max_x), 0.5 * float(p.max_z)
+    half, thick = 0.5 * blade[0] * float(p.max_x), 0.5 * blade[1] * float(p.max_z)
+    paddle = Box((cx - half, -h, cz - thick), (cx + half, box[1] * depth + 2.0 * h, cz + thick))
+    turn = Rotation(1, (cx, 0.0, cz), 0.0, rate, start, stop)
+    pos, vel, mass = carve(pos, vel, mass, [paddle])
+    return p, pos, vel, mass, [paddle], [turn]
 
 
 def dam_break_debris(n, size=(0.12, 0.12, 0.3), gap=3.0, density_ratio=6.0, surge=0.7, box=(1.0, 1.0, 1.0),
