@@ -432,6 +432,72 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
                    int width, int height, int flags, uint8_t* rgba, float* depth,
                    float* normal_xyz, float* velocity_xyz, int32_t* first_inside);
 
+/* ---- scene renderer ------------------------------------------------------------------------ *
+ *
+ * sph_hip_render's frame with the context's solids drawn into it: the obstacles as they stand now
+ * (what sph_hip_get_obstacles_now returns: motions at the current clock, bodies where the device has
+ * moved them), met analytically by each pixel's ray and composited with the fluid by depth.  The
+ * fluid pass is sph_hip_render's, unchanged; a pass of its own (k_scene_solids) then overwrites the
+ * pixels a solid takes.  csrc/scene_policy.h holds the functions, one set for the device and the
+ * host.  All arithmetic is fp32, unfused, in the order written ("a + b + c" is (a + b) + c); sqrtf and
+ * "/" are correctly rounded; fminf / fmaxf follow C99.  eye, d: the camera's eye and the pixel's
+ * normalised direction exactly as the renderer forms it (a pixel whose len is 0 or not finite meets no
+ * solid); the ray is eye + t * d.
+ *   slab       of one axis a with bounds lo, hi: inv = 1.0f / d_a, u0 = (lo - eye_a) * inv,
+ *              u1 = (hi - eye_a) * inv, near_a = fminf(u0, u1), far_a = fmaxf(u0, u1) - the renderer's
+ *              box, with its NaN behaviour: d_a == 0 with eye_a on a plane makes that u NaN, and
+ *              near_a = far_a = the other u.
+ *   interval   every kind gives [t0, t1].  A miss unless t0 <= t1 and t1 >= 0 (NaN misses).
+ *              t0 < 0: the eye is inside; t = 0 and the normal is -d per component.  Otherwise
+ *              t = fmaxf(t0, 0.0f) + 0.0f (the sum makes a -0 a +0) and the normal is the kind's.
+ *   sphere     o = eye - center; b = (ox*dx + oy*dy) + oz*dz; c = ((ox*ox + oy*oy) + oz*oz) - r*r;
+ *              disc = b*b - c; a miss unless disc >= 0; s = sqrtf(disc); t0 = -b - s, t1 = -b + s.
+ *              normal_a = ((eye_a + t * d_a) - center_a) / r.
+ *   box        t0 = fmaxf(fmaxf(near_x, near_y), near_z), t1 = fminf(fminf(far_x, far_y), far_z).
+ *              The normal lies on the first axis a of x, y, z with near_a == t0:
+ *              normal_a = d_a > 0 ? -1 : 1, the other two components 0.
+ *   cylinder   axis a, u = (a+1)%3, w = (a+2)%3; ou = eye_u - center_u, ow = eye_w - center_w;
+ *              A = du*du + dw*dw.  A == 0 (the ray is parallel to the axis): a miss unless
+ *              ou*ou + ow*ow < r*r, else s0 = -inf, s1 = +inf.  Otherwise B = ou*du + ow*dw,
+ *              C = (ou*ou + ow*ow) - r*r, disc = B*B - A*C, a miss unless disc >= 0, s = sqrtf(disc),
+ *              s0 = (-B - s) / A, s1 = (-B + s) / A.  Cap slab on a: near_a, far_a.
+ *              side = s0 >= near_a (on equal bounds the side wins); t0 = side ? s0 : near_a;
+ *              t1 = fminf(s1, far_a).  Side: normal_u = ((eye_u + t * d_u) - center_u) / r, normal_w
+ *              likewise, normal_a = 0.  Cap: normal_a = d_a > 0 ? -1 : 1, the other two 0.
+ *   nearest    the solids in list order; solid i replaces the best so far when it is hit with
+ *              t_i < t_best (strictly; t_best starts at +inf): the lower index wins a tie.
+ *   composite  the nearest solid takes the pixel when t_solid < depth_fluid, strictly; depth_fluid is
+ *              sph_hip_render's depth, +inf on a miss.  The marched box does not clip solids.  Such a
+ *              pixel gets: rgba by the renderer's shade formula with the solid's normal, rp->light, the
+ *              solid's albedo (solid_albedo_rgb[3 * i ..], or sp->albedo for every solid when
+ *              n_albedo == 0) and sp->ambient / sp->diffuse, alpha 255; depth = t_solid; normal_xyz =
+ *              the solid's normal; velocity_xyz = the solid's velocity with SPH_HIP_RENDER_VELOCITY,
+ *              else 0; first_inside = -1; solid_id = i.  Every other pixel keeps sph_hip_render's
+ *              outputs bit for bit and gets solid_id = -1.
+ *   velocity   of solid i: its motion's velocity while start <= tau < stop on the motion clock (and
+ *              the motion moves); a body's velocity V of its device state; otherwise 0.
+ * Without obstacles every output equals sph_hip_render's byte for byte and solid_id is -1 everywhere.
+ * With obstacles and no particle resident the solids are drawn over `background`.  The call
+ * synchronises (it reads the bodies' state when bodies are set) and does not change the simulation:
+ * sph_hip_download returns the same bytes before and after it, later steps are bit-identical, the
+ * motion clock and the bodies' state are untouched.
+ * SPH_HIP_ERR_INVALID, with a last_error text that names sph_hip_render_scene, for everything
+ * sph_hip_render refuses, null scene params, a scene params field or a solid's albedo that is not
+ * finite, an n_albedo that is neither 0 nor the obstacle count (or a null array with n_albedo > 0),
+ * and flag bits other than SPH_HIP_RENDER_VELOCITY.
+ * This entry point was added without a change of SPH_HIP_ABI_VERSION: no existing struct and no
+ * existing prototype changed.  A host that must run with older libraries looks the symbol up. */
+typedef struct sph_hip_scene_params {   /* field order is ABI: 20 bytes */
+   float albedo[3];       /* of every solid without an entry in solid_albedo */
+   float ambient, diffuse;
+} sph_hip_scene_params;
+
+int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                         const sph_hip_scene_params* sp, const float* solid_albedo_rgb /* 3n or NULL */,
+                         int n_albedo, int width, int height, int flags,
+                         uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
+                         int32_t* first_inside, int32_t* solid_id);
+
 /* ---- static obstacles --------------------------------------------------------------------- *
  *
  * Analytic solids inside the domain: spheres, axis-aligned boxes and axis-aligned capped

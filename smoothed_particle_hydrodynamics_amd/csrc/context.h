@@ -20,6 +20,7 @@
 #include "sample_kernels.h"
 #include "surface_kernels.h"
 #include "render_kernels.h"
+#include "scene_kernels.h"
 #include "tracer_kernels.h"
 #include "gauge_kernels.h"
 #include "slab_kernels.h"
@@ -294,6 +295,10 @@ struct sph_hip_context {
    Scratch<unsigned char> render_scratch;
    Scratch<unsigned char> render_occ;
    int render_noskip = 0;   // SPH_HIP_RENDER_NOSKIP=1 (tests, A/B runs): every sample walks
+   // scene renderer (sph_hip_render_scene): a chunk's solid_id, and the solids as they stand at the call
+   Scratch<int32_t> scene_id;
+   Scratch<SceneSolid> scene_list;
+   SceneSolid scene_list_host[SPH_HIP_MAX_OBSTACLES];
 
    // static obstacles (sph_hip_set_obstacles): the list the next enqueued steps use, its device copy,
    // and the pinned staging of that copy (reused only after the event behind the last copy)

@@ -1151,6 +1151,26 @@ int sph_hip_get_obstacle_motion(sph_hip_context* ctx, sph_hip_obstacle_motion* o
    return ctx->n_motion;
 }
 
+namespace {
+// The first k obstacles as they stand now: displaced to the motion clock, bodies to where the device
+// has moved them (which synchronises; `st`, when given, receives the bodies' device state then).
+int obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int k, BodyState* st)
+{
+   for (int i = 0; i < k; i++)
+      out[i] = obstacle_at(ctx->obst_host[i], i < ctx->n_motion ? &ctx->motion_host[i] : nullptr, ctx->motion_tau);
+   if (ctx->n_bodies > 0 && k > 0) {   // a body stands where the device has moved it to
+      BodyState mine[SPH_HIP_MAX_OBSTACLES];
+      if (!st) st = mine;
+      int rc = check_ctx(ctx);
+      if (rc) return rc;
+      if ((rc = read_body_states(ctx, st))) return rc;
+      for (int i = 0; i < k; i++)
+         if (body_is(ctx->bodies_host[i])) out[i] = obstacle_shifted(ctx->obst_host[i], st[i].D);
+   }
+   return SPH_HIP_OK;
+}
+} // namespace
+
 int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity)
 {
    if (!ctx) return SPH_HIP_ERR_INVALID;
@@ -1159,16 +1179,7 @@ int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int c
       return SPH_HIP_ERR_INVALID;
    }
    const int k = capacity < ctx->n_obst ? capacity : ctx->n_obst;
-   for (int i = 0; i < k; i++)
-      out[i] = obstacle_at(ctx->obst_host[i], i < ctx->n_motion ? &ctx->motion_host[i] : nullptr, ctx->motion_tau);
-   if (ctx->n_bodies > 0 && k > 0) {   // a body stands where the device has moved it to
-      BodyState st[SPH_HIP_MAX_OBSTACLES];
-      int rc = check_ctx(ctx);
-      if (rc) return rc;
-      if ((rc = read_body_states(ctx, st))) return rc;
-      for (int i = 0; i < k; i++)
-         if (body_is(ctx->bodies_host[i])) out[i] = obstacle_shifted(ctx->obst_host[i], st[i].D);
-   }
+   if (int rc = obstacles_now(ctx, out, k, nullptr)) return rc;
    return ctx->n_obst;
 }
 
@@ -1796,18 +1807,28 @@ int sph_hip_download_surface(sph_hip_context* ctx, float* vertices_xyz, float* n
 
 // ---- renderer -------------------------------------------------------------------------------------
 
-int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp, int width,
-                   int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
-                   int32_t* first_inside)
+namespace {
+
+// the solids a scene frame draws (null: sph_hip_render's frame)
+struct SceneDraw {
+   sph_hip_scene_params sp;
+   int n;               // solids in ctx->scene_list_host
+   int32_t* solid_id;   // host output, may be null
+};
+
+// The frame of both entry points, arguments checked: the row chunks, their scratch, the launches and the
+// copies.  `who` names the caller in an error text.
+int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                 int width, int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz,
+                 float* velocity_xyz, int32_t* first_inside, const SceneDraw* scene)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   if ((rc = sample_check(ctx, "sph_hip_render"))) return rc;
-   if (const char* why = render_check(cam, rp, width, height, flags)) return refuse(ctx, "sph_hip_render", why);
+   int rc;
    const size_t pixels = (size_t)width * height;
    const bool vel = (flags & SPH_HIP_RENDER_VELOCITY) != 0;
+   const bool solids = scene && scene->n > 0;
    if (velocity_xyz && !vel) memset(velocity_xyz, 0, sizeof(float) * 3 * pixels);
-   if (ctx->n == 0) {
+   if (scene && !solids && scene->solid_id) memset(scene->solid_id, 0xff, sizeof(int32_t) * pixels);
+   if (ctx->n == 0 && !solids) {
       // nothing resident (the cell arrays may still describe an earlier upload): every ray misses
       for (size_t i = 0; i < pixels; i++) {
          if (rgba) memcpy(rgba + 4 * i, rp->background, 4);
@@ -1818,11 +1839,12 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
       if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * pixels);
       return SPH_HIP_OK;
    }
-   if ((rc = sample_prepare(ctx))) return rc;
+   const bool fluid = ctx->n > 0;   // without a particle the solids are drawn over a background frame
+   if (fluid && (rc = sample_prepare(ctx))) return rc;
    hipStream_t st = ctx->stream;
    const CellGrid& g = ctx->grid;
    const bool skip = !ctx->render_noskip;
-   if (skip) {
+   if (fluid && skip) {
       if ((rc = ctx->render_occ.reserve(ctx, (size_t)g.ncells))) return rc;
       hipLaunchKernelGGL(k_render_occupancy, dim3(div_up(g.ncells, RENDER_THREADS)), dim3(RENDER_THREADS), 0, st,
                          ctx->cell_start, g, ctx->render_occ.get());
@@ -1830,8 +1852,8 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
    }
    // scratch of one row chunk (render_policy.h)
    const int rows = render_chunk_rows(width, height);
-   if ((rc = ctx->render_scratch.reserve(ctx, (size_t)render_scratch_bytes(width, rows),
-                                         "sph_hip_render: cannot allocate the chunk scratch")))
+   const std::string no_scratch = std::string(who) + ": cannot allocate the chunk scratch";
+   if ((rc = ctx->render_scratch.reserve(ctx, (size_t)render_scratch_bytes(width, rows), no_scratch.c_str())))
       return rc;
    const long long cp = (long long)width * rows;
    Carver carve{ctx->render_scratch};
@@ -1842,6 +1864,15 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
    int32_t* s_first = carve.take<int32_t>(cp * 4);
    int32_t* s_hits = carve.take<int32_t>(cp * 4);
    uint32_t* s_count = carve.take<uint32_t>(256);
+   int32_t* s_id = nullptr;
+   if (solids) {
+      // the scene pass's own scratch (scene_policy.h) and the list, on the device before the first chunk
+      if ((rc = ctx->scene_id.reserve(ctx, (size_t)(scene_id_bytes(width, rows) / 4), no_scratch.c_str()))) return rc;
+      if ((rc = ctx->scene_list.reserve(ctx, SPH_HIP_MAX_OBSTACLES))) return rc;
+      s_id = ctx->scene_id.get();
+      SPH_TRY(hipMemcpyAsync(ctx->scene_list.get(), ctx->scene_list_host, sizeof(SceneSolid) * (size_t)scene->n,
+                             hipMemcpyHostToDevice, st));
+   }
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
    const unsigned char* occ = skip ? ctx->render_occ.get() : nullptr;
@@ -1855,19 +1886,30 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
       F.rows = height - F.row0 < rows ? height - F.row0 : rows;
       const int chunk = width * F.rows;
       const int tiles = F.tiles_x * div_up(F.rows, RENDER_TILE);
-      SPH_TRY(hipMemsetAsync(s_count, 0, sizeof(uint32_t), st));
-      bind_flags([&](auto U, auto S) {
-         hipLaunchKernelGGL((k_render_march<U.value, S.value>), dim3(div_up(tiles, RENDER_THREADS / SPH_WAVE)),
-                            dim3(RENDER_THREADS), 0, st, F, ctx->posm[ctx->cur], ctx->cell_start, g, k, occ, s_rgba,
-                            s_depth, s_nrm, s_vel, s_first, s_hits, s_count);
-      }, unit, skip);
-      SPH_TRY(hipGetLastError());
-      bind_flags([&](auto U, auto S, auto V) {
-         hipLaunchKernelGGL((k_render_shade<U.value, S.value, V.value>), dim3(div_up(chunk, RENDER_THREADS)),
-                            dim3(RENDER_THREADS), 0, st, F, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start,
-                            g, k, occ, s_hits, s_count, s_first, s_rgba, s_depth, s_nrm, s_vel);
-      }, unit, skip, vel);
-      SPH_TRY(hipGetLastError());
+      if (fluid) {
+         SPH_TRY(hipMemsetAsync(s_count, 0, sizeof(uint32_t), st));
+         bind_flags([&](auto U, auto S) {
+            hipLaunchKernelGGL((k_render_march<U.value, S.value>), dim3(div_up(tiles, RENDER_THREADS / SPH_WAVE)),
+                               dim3(RENDER_THREADS), 0, st, F, ctx->posm[ctx->cur], ctx->cell_start, g, k, occ, s_rgba,
+                               s_depth, s_nrm, s_vel, s_first, s_hits, s_count);
+         }, unit, skip);
+         SPH_TRY(hipGetLastError());
+         bind_flags([&](auto U, auto S, auto V) {
+            hipLaunchKernelGGL((k_render_shade<U.value, S.value, V.value>), dim3(div_up(chunk, RENDER_THREADS)),
+                               dim3(RENDER_THREADS), 0, st, F, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start,
+                               g, k, occ, s_hits, s_count, s_first, s_rgba, s_depth, s_nrm, s_vel);
+         }, unit, skip, vel);
+         SPH_TRY(hipGetLastError());
+      }
+      if (solids) {
+         bind_flags([&](auto FILL) {
+            hipLaunchKernelGGL((k_scene_solids<FILL.value>), dim3(div_up(tiles, RENDER_THREADS / SPH_WAVE)),
+                               dim3(RENDER_THREADS), 0, st, F, scene->sp,
+                               reinterpret_cast<const uint32_t*>(ctx->scene_list.get()), scene->n, vel ? 1 : 0, s_rgba,
+                               s_depth, s_nrm, s_vel, s_first, s_id);
+         }, !fluid);
+         SPH_TRY(hipGetLastError());
+      }
       const size_t o = (size_t)F.row0 * width;
       if (rgba) SPH_TRY(hipMemcpyAsync(rgba + 4 * o, s_rgba, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
       if (depth) SPH_TRY(hipMemcpyAsync(depth + o, s_depth, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
@@ -1875,9 +1917,57 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
       if (velocity_xyz && vel)
          SPH_TRY(hipMemcpyAsync(velocity_xyz + 3 * o, s_vel, (size_t)chunk * 12, hipMemcpyDeviceToHost, st));
       if (first_inside) SPH_TRY(hipMemcpyAsync(first_inside + o, s_first, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
+      if (solids && scene->solid_id)
+         SPH_TRY(hipMemcpyAsync(scene->solid_id + o, s_id, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
    }
    SPH_TRY(hipStreamSynchronize(st));
    return SPH_HIP_OK;
+}
+
+} // namespace
+
+int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp, int width,
+                   int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
+                   int32_t* first_inside)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if ((rc = sample_check(ctx, "sph_hip_render"))) return rc;
+   if (const char* why = render_check(cam, rp, width, height, flags)) return refuse(ctx, "sph_hip_render", why);
+   return render_frame(ctx, "sph_hip_render", cam, rp, width, height, flags, rgba, depth, normal_xyz, velocity_xyz,
+                       first_inside, nullptr);
+}
+
+// ---- scene renderer (scene_kernels.h; decisions: scene_policy.h) ---------------------------------------
+
+int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                         const sph_hip_scene_params* sp, const float* solid_albedo_rgb, int n_albedo, int width,
+                         int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
+                         int32_t* first_inside, int32_t* solid_id)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if ((rc = sample_check(ctx, "sph_hip_render_scene"))) return rc;
+   if (const char* why = scene_check(cam, rp, sp, solid_albedo_rgb, n_albedo, ctx->n_obst, width, height, flags))
+      return refuse(ctx, "sph_hip_render_scene", why);
+   // the solids as they stand now (sph_hip_get_obstacles_now's list), their velocities and albedos
+   SceneDraw scene = {*sp, ctx->n_obst, solid_id};
+   sph_hip_obstacle now[SPH_HIP_MAX_OBSTACLES];
+   BodyState st[SPH_HIP_MAX_OBSTACLES];
+   if ((rc = obstacles_now(ctx, now, scene.n, st))) return rc;
+   for (int i = 0; i < scene.n; i++) {
+      SceneSolid& s = ctx->scene_list_host[i];
+      s.o = now[i];
+      if (ctx->n_bodies > 0 && body_is(ctx->bodies_host[i]))
+         for (int c = 0; c < 3; c++) s.vel[c] = st[i].V[c];
+      else if (i < ctx->n_motion)
+         scene_motion_velocity(ctx->motion_host[i], ctx->motion_tau, s.vel);
+      else
+         for (int c = 0; c < 3; c++) s.vel[c] = 0.0f;
+      for (int c = 0; c < 3; c++) s.alb[c] = n_albedo > 0 ? solid_albedo_rgb[3 * i + c] : sp->albedo[c];
+   }
+   return render_frame(ctx, "sph_hip_render_scene", cam, rp, width, height, flags, rgba, depth, normal_xyz,
+                       velocity_xyz, first_inside, &scene);
 }
 
 void* sph_hip_stream(sph_hip_context* ctx) { return ctx ? (void*)ctx->stream : nullptr; }

@@ -73,6 +73,12 @@ class SphRenderParams(C.Structure):
     ]
 
 
+class SphSceneParams(C.Structure):
+    """Mirror of sph_hip_scene_params (include/sph_hip.h: scene renderer): 20 bytes."""
+
+    _fields_ = [("albedo", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float)]
+
+
 from . import obstacles as _obstacles  # noqa: E402
 from .obstacles import SphBody, SphBodyState, SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of the C structs)
 from .gauges import GaugeReadings, GaugeRecord, SphGauge  # noqa: E402,F401
@@ -124,6 +130,9 @@ PROTOTYPES = {
     "sph_hip_download_surface": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_render": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_render_scene": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), _P(SphSceneParams), C.c_void_p,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_set_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_get_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_set_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int]),

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import gauges as _G
 from . import obstacles as _O
-from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, TracerPath, Tracers, _ptr, default_params
+from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, TracerPath, Tracers, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
@@ -44,8 +44,10 @@ SurfaceMesh = collections.namedtuple("SurfaceMesh", ["vertices", "triangles", "n
 RENDER_VELOCITY = 1   # SPH_HIP_RENDER_VELOCITY (include/sph_hip.h)
 
 # sph_hip_render's frame: rgba (H, W, 4) uint8, depth (H, W) float32, normal (H, W, 3) float32,
-# velocity (H, W, 3) float32 or None where not asked for, first_inside (H, W) int32
-RenderResult = collections.namedtuple("RenderResult", ["rgba", "depth", "normal", "velocity", "first_inside"])
+# velocity (H, W, 3) float32 or None where not asked for, first_inside (H, W) int32; solid_id (H, W) int32 -
+# the obstacle a pixel shows, -1 for none - from sph_hip_render_scene (render(..., solids=True)), else None
+RenderResult = collections.namedtuple("RenderResult", ["rgba", "depth", "normal", "velocity", "first_inside",
+                                                       "solid_id"], defaults=[None])
 
 
 class Camera:
@@ -464,11 +466,16 @@ class SPH(Context):
 
     def render(self, camera, width, height, iso, step=None, refine=8, grad_step=None, box=None,
                light=(0.4, 0.8, 0.45), albedo=(0.25, 0.55, 0.9), ambient=0.2, diffuse=0.8,
-               background=(0, 0, 0, 255), velocity=False, max_samples=1 << 16):
+               background=(0, 0, 0, 255), velocity=False, max_samples=1 << 16, solids=False,
+               solid_albedo=(0.72, 0.72, 0.72), solid_colors=None, solid_ambient=None, solid_diffuse=None):
         """Ray-march the surface {density > iso} of the current state into a width x height image on
         the device (include/sph_hip.h: renderer): a RenderResult of numpy arrays.  step and
         grad_step default to h / 2, the box to the particle bounds [0, max] grown by h on every
-        side; the simulation is not changed by the call."""
+        side; the simulation is not changed by the call.
+        solids=True draws the context's obstacles, where they stand now, into the frame with the fluid
+        (include/sph_hip.h: scene renderer) and fills RenderResult.solid_id: solid_albedo for every
+        solid, or solid_colors, one RGB albedo per obstacle; solid_ambient / solid_diffuse default to the
+        fluid's."""
         rp = self.renderParams(iso, step, refine, grad_step, box, light, albedo, ambient, diffuse, background,
                                max_samples)
         W, H = int(width), int(height)
@@ -480,9 +487,21 @@ class SPH(Context):
         vel = np.zeros((H, W, 3), np.float32) if velocity else None
         first = np.zeros((H, W), np.int32)
         cam = camera.as_struct()
-        self.call("sph_hip_render", C.byref(cam), C.byref(rp), W, H, RENDER_VELOCITY if velocity else 0,
-                  _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first))
-        return RenderResult(rgba, depth, normal, vel, first)
+        flags = RENDER_VELOCITY if velocity else 0
+        if not solids:
+            self.call("sph_hip_render", C.byref(cam), C.byref(rp), W, H, flags,
+                      _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first))
+            return RenderResult(rgba, depth, normal, vel, first)
+        sp = SphSceneParams()
+        sp.albedo[:] = [float(v) for v in solid_albedo]
+        sp.ambient = float(ambient if solid_ambient is None else solid_ambient)
+        sp.diffuse = float(diffuse if solid_diffuse is None else solid_diffuse)
+        colors = None if solid_colors is None else np.ascontiguousarray(solid_colors, np.float32).reshape(-1, 3)
+        solid_id = np.zeros((H, W), np.int32)
+        self.call("sph_hip_render_scene", C.byref(cam), C.byref(rp), C.byref(sp), _ptr(colors),
+                  0 if colors is None else colors.shape[0], W, H, flags,
+                  _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first), _ptr(solid_id))
+        return RenderResult(rgba, depth, normal, vel, first, solid_id)
 
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
