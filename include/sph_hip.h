@@ -822,6 +822,79 @@ int sph_hip_record_gauges(sph_hip_context* ctx, int rows, int every);
 int sph_hip_get_gauge_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_gauge_reading* out,
                              int32_t* steps_done);
 
+/* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
+ *
+ * A particle count that changes while the steps stay queued: emitters append whole lattice layers
+ * of new particles, sinks remove the particles that stand inside a box.  No counterpart in the
+ * reference.  The operation-by-operation contract is in csrc/port_policy.h; all arithmetic is fp32,
+ * unfused, in the order written.
+ *   emitter   a = axis, u = (a + 1) % 3, w = (a + 2) % 3.  A layer is count = {nu, nw} points on the
+ *             plane x_a = origin[a]: point k has i = k % nu, j = k / nu, x_u = origin[u] +
+ *             (float)i * spacing, x_w = origin[w] + (float)j * spacing.  Every point enters with the
+ *             emitter's velocity and mass.  Emitter e fires in port step s when s >= first,
+ *             (s - first) % every == 0 and it has fired fewer than `layers` times (layers = -1: no
+ *             limit).  s counts the steps of sph_hip_step / sph_hip_run since the ports were set or
+ *             the state was uploaded, from 0.
+ *   ids       the context keeps next_id: an upload sets it to n, an upload with ids to the largest
+ *             id + 1.  The emitters that fire in a step take ids in list order, point k of emitter e
+ *             gets id_base_e + k.  A step whose ids would reach 0xffffffff is refused.
+ *   sink      the box lo <= x < hi on all three axes (NaN is never inside).  A particle inside several
+ *             sinks counts for the one with the lowest index.
+ *   order     at the start of a step, before its cell build: the sinks look at the particles the last
+ *             step left and remove those inside; then the firing emitters' layers are appended.  A
+ *             layer is never caught in the step it enters, and it takes part in that whole step: cell
+ *             build, sums, integrate.  Sinks act at the START of a step only: whatever stands inside a
+ *             sink after the last step of a run is still there and is read back.
+ *   capacity  a layer that does not fit the context's capacity is never emitted in part: the step is
+ *             refused with SPH_HIP_ERR_CAPACITY before anything of it is enqueued (the call first
+ *             waits for the queued steps and counts what the sinks have freed).  sph_hip_run returns
+ *             at that step, the earlier steps stand, and the schedule does not advance.
+ *   route     a context with ports gives up the prehash and the fused integrate: its steps take the
+ *             separate integrate kernel and hash in the cell build, plus one launch of
+ *             k_ports_apply in front of the build.  Results are bit-identical to the default route.
+ *             A context without ports enqueues exactly what it always did.
+ *   with      obstacles, motions, bodies, load recordings, tracers, gauges, the sampler, the surface
+ *             extractor and both renderers work on a port context unchanged.  The stand-alone phase
+ *             calls (sph_hip_voxelize ... sph_hip_integrate) apply no ports.
+ *   not done  REF contexts, slab contexts and contexts that have exchanged are refused.  From the first
+ *             step with a sink or a firing emitter until the next upload the ids are no longer 0..n-1:
+ *             sph_hip_download and sph_hip_download_async are refused and name sph_hip_download_live.
+ * sph_hip_set_ports replaces both lists (ne = ns = 0 clears them) and restarts the schedule, the totals
+ * and the port step count at 0; an upload does the same and keeps the lists.  SPH_HIP_ERR_INVALID, the
+ * previous lists kept, for everything port_check (csrc/port_policy.h) refuses.
+ * sph_hip_get_ports synchronises; copies up to capacity_e emitters and capacity_s sinks; emitted[e] =
+ * particles emitter e has added, removed[s] = particles sink s has caught (arrays of
+ * SPH_HIP_MAX_EMITTERS / SPH_HIP_MAX_SINKS entries, each may be NULL); *live = the resident particles,
+ * *next_id.  Returns ne | ns << 8.
+ * sph_hip_download_live is the compact read-back: synchronises, *rows = the live count, and - when that
+ * is at most max_rows - the particles in device order with their ids; every array may be NULL.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no struct and no existing
+ * prototype changed. */
+#define SPH_HIP_MAX_EMITTERS 8
+#define SPH_HIP_MAX_SINKS    8
+#define SPH_HIP_MAX_EMITTER_POINTS 65536
+typedef struct sph_hip_emitter {   /* field order is ABI: 56 bytes */
+   int32_t axis;          /* normal of the lattice plane, 0..2 */
+   float origin[3];
+   int32_t count[2];      /* nu, nw; nu * nw <= SPH_HIP_MAX_EMITTER_POINTS */
+   float spacing;
+   float velocity[3];
+   float mass;
+   int32_t first;         /* first port step that fires */
+   int32_t every;         /* then every every-th */
+   int32_t layers;        /* at most this many layers; -1 = no limit */
+} sph_hip_emitter;
+typedef struct sph_hip_sink {      /* 24 bytes */
+   float lo[3];
+   float hi[3];
+} sph_hip_sink;
+int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int ne, const sph_hip_sink* sinks,
+                      int ns);
+int sph_hip_get_ports(sph_hip_context* ctx, sph_hip_emitter* emitters, sph_hip_sink* sinks, int capacity_e,
+                      int capacity_s, int64_t* emitted, int64_t* removed, int32_t* live, uint32_t* next_id);
+int sph_hip_download_live(sph_hip_context* ctx, int max_rows, int32_t* rows, uint32_t* ids, float* pos, float* vel,
+                          float* density, float* acc, int32_t* neighbor_count);
+
 /* ---- multi-GPU: 1-D slab decomposition of the FULL-mode cell grid ------------------------- *
  *
  * No counterpart in the reference (one process, one thread).  One context per GPU owns the

@@ -10,4 +10,5 @@ from .lib import TIMING_OFF, TIMING_SUMS, TIMING_PHASES  # noqa: F401
 from .lib import Loads, LOAD_SOLIDS  # noqa: F401
 from .lib import Tracers, TracerPath  # noqa: F401
 from .gauges import PointGauge, ColumnGauge, SectionGauge, GaugeReadings, GaugeRecord  # noqa: F401
-from . import gauges, obstacles, scenes  # noqa: F401
+from .ports import Emitter, Sink, PortTotals  # noqa: F401
+from . import gauges, obstacles, ports, scenes  # noqa: F401

@@ -23,6 +23,7 @@
 #include "scene_kernels.h"
 #include "tracer_kernels.h"
 #include "gauge_kernels.h"
+#include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
 
@@ -377,6 +378,33 @@ struct sph_hip_context {
    DevBuf<sph_hip_gauge_reading> grec_dev;
    int grec_rows = 0, grec_every = 1, grec_filled = 0;
    long long grec_step = 0;
+
+   // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
+   // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the
+   // emitted totals (host-known) and the removed totals (device, one int64 per sink)
+   sph_hip_emitter emit_host[SPH_HIP_MAX_EMITTERS];
+   sph_hip_sink sink_host[SPH_HIP_MAX_SINKS];
+   int n_emit = 0, n_sink = 0;
+   DevBuf<sph_hip_emitter> emit_dev;
+   PinnedBuf<sph_hip_emitter> emit_stage;
+   Event ev_emit_copied;
+   int emit_copy_pending = 0;
+   DevBuf<sph_hip_sink> sink_dev;
+   PinnedBuf<sph_hip_sink> sink_stage;
+   Event ev_sink_copied;
+   int sink_copy_pending = 0;
+   DevBuf<unsigned long long> removed_dev;   // SPH_HIP_MAX_SINKS
+   long long port_step = 0;
+   long long port_fired[SPH_HIP_MAX_EMITTERS] = {0};
+   long long port_emitted[SPH_HIP_MAX_EMITTERS] = {0};
+   uint32_t next_id = 0;
+   int ports_seen = 0;        // ports have been set since the creation: counts are read from the device
+   int ids_changed = 0;       // a step with a sink or a firing emitter since the last upload: ids are not 0..n-1
+   int n_in_stale = 0;        // meta[META_N_IN] is what the last port step's build read, not n_live
+   // the uploaded masses, for the uniform-mass rule with emitters: known (host masses were given), and the
+   // first one - the value of them all while uniform_mass holds
+   int upload_mass_known = 0;
+   float upload_mass = 0.0f;
 };
 
 namespace {
@@ -601,6 +629,14 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    CREATE_TRY(pinned_alloc(ctx->body_state_stage, SPH_HIP_MAX_OBSTACLES));
    CREATE_TRY(event_create(ctx->ev_body_state_copied));
    CREATE_TRY(dev_alloc(ctx->body_rows, 2 * LOAD_ROW_WORDS));
+   CREATE_TRY(dev_alloc(ctx->emit_dev, SPH_HIP_MAX_EMITTERS));
+   CREATE_TRY(pinned_alloc(ctx->emit_stage, SPH_HIP_MAX_EMITTERS));
+   CREATE_TRY(event_create(ctx->ev_emit_copied));
+   CREATE_TRY(dev_alloc(ctx->sink_dev, SPH_HIP_MAX_SINKS));
+   CREATE_TRY(pinned_alloc(ctx->sink_stage, SPH_HIP_MAX_SINKS));
+   CREATE_TRY(event_create(ctx->ev_sink_copied));
+   CREATE_TRY(dev_alloc(ctx->removed_dev, SPH_HIP_MAX_SINKS));
+   CREATE_TRY(hipMemsetAsync(ctx->removed_dev, 0, SPH_HIP_MAX_SINKS * sizeof(unsigned long long), ctx->stream));
    CREATE_TRY(hipStreamSynchronize(ctx->stream));
 #undef CREATE_TRY
    *out = ctx.release();

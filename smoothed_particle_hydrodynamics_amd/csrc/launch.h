@@ -205,6 +205,87 @@ void pick_tile_caps(sph_hip_context* ctx)
               fb[TSTAT_BLOCKS], fb[TSTAT_MAX], caps.cap_density, caps.cap_accel);
 }
 
+// ---- ports (port_kernels.h; the contract and the decisions: port_policy.h, launch_policy.h) ----------------
+// the cell grid as port_policy.h takes it
+PortGrid port_grid(const sph_hip_context* ctx)
+{
+   const CellGrid& g = ctx->grid;
+   return {g.nx, g.ny, g.nz_global, g.inv, g.z0, g.nz};
+}
+
+// Waits for the steps enqueued so far and reads the device's counts: the host bound ctx->n becomes n_live and
+// n_owned the owned count (the same number on a context that holds the whole grid).
+int ports_tighten(sph_hip_context* ctx, int32_t* meta_out = nullptr)
+{
+   int32_t meta[META_COUNT];
+   SPH_TRY(hipMemcpyAsync(meta, ctx->meta, sizeof(meta), hipMemcpyDeviceToHost, ctx->stream));
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   ctx->n = meta[META_N_LIVE];
+   ctx->n_owned = meta[META_OWN_END] - meta[META_OWN_BEGIN];
+   if (meta_out) memcpy(meta_out, meta, sizeof(meta));
+   return SPH_HIP_OK;
+}
+
+void launch_ports_kernel(sph_hip_context* ctx, int ns, const PortFiring& f, int bound)
+{
+   const int sink_blocks = bound > 0 ? div_up(bound, PORT_THREADS) : 1;
+   hipLaunchKernelGGL(k_ports_apply, dim3(sink_blocks + div_up(f.m, PORT_THREADS)), dim3(PORT_THREADS), 0, ctx->stream,
+                      ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->meta, ctx->sink_dev, ns, ctx->emit_dev, f,
+                      sink_blocks, ctx->capacity, ctx->removed_dev);
+}
+
+// After a port step's build meta[META_N_IN] is that build's input count, which dropped entries make larger
+// than n_live: a build that no port launch precedes (a phase call, the sampler's, the first step after the
+// ports were cleared) sets it right first - k_ports_apply with nothing to catch and nothing to append.
+int launch_ports_reset(sph_hip_context* ctx)
+{
+   const PortFiring none = {};
+   launch_ports_kernel(ctx, 0, none, 0);
+   SPH_TRY(hipGetLastError());
+   ctx->n_in_stale = 0;
+   return SPH_HIP_OK;
+}
+
+// The firing table of the step about to be enqueued, and whether its layers fit - decided before anything of
+// the step is enqueued.  The host bound first; where that does not settle it, the device's own count.
+int ports_plan(sph_hip_context* ctx, PortFiring& f)
+{
+   f = port_plan(ctx->emit_host, ctx->n_emit, ctx->port_step, ctx->port_fired, ctx->next_id);
+   if (f.m == 0) return SPH_HIP_OK;
+   if (!port_ids_fit(ctx->next_id, f.m)) {
+      ctx->err = "sph_hip_step: the emitters have used up the particle ids (the next layer would reach 0xffffffff)";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if (!ports_must_tighten(ctx->n, f.m, ctx->capacity)) return SPH_HIP_OK;
+   int rc = ports_tighten(ctx);
+   if (rc) return rc;
+   if (ports_layer_fits(ctx->n, f.m, ctx->capacity)) return SPH_HIP_OK;
+   ctx->err = "sph_hip_step: port step " + std::to_string(ctx->port_step) + " would emit " + std::to_string(f.m) +
+              " particles on top of " + std::to_string(ctx->n) + " live ones, more than the context capacity " +
+              std::to_string(ctx->capacity) + ": nothing of the step was enqueued";
+   return SPH_HIP_ERR_CAPACITY;
+}
+
+// The step's port launch, in front of its cell build, and the host's side of it: the schedule, the ids, the
+// emitted totals and the bound move on.
+int launch_ports(sph_hip_context* ctx, const PortFiring& f)
+{
+   launch_ports_kernel(ctx, ctx->n_sink, f, ctx->n);
+   SPH_TRY(hipGetLastError());
+   for (int q = 0; q < f.n; q++) {
+      const int e = f.emitter[q];
+      ctx->port_fired[e]++;
+      ctx->port_emitted[e] += port_points(ctx->emit_host[e]);
+   }
+   ctx->n += f.m;
+   ctx->next_id += (uint32_t)f.m;
+   ctx->port_step++;
+   ctx->n_in_stale = 0;
+   if (ctx->n_sink > 0) ctx->may_hold_dead = 1;   // the build that follows drops the caught entries
+   if (ctx->n_sink > 0 || f.m > 0) ctx->ids_changed = 1;
+   return SPH_HIP_OK;
+}
+
 // what the cell build has to know about the slab's neighbours
 SlabZone slab_zone(const sph_hip_context* ctx)
 {
@@ -223,6 +304,10 @@ SlabZone slab_zone(const sph_hip_context* ctx)
 int launch_cell_build(sph_hip_context* ctx, void* clear_left = nullptr, void* clear_right = nullptr,
                       bool keep_sums = false)
 {
+   if (ctx->n_in_stale) {
+      int rc = launch_ports_reset(ctx);
+      if (rc) return rc;
+   }
    const int n = ctx->n;  // host upper bound of entries; the exact count is meta[META_N_IN]
    if (n == 0) return SPH_HIP_OK;
    const int blocks = div_up(n, 256);
@@ -768,9 +853,15 @@ int step_impl(sph_hip_context* ctx, bool timed)
    int rc;
    hipStream_t st = ctx->stream;
    StepEvents se;
+   // ports: what fires is planned - and a layer that does not fit refused - before anything is enqueued
+   const bool ports = ports_active(ctx->n_emit, ctx->n_sink);
+   PortFiring firing = {};
+   if (ports && (rc = ports_plan(ctx, firing))) return rc;
    if ((rc = open_step(ctx, timed, se))) return rc;
    if ((rc = mark_phase(ctx, se, 0, st))) return rc;
+   if (ports && (rc = launch_ports(ctx, firing))) return rc;
    if ((rc = launch_cell_build(ctx))) return rc;
+   if (ports) ctx->n_in_stale = 1;
    if (ctx->n_tracers > 0 && (rc = launch_tracers(ctx))) return rc;   // in S_k, before anything moves
    if (ctx->grec_rows > 0 && (rc = launch_gauges(ctx))) return rc;    // likewise
    if ((rc = mark_phase(ctx, se, 1, st))) return rc;
@@ -781,7 +872,8 @@ int step_impl(sph_hip_context* ctx, bool timed)
    // a context that holds the whole grid and has never exchanged anything: the integrate also
    // hashes and counts for the next cell build - and the tiled acceleration pass does both itself
    const bool hash_too = ctx->mode == SPH_HIP_MODE_FULL && !ctx->had_exchange && ctx->plane_lo == 0 &&
-                         ctx->plane_hi == ctx->grid.nz_global && !ctx->no_prehash;
+                         ctx->plane_hi == ctx->grid.nz_global &&
+                         !ports_no_prehash(ctx->no_prehash != 0, ctx->n_emit, ctx->n_sink);
    const bool fused = fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
                                      loads_pending(ctx));
    if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;

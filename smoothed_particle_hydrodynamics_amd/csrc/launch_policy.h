@@ -300,6 +300,26 @@ inline bool motion_clock_runs(int n_obstacles, int n_moving, int n_rotating)
    return n_obstacles > 0 && (n_moving > 0 || n_rotating > 0);
 }
 
+// ---- ports (port_policy.h) ------------------------------------------------------------------
+// Whether a step launches k_ports_apply in front of its cell build: some emitter or sink is set.  Then it
+// runs every step, because after a build meta[META_N_IN] is stale and must be reset to n_live even when
+// nothing fires.  A context without ports launches what it always launched.
+inline bool ports_active(int n_emitters, int n_sinks) { return n_emitters > 0 || n_sinks > 0; }
+
+// A context with ports never prehashes: its integrate cannot count for a build whose entries the ports
+// change first.  (fuse_integrate(hash_too = false, ...) is then false by itself.)
+inline bool ports_no_prehash(bool no_prehash_switch, int n_emitters, int n_sinks)
+{
+   return no_prehash_switch || ports_active(n_emitters, n_sinks);
+}
+
+// The host bound: ctx->n stays an upper bound of meta[META_N_IN]; each step adds the m it enqueues.
+// Whether a step of m new points must first wait for the queued steps and tighten the bound to n_live ...
+inline bool ports_must_tighten(int bound, int m, int capacity) { return (long long)bound + m > (long long)capacity; }
+// ... and whether, with the live count known, the step is enqueued at all (else SPH_HIP_ERR_CAPACITY: no
+// partial layer is ever emitted)
+inline bool ports_layer_fits(int live, int m, int capacity) { return (long long)live + m <= (long long)capacity; }
+
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
 // slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary

@@ -15,6 +15,13 @@ extern "C" __global__ void k_msg_fill(const SlabMsg* __restrict__ left, const Sl
 
 namespace {
 
+// ports (port_policy.h) change one context's count between its own steps: a context that holds some cannot be a slab
+int refuse_ports(sph_hip_context* ctx)
+{
+   ctx->err = "a context with ports (sph_hip_set_ports) cannot exchange with neighbouring slabs";
+   return SPH_HIP_ERR_INVALID;
+}
+
 // free bodies (body_policy.h) are advanced from one context's rows: a context that holds some cannot be a slab
 int refuse_bodies(sph_hip_context* ctx)
 {
@@ -28,6 +35,7 @@ int slab_pack(sph_hip_context* ctx, void* left_device, void* right_device,
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
+   if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
    hipStream_t st = ctx->stream;
    ctx->had_exchange = 1;
    if ((rc = drop_prehash(ctx))) return rc;
@@ -49,6 +57,7 @@ int slab_unpack(sph_hip_context* ctx, const void* left_device, const void* right
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
+   if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
    ctx->had_exchange = 1;
    // (a slab's fused step has hashed its owned entries for the next build, which hashes what is
    // unpacked here: that stays; a whole-grid prehash knows nothing of new entries)
@@ -68,6 +77,7 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
+   if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
    if (!ctx->use_tiled) {
       ctx->err = "sph_hip_slab_step_begin: needs the tiled kernels (SPH_HIP_UNTILED is set)";
       return SPH_HIP_ERR_INVALID;

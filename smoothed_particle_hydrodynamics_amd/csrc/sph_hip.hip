@@ -315,6 +315,40 @@ int sph_hip_get_params(const sph_hip_context* ctx, sph_hip_params* out)
    return SPH_HIP_OK;
 }
 
+// The uniform-mass rule with emitters (port_policy.h): a context whose resident particles all have one mass
+// keeps skipping the mass gather only while every emitter's mass equals it in bits.  nothing_resident: an
+// upload of no particles that nothing has been emitted into - the emitters' own agreement decides, and their
+// mass becomes the resident one.  Results are bit-identical either way.
+static void ports_mass_rule(sph_hip_context* ctx, bool nothing_resident)
+{
+   if (ctx->n_emit == 0) return;
+   const float m0 = ctx->emit_host[0].mass;
+   if (nothing_resident) {
+      int same = 1;
+      for (int e = 1; e < ctx->n_emit; e++) same &= memcmp(&ctx->emit_host[e].mass, &m0, sizeof(float)) == 0;
+      ctx->uniform_mass = same;
+      ctx->upload_mass_known = 1;
+      ctx->upload_mass = m0;
+      return;
+   }
+   if (!ctx->uniform_mass) return;
+   if (!ctx->upload_mass_known) {
+      ctx->uniform_mass = 0;
+      return;
+   }
+   for (int e = 0; e < ctx->n_emit; e++)
+      if (memcmp(&ctx->emit_host[e].mass, &ctx->upload_mass, sizeof(float)) != 0) ctx->uniform_mass = 0;
+}
+
+// the port schedule, the totals and the id bookkeeping start over (sph_hip_set_ports, every upload)
+static int ports_restart(sph_hip_context* ctx)
+{
+   ctx->port_step = 0;
+   for (int e = 0; e < SPH_HIP_MAX_EMITTERS; e++) ctx->port_fired[e] = ctx->port_emitted[e] = 0;
+   SPH_TRY(hipMemsetAsync(ctx->removed_dev, 0, SPH_HIP_MAX_SINKS * sizeof(unsigned long long), ctx->stream));
+   return SPH_HIP_OK;
+}
+
 // shared by sph_hip_upload (ids = 0..n-1) and sph_hip_slab_upload (caller's global ids)
 static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const float* vel,
                        const float* mass, const uint32_t* ids, int uniform_mass,
@@ -336,6 +370,22 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    ctx->n_owned = n;
    ctx->cur = 0;
    ctx->uniform_mass = uniform_mass;
+   // ports: the ids start over behind the uploaded ones, the schedule at step 0, with the lists kept
+   ctx->next_id = (uint32_t)n;
+   if (ids && n > 0) {
+      uint32_t most = 0;
+      for (int i = 0; i < n; i++) most = ids[i] > most ? ids[i] : most;
+      ctx->next_id = most + 1u;
+   }
+   ctx->ids_changed = 0;
+   ctx->n_in_stale = 0;
+   ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
+   ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
+   ports_mass_rule(ctx, n == 0);
+   if (ctx->ports_seen) {
+      int rc_ports = ports_restart(ctx);
+      if (rc_ports) return rc_ports;
+   }
    ctx->ev_steps = 0;
    ctx->err_watch[0] = 0;   // (the upload clears the device's error word below)
    ctx->watch_pending = 0;
@@ -457,7 +507,28 @@ int sph_hip_download(sph_hip_context* ctx, float* pos, float* vel, float* densit
       ctx->err = "sph_hip_download: slab contexts use sph_hip_slab_download";
       return SPH_HIP_ERR_INVALID;
    }
+   if (ctx->ids_changed)
+      return refuse(ctx, "sph_hip_download", "ports have changed the particle set, the ids are no longer 0..n-1 until "
+                                             "the next upload: use sph_hip_download_live");
    return download_impl(ctx, 0, ctx->n_owned, nullptr, pos, vel, density, acc, neighbor_count);
+}
+
+int sph_hip_download_live(sph_hip_context* ctx, int max_rows, int32_t* rows, uint32_t* ids, float* pos, float* vel,
+                          float* density, float* acc, int32_t* neighbor_count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (ctx->mode != SPH_HIP_MODE_FULL || !(ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global))
+      return refuse(ctx, "sph_hip_download_live", "FULL and FULL_FAST contexts that hold the whole grid only");
+   if (max_rows < 0) return refuse(ctx, "sph_hip_download_live", "negative max_rows");
+   // the device's count, and the host bound with it (launch.h: ports_tighten)
+   if ((rc = ports_tighten(ctx))) return rc;
+   if (rows) *rows = ctx->n_owned;
+   if (ctx->n_owned > max_rows) {
+      ctx->err = "sph_hip_download_live: caller's arrays are too small";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   return download_impl(ctx, 1, ctx->n_owned, ids, pos, vel, density, acc, neighbor_count);
 }
 
 // ---- asynchronous host mirror ---------------------------------------------------------------
@@ -513,6 +584,9 @@ int sph_hip_download_async(sph_hip_context* ctx, float* pos, float* vel, float* 
       ctx->err = "sph_hip_download_async: whole-grid contexts only";
       return SPH_HIP_ERR_INVALID;
    }
+   if (ctx->ids_changed)
+      return refuse(ctx, "sph_hip_download_async", "ports have changed the particle set, the ids are no longer 0..n-1 "
+                                                   "until the next upload: use sph_hip_download_live");
    // the previous mirror is still on its way: this request is dropped (a mirror is a picture of
    // the latest state, not a queue) - its staging must not be overwritten under the copy
    rc = sph_hip_download_done(ctx, 0);
@@ -1051,6 +1125,59 @@ int sph_hip_get_gauge_record(sph_hip_context* ctx, int first_row, int n_rows, sp
                         sizeof(sph_hip_gauge_reading) * row * (size_t)n_rows, hipMemcpyDeviceToHost));
    for (int r = 0; steps_done && r < n_rows; r++) steps_done[r] = gauge_record_steps_done(first_row + r, ctx->grec_every);
    return ctx->grec_filled;
+}
+
+// ---- ports (port_kernels.h; contract: port_policy.h; routes: launch_policy.h ports_active) -----------
+int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int ne, const sph_hip_sink* sinks, int ns)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_ports";
+   if (ctx->mode != SPH_HIP_MODE_FULL) return refuse(ctx, who, "FULL and FULL_FAST contexts only");
+   if (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange)
+      return refuse(ctx, who, "slab contexts (with neighbours, or that have exchanged) cannot have ports");
+   if (const char* why = port_check(emitters, ne, sinks, ns, port_grid(ctx))) return refuse(ctx, who, why);
+   // a pending prehash counted for a build whose entries the ports may change first
+   if ((rc = drop_prehash(ctx))) return rc;
+   // steps already queued keep the lists they were enqueued with: the copies go behind them
+   if (ne > 0 && (rc = stage_list(ctx, emitters, ne, ctx->emit_stage, ctx->emit_dev, ctx->ev_emit_copied,
+                                  ctx->emit_copy_pending)))
+      return rc;
+   if (ns > 0 && (rc = stage_list(ctx, sinks, ns, ctx->sink_stage, ctx->sink_dev, ctx->ev_sink_copied,
+                                  ctx->sink_copy_pending)))
+      return rc;
+   if (ne > 0) memcpy(ctx->emit_host, emitters, sizeof(sph_hip_emitter) * (size_t)ne);
+   if (ns > 0) memcpy(ctx->sink_host, sinks, sizeof(sph_hip_sink) * (size_t)ns);
+   ctx->n_emit = ne;
+   ctx->n_sink = ns;
+   if (ports_active(ne, ns)) ctx->ports_seen = 1;
+   if ((rc = ports_restart(ctx))) return rc;
+   ports_mass_rule(ctx, ctx->n == 0 && !ctx->ids_changed);
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_ports(sph_hip_context* ctx, sph_hip_emitter* emitters, sph_hip_sink* sinks, int capacity_e,
+                      int capacity_s, int64_t* emitted, int64_t* removed, int32_t* live, uint32_t* next_id)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (capacity_e < 0 || capacity_s < 0 || (capacity_e > 0 && !emitters) || (capacity_s > 0 && !sinks))
+      return refuse(ctx, "sph_hip_get_ports", "negative capacity or null array");
+   int32_t meta[META_COUNT];
+   if ((rc = ports_tighten(ctx, meta))) return rc;
+   const int me = ctx->n_emit < capacity_e ? ctx->n_emit : capacity_e;
+   const int ms = ctx->n_sink < capacity_s ? ctx->n_sink : capacity_s;
+   if (me > 0) memcpy(emitters, ctx->emit_host, sizeof(sph_hip_emitter) * (size_t)me);
+   if (ms > 0) memcpy(sinks, ctx->sink_host, sizeof(sph_hip_sink) * (size_t)ms);
+   if (emitted)
+      for (int e = 0; e < SPH_HIP_MAX_EMITTERS; e++) emitted[e] = (int64_t)ctx->port_emitted[e];
+   if (removed) {
+      static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the removed totals are int64");
+      SPH_TRY(hipMemcpy(removed, ctx->removed_dev, SPH_HIP_MAX_SINKS * sizeof(int64_t), hipMemcpyDeviceToHost));
+   }
+   if (live) *live = meta[META_N_LIVE];
+   if (next_id) *next_id = ctx->next_id;
+   return ctx->n_emit | (ctx->n_sink << 8);
 }
 
 // ---- static obstacles (obstacle_policy.h; routes: launch_policy.h fuse_integrate / fuse_slab_step) ----

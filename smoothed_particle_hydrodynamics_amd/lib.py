@@ -82,6 +82,7 @@ class SphSceneParams(C.Structure):
 from . import obstacles as _obstacles  # noqa: E402
 from .obstacles import SphBody, SphBodyState, SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of the C structs)
 from .gauges import GaugeReadings, GaugeRecord, SphGauge  # noqa: E402,F401
+from .ports import PortTotals, SphEmitter, SphSink  # noqa: E402,F401
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -152,6 +153,11 @@ PROTOTYPES = {
     "sph_hip_read_gauges": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_record_gauges": (C.c_int, [_ctx, C.c_int, C.c_int]),
     "sph_hip_get_gauge_record": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sph_hip_set_ports": (C.c_int, [_ctx, _P(SphEmitter), C.c_int, _P(SphSink), C.c_int]),
+    "sph_hip_get_ports": (C.c_int, [_ctx, _P(SphEmitter), _P(SphSink), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                    _P(C.c_int32), _P(C.c_uint32)]),
+    "sph_hip_download_live": (C.c_int, [_ctx, C.c_int, _P(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

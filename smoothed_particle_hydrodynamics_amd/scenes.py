@@ -346,3 +346,50 @@ def dam_break_gauged(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), n
     gauges.append(SectionGauge((0.2 * box[0], 0.0, 0.0), 0, (s, s), (nu, nv), iso))
     gauges.append(PointGauge((0.5 * column[0], 0.5 * column[1], 0.5 * column[2])))
     return p, pos, vel, mass, gauges
+
+
+def filling_tank(capacity, box=(1.0, 1.0, 1.0), inlet=1.0 / 3.0, speed=2.0, neighbors=32.0, gravity=-9.81):
+    """An empty tank (gravity along -y, the walls on) that fills through an inlet under its lid: one Emitter with
+    normal y, a square lattice `inlet` of the tank's width across, centred, one kernel radius below the lid,
+    blowing downward at `speed`.  The smoothing length is the one at which `capacity` particles filling the
+    whole tank would have ~`neighbors` neighbours, the lattice spacing that fluid's own; a layer enters every
+    round(spacing / (speed * time_step)) steps, so that successive layers are one spacing apart.  Create the
+    context with this capacity and upload the empty arrays.  Returns (params, pos, vel, mass, [Emitter], []):
+    setParticles, then setPorts."""
+    from .ports import Emitter
+    p, _ = dam_break_params(capacity, box, (1.0, 1.0, 1.0), neighbors)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    s = (box[0] * box[1] * box[2] / float(capacity)) ** (1.0 / 3.0)
+    nu = max(1, int(math.floor(inlet * box[2] / s)))
+    nw = max(1, int(math.floor(inlet * box[0] / s)))
+    every = max(1, int(round(s / (speed * float(p.time_step)))))
+    origin = (0.5 * (box[0] - (nw - 1) * s), box[1] - float(p.h), 0.5 * (box[2] - (nu - 1) * s))
+    emitter = Emitter(1, origin, (nu, nw), s, (0.0, -speed, 0.0), 1.0, 0, every, -1)
+    empty = np.zeros(0, np.float32)
+    return p, empty, empty.copy(), empty.copy(), [emitter], []
+
+
+def channel_flow(n, box=(2.0, 0.5, 0.5), depth=0.5, speed=1.0, neighbors=32.0, gravity=-9.81):
+    """An open channel (gravity along -y, the walls on): a block of n particles at rest filling the channel's
+    whole length to `depth` of its height, an inlet face upstream - one Emitter with normal x half a spacing
+    from the upstream wall, a lattice over the wet cross-section, blowing along +x at `speed` - and a sink slab
+    downstream: the last two kernel radii of the channel over its whole cross-section.  The lattice spacing is
+    the block's own; a layer enters every round(spacing / (speed * time_step)) steps.  Returns (params, pos,
+    vel, mass, [Emitter], [Sink]): setParticles, then setPorts."""
+    from .ports import Emitter, Sink
+    fill = (1.0, depth, 1.0)
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    h = float(p.h)
+    s = (box[0] * box[1] * depth * box[2] / float(n)) ** (1.0 / 3.0)
+    nu = max(1, int(math.floor(depth * box[1] / s)))
+    nw = max(1, int(math.floor(box[2] / s)))
+    every = max(1, int(round(s / (speed * float(p.time_step)))))
+    emitter = Emitter(0, (0.5 * s, 0.5 * s, 0.5 * s), (nu, nw), s, (speed, 0.0, 0.0), 1.0, 0, every, -1)
+    top = (float(p.max_x), float(p.max_y), float(p.max_z))
+    sink = Sink((box[0] - 2.0 * h, -h, -h), (top[0] + h, top[1] + h, top[2] + h))
+    return p, pos, vel, mass, [emitter], [sink]

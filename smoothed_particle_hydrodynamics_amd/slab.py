@@ -269,6 +269,10 @@ class HipSlab(Context):
         super().set_obstacle_motion(motions)
         self._settings["obstacle_motion"] = self.get_obstacle_motion()[0]   # a Motion per obstacle, or []
 
+    def set_ports(self, emitters=(), sinks=()):
+        """Ports (sph_hip_set_ports) change one context's particle count between its own steps: refused."""
+        raise SphHipError("set_ports: a slab cannot have ports (single contexts only: SPH.setPorts)")
+
     # record_loads / get_loads are lib.Context's: a slab records the responses of the particles it owns
     # (each particle is owned by one slab), so the rows of all slabs of a run add up to the single
     # context's (LocalSlabGroup.get_loads; across ranks, an integer all-reduce of Loads.impulse_q,
@@ -816,6 +820,10 @@ class LocalSlabGroup:
         """HipSlab.set_obstacle_motion on every slab, between two steps of the group."""
         for s in self.slabs:
             s.set_obstacle_motion(motions)
+
+    def set_ports(self, emitters=(), sinks=()):
+        """Refused, as HipSlab.set_ports."""
+        raise SphHipError("set_ports: a slab group cannot have ports (single contexts only: SPH.setPorts)")
 
     def record_loads(self, steps, quantum_log2=LOAD_QUANTUM_LOG2):
         """HipSlab.record_loads on every slab: row r of each is the group's step r."""

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import gauges as _G
 from . import obstacles as _O
+from . import ports as _P
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, TracerPath, Tracers, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
@@ -115,6 +116,9 @@ class SPH(Context):
         super().__init__("sph_hip_create", C.byref(self._params), cap, int(mode), int(device))
         self.mSrcParticles = Particle(self.mParticleCount)
         self._mirror_fresh = False
+        self._capacity = cap
+        self._ports_set = False   # some emitter or sink is set
+        self._had_ports = False   # ... or was since the last upload: the mirror holds the live rows by id
 
     # ---- scene ------------------------------------------------------------------------------
     def setParticles(self, position, velocity, mass):
@@ -134,9 +138,14 @@ class SPH(Context):
         self.mSrcParticles.mMass[:] = m
         self.call("sph_hip_upload", n, _ptr(pos), _ptr(vel), _ptr(m))
         self._mirror_fresh = False
+        self._had_ports = self._ports_set   # (the lists survive an upload; the ids start over)
 
     def syncParticles(self):
-        """Refresh the host `Particle` mirror from the device."""
+        """Refresh the host `Particle` mirror from the device.  On a context that has had ports since its
+        last upload the mirror is a new Particle of the live rows in ascending id order, with the ids in mId
+        (and no mMass: the masses are the emitters' and the upload's)."""
+        if self._had_ports:
+            return self._sync_live()
         p = self.mSrcParticles
         self.call("sph_hip_download", _ptr(p.mPosition), _ptr(p.mVelocity), _ptr(p.mDensity),
                   _ptr(p.mAcceleration), _ptr(p.mNeighborCount))
@@ -150,7 +159,66 @@ class SPH(Context):
         return self.mSrcParticles
 
     def getParticleCount(self):
+        """The particle count: on a context that has had ports the live count, read from the device."""
+        if self._had_ports:
+            self.mParticleCount = self.getPorts()[0].live
         return self.mParticleCount
+
+    # ---- ports (sph_hip_set_ports) ---------------------------------------------------------------
+    def setPorts(self, emitters=(), sinks=()):
+        """Replace the emitters and sinks (ports.Emitter / ports.Sink, at most 8 of each; none clears them):
+        from the next step on the sinks remove what stands inside them at the start of a step and the emitters
+        append their layers (include/sph_hip.h: ports).  The schedule and the totals start at 0.  Single
+        contexts only."""
+        ea, ne = _P.as_emitter_array(emitters)
+        sa, ns = _P.as_sink_array(sinks)
+        self.call("sph_hip_set_ports", ea, ne, sa, ns)
+        self._ports_set = ne > 0 or ns > 0
+        self._had_ports = self._had_ports or self._ports_set
+        self._mirror_fresh = False
+
+    def getPorts(self):
+        """(PortTotals(emitted, removed, live, next_id), [Emitter], [Sink]) after every step enqueued so far
+        (sph_hip_get_ports; synchronises)."""
+        ea = (_P.SphEmitter * _P.MAX_EMITTERS)()
+        sa = (_P.SphSink * _P.MAX_SINKS)()
+        emitted = np.zeros(_P.MAX_EMITTERS, np.int64)
+        removed = np.zeros(_P.MAX_SINKS, np.int64)
+        live, next_id = C.c_int32(), C.c_uint32()
+        r = self.call("sph_hip_get_ports", ea, sa, _P.MAX_EMITTERS, _P.MAX_SINKS, _ptr(emitted), _ptr(removed),
+                      C.byref(live), C.byref(next_id))
+        ne, ns = r & 0xFF, r >> 8
+        return (_P.PortTotals(emitted[:ne].copy(), removed[:ns].copy(), live.value, next_id.value),
+                [_P.emitter_from_struct(ea[i]) for i in range(ne)], [_P.sink_from_struct(sa[i]) for i in range(ns)])
+
+    def downloadLive(self):
+        """The live particles in device order (sph_hip_download_live; synchronises): (ids uint32 [n], pos [3n],
+        vel [3n], density [n], acc [3n], neighbour count [n])."""
+        cap = self._capacity
+        rows = C.c_int32()
+        ids = np.zeros(cap, np.uint32)
+        pos, vel, acc = (np.zeros(3 * cap, np.float32) for _ in range(3))
+        rho = np.zeros(cap, np.float32)
+        cnt = np.zeros(cap, np.int32)
+        self.call("sph_hip_download_live", cap, C.byref(rows), _ptr(ids), _ptr(pos), _ptr(vel), _ptr(rho), _ptr(acc),
+                  _ptr(cnt))
+        n = rows.value
+        return ids[:n], pos[:3 * n], vel[:3 * n], rho[:n], acc[:3 * n], cnt[:n]
+
+    def _sync_live(self):
+        ids, pos, vel, rho, acc, cnt = self.downloadLive()
+        order = np.argsort(ids, kind="stable")
+        p = Particle(ids.size)
+        p.mId = ids[order]
+        p.mPosition[:] = pos.reshape(-1, 3)[order].reshape(-1)
+        p.mVelocity[:] = vel.reshape(-1, 3)[order].reshape(-1)
+        p.mAcceleration[:] = acc.reshape(-1, 3)[order].reshape(-1)
+        p.mDensity[:] = rho[order]
+        p.mNeighborCount[:] = cnt[order]
+        self.mSrcParticles = p
+        self.mParticleCount = ids.size
+        self._mirror_fresh = True
+        return p
 
     def getGridCellCounts(self):
         return self._params.cells_x, self._params.cells_y, self._params.cells_z
