@@ -12,6 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 SOURCES = ["sph_hip.hip"]
 HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "full_tiled.h", "neighbor_lists.h",
            "ref_kernels.h", "common_kernels.h", "slab_kernels.h", "slab_rccl.h", "launch_policy.h",
+           "tile_layout.h",
            "context.h", "launch.h", "slab_comm.h", "sample_kernels.h", "sample_policy.h",
            "surface_kernels.h", "surface_policy.h", "render_kernels.h", "render_policy.h",
            "scene_kernels.h", "scene_policy.h", "obstacle_policy.h",

@@ -26,6 +26,7 @@
 #pragma once
 
 #include "launch_policy.h"
+#include "tile_layout.h"
 #include "common_kernels.h"
 #include "full_kernels.h"
 #include "neighbor_lists.h"
@@ -124,14 +125,6 @@ __device__ __forceinline__ f32x4 lds_read4(const float* base, int i)
    return *reinterpret_cast<const f32x4*>(__builtin_assume_aligned(base + i, 16));
 }
 
-// Per-workgroup tile layout, computed by k_tile_desc before the sums run.
-struct TileDesc {
-   int D[9];      // tile index = sorted index + D[k] inside segment k
-   int B[9];      // first tile index of segment k (B[0] = 0)
-   int total;     // tile entries; > the launch's tile capacity => the workgroup runs untiled
-   int pad;
-};
-
 // SoA tile of the density pass inside the dynamic LDS block: three arrays of cap + TILE_PAD floats
 struct TileLds {
    float* x;
@@ -175,33 +168,9 @@ tile_desc(int tile, int ntiles, const uint32_t* __restrict__ perm, const uint32_
             len[k] = (int)cell_start[hi + 1] - G[k];
          }
       }
-      // Segments come in ascending sorted position.  Where consecutive ones overlap or touch
-      // (short rows: a 256-particle span then covers several rows, and the dy = -1, 0, +1
-      // segments of a plane are nearly the same range) they share tile storage: same index
-      // shift D, and only the part past the previous segment's end is new.  B[k] = first tile
-      // index of segment k's new part, so "tile index t in [B[k], B[k+1])  <->  sorted index
-      // t - D[k]" holds for the loader.
-      int run = 0, chain_end = -1, chain_d = 0;
-#pragma unroll
-      for (int k = 0; k < 9; k++) {
-         d.B[k] = run;
-         if (len[k] == 0) {          // nothing to load, no lane range refers to it
-            d.D[k] = run - G[k];
-         } else if (G[k] <= chain_end) {
-            const int seg_end = G[k] + len[k];
-            d.D[k] = chain_d;
-            if (seg_end > chain_end) {
-               run += seg_end - chain_end;
-               chain_end = seg_end;
-            }
-         } else {
-            d.D[k] = chain_d = run - G[k];
-            run += len[k];
-            chain_end = G[k] + len[k];
-         }
-      }
-      d.total = run;
-      d.pad = 0;
+      // (tile_layout.h: consecutive segments that overlap or touch share tile storage)
+      tile_layout_chain(G, len, d);
+      const int run = d.total;
       desc[tile] = d;
       most = run;
    }
@@ -268,19 +237,60 @@ __device__ __forceinline__ int xcd_workgroup(int block, int nblocks)
    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + block / 8;
 }
 
+// The tile fill's view of the workgroup's descriptor: workgroup-uniform values read straight from
+// desc[wg] (scalar loads, scalar registers), next to the copy in LDS that the lanes' ranges and the
+// list entries use.  A pass of the fill - TILE_THREADS consecutive tile indices, one per lane -
+// takes its shift from these (tile_layout.h); no lane searches the segments.
+struct TileFill {
+   int B[TILE_SEGMENTS], D[TILE_SEGMENTS];
+   int total;
+   unsigned long long passes;   // tile_pass_mask(): the passes with a change of shift inside
+};
+__device__ __forceinline__ void tile_fill_begin(const TileDesc* __restrict__ desc, int wg, TileFill& f)
+{
+   const TileDesc* __restrict__ gd = desc + wg;
+#define TILE_STEP(k, prev) f.B[k] = gd->B[k]; f.D[k] = gd->D[k];
+   TILE_STEP(0, 0) TILE_EACH_BOUNDARY(TILE_STEP)
+#undef TILE_STEP
+   f.total = gd->total;
+   f.passes = tile_pass_mask(f.B, f.D, f.total);
+}
+// The boundaries inside the pass [start, end), applied to the lane's shift d: one compare and
+// select per boundary.  Only the passes flagged as holding one come here.  B and D are the
+// descriptor's words in scalar registers; those of a boundary picked at run time come from the
+// copy in LDS (read before the select, and said to be uniform: no load under a lane mask).
+__device__ __forceinline__ int tile_fill_boundaries(const int (&B)[TILE_SEGMENTS], const int (&D)[TILE_SEGMENTS],
+                                                    const TileDesc& sd, int start, int end, int idx, int d)
+{
+   uint32_t m = tile_pass_boundaries(B, D, start, end);
+   while (m) {
+      const int k = __builtin_ctz(m);
+      m &= m - 1;
+      const int b = __builtin_amdgcn_readfirstlane(sd.B[k]), dk = __builtin_amdgcn_readfirstlane(sd.D[k]);
+      d = (idx >= b) ? dk : d;
+   }
+   return d;
+}
+// The shift of the lane's index idx = min(start + tid, total - 1) in the pass that begins at `start`
+// (a multiple of TILE_THREADS).  Scalar: the shift of the pass's first index and the bit that says
+// whether a boundary lies inside the pass.  Per lane: what tile_fill_boundaries() does in a pass
+// that holds one.  A pass past the tile's end has every lane at total - 1.
+__device__ __forceinline__ int tile_fill_shift(const TileFill& f, const TileDesc& sd, int start, int idx)
+{
+   const int last = f.total - 1;
+   int d = tile_shift_at(f.B, f.D, min(start, last));
+   if (start < last && tile_pass_has_boundary(f.passes, start / TILE_THREADS))
+      d = tile_fill_boundaries(f.B, f.D, sd, start, min(start + TILE_THREADS, f.total), idx, d);
+   return d;
+}
+
 // Copies the candidate positions of the workgroup's tile into LDS, TILE_BATCH 16-byte loads per
 // thread in flight before the first LDS store of a batch.  The descriptor is already in LDS.
-__device__ __forceinline__ void tile_load(const float4* __restrict__ posm, const TileDesc& sd,
-                                          const TileLds& L)
+__device__ __forceinline__ void tile_load(const float4* __restrict__ posm, const TileFill& f,
+                                          const TileDesc& sd, const TileLds& L)
 {
    const int tid = threadIdx.x;
-   const int total = sd.total;
-   int B[9], D[9];
-#pragma unroll
-   for (int k = 0; k < 9; k++) {
-      B[k] = sd.B[k];
-      D[k] = sd.D[k];
-   }
+   const int total = f.total;
 #if defined(SPH_ABLATE) && (SPH_ABLATE == 3 || SPH_ABLATE == 5)
    for (int base = 0; base < 0; base += TILE_BATCH * TILE_THREADS) {
 #else
@@ -292,10 +302,7 @@ __device__ __forceinline__ void tile_load(const float4* __restrict__ posm, const
 #pragma unroll
       for (int r = 0; r < TILE_BATCH; r++) {
          const int idx = min(base + tid + r * TILE_THREADS, total - 1);
-         int d = D[0];
-#pragma unroll
-         for (int k = 1; k < 9; k++) d = (idx >= B[k]) ? D[k] : d;
-         buf[r] = posm[idx - d];
+         buf[r] = posm[idx - tile_fill_shift(f, sd, base + r * TILE_THREADS, idx)];
       }
 #pragma unroll
       for (int r = 0; r < TILE_BATCH; r++) {
@@ -444,6 +451,8 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
    // out before the tile's loads, so that both are in flight together.
    float4 pi = make_float4(0.f, 0.f, 0.f, 0.f);
    if (live) pi = posm[p];
+   TileFill fill;
+   tile_fill_begin(desc, wg, fill);
    tile_desc_load(desc, wg, sd);
    if (sd.total > tile_cap) {
       // tile does not fit: on the give-up lists, computed by the first workgroups of both passes
@@ -475,7 +484,7 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
 #endif
    }
    PHASE_MARK(0);   // descriptor, own position, row ranges
-   tile_load(posm, sd, L);
+   tile_load(posm, fill, sd, L);
    PHASE_MARK(1);   // tile
    const int self_t = p + sd.D[4];
    const f32x2 px = {pi.x, pi.x}, py = {pi.y, pi.y}, pz = {pi.z, pi.z};
@@ -1220,6 +1229,10 @@ k_full_accel_lists(const float4* __restrict__ posm, const float4* __restrict__ v
    // it is on the give-up list and one of the first workgroups computes it.  Computing it here as
    // well would integrate and count its particles twice.
    if (total > tile_cap || total > tile_cap_density) return;
+   // (This pass keeps the per-lane search of the nine segments that the density pass's tile_load()
+   // dropped.  Its arguments alone overflow the scalar file, so the descriptor's words cannot stay in
+   // scalar registers; a per-wave table of the passes' shifts - one search per wave, lane q = pass q,
+   // v_readlane per pass - measured 14 us SLOWER at 4M than the search: profiles/tile_fill_passes.txt.)
    int B[9], D[9];
 #pragma unroll
    for (int kk = 0; kk < 9; kk++) {

@@ -109,7 +109,8 @@ def source_spans():
     return spans
 
 
-HELPERS = ("sph_device.h", "pair_math.h", "common_kernels.h", "slab_kernels.h", "cell_build.h", "neighbor_lists.h")
+HELPERS = ("sph_device.h", "pair_math.h", "common_kernels.h", "slab_kernels.h", "cell_build.h", "neighbor_lists.h",
+           "tile_layout.h")
 
 
 def attribute(asm, kernel, prefix, spans):
