@@ -464,6 +464,13 @@ int sph_hip_render(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hi
  *              side = s0 >= near_a (on equal bounds the side wins); t0 = side ? s0 : near_a;
  *              t1 = fminf(s1, far_a).  Side: normal_u = ((eye_u + t * d_u) - center_u) / r, normal_w
  *              likewise, normal_a = 0.  Cap: normal_a = d_a > 0 ? -1 : 1, the other two 0.
+ *   wedge      n = center, off = radius.  The box's b0 = fmaxf(fmaxf(near_x, near_y), near_z) and
+ *              b1 = fminf(fminf(far_x, far_y), far_z); g = (n0*d0 + n1*d1) + n2*d2,
+ *              f = ((n0*eye0 + n1*eye1) + n2*eye2) - off.  g < 0: near_p = (-f) / g, far_p = +inf.
+ *              g > 0: near_p = -inf, far_p = (-f) / g.  Otherwise a miss unless f < 0, else
+ *              near_p = -inf, far_p = +inf.  t0 = fmaxf(b0, near_p), t1 = fminf(b1, far_p).  The normal
+ *              is the box's (first axis with near_a == t0) when t0 == b0 - a box face wins a tie with
+ *              the cut face -, else n as stored.
  *   nearest    the solids in list order; solid i replaces the best so far when it is hit with
  *              t_i < t_best (strictly; t_best starts at +inf): the lower index wins a tie.
  *   composite  the nearest solid takes the pixel when t_solid < depth_fluid, strictly; depth_fluid is
@@ -500,10 +507,11 @@ int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const 
 
 /* ---- static obstacles --------------------------------------------------------------------- *
  *
- * Analytic solids inside the domain: spheres, axis-aligned boxes and axis-aligned capped
- * cylinders, in position units (those of mPosition and max_x/y/z).  No counterpart in the
- * reference's step: the response generalises SPH::applyBoundary (src/sph.cpp:1124-1148), which the
- * reference applies to the six walls only.  Inside integrate, after the drift, the kick and the wall
+ * Analytic solids inside the domain: spheres, axis-aligned boxes, axis-aligned capped
+ * cylinders and wedges (an axis-aligned box cut by one plane: ramps, beaches, weirs), in position
+ * units (those of mPosition and max_x/y/z).  No counterpart in the reference's step: the response
+ * generalises SPH::applyBoundary (src/sph.cpp:1124-1148), which the reference applies to the six
+ * walls only.  Inside integrate, after the drift, the kick and the wall
  * handling (apply_walls), every obstacle in list order tests the particle's new position strictly
  * (on the surface is outside) and, when it is inside, reflects the particle where the line from its
  * old position along its new velocity enters the obstacle and moves it on for the rest of the step
@@ -516,25 +524,35 @@ int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const 
  *   box       lo, hi.
  *   cylinder  axis (0 x, 1 y, 2 z), center (its axis component is ignored), radius, and its caps at
  *             lo[axis], hi[axis].
+ *   wedge     the box lo < x < hi intersected with the half-space n.x < d: the unit normal n of the
+ *             cut face, pointing out of the solid, in center[0..2]; d in radius; axis is ignored.
+ *             n.x is always (n0*x0 + n1*x1) + n2*x2.  A plane that cuts nothing off is allowed (the
+ *             solid is the box); one that leaves nothing is refused.  Moved by a motion or as a body,
+ *             lo and hi get the shift D, n stays and d = d + ((n0*D0 + n1*D1) + n2*D2).
  * sph_hip_set_obstacles replaces the whole list (n = 0 clears it), ordered on the context's stream:
  * steps enqueued before the call keep the old list; `list` may be reused as soon as it returns.  It
  * is refused with SPH_HIP_ERR_INVALID, and the previous list kept, for an unknown kind, a field that
  * is not finite (unused fields included), a radius that is not > 0, lo >= hi on a used axis, a
- * cylinder axis outside 0..2, n < 0, n > SPH_HIP_MAX_OBSTACLES, a null list with n > 0, and on a slab
- * between sph_hip_slab_step_begin and sph_hip_slab_step_end.  Valid in REF, FULL and FULL_FAST and on
- * slab contexts; without obstacles every step is bit-identical to one on a context that never had any.
+ * cylinder axis outside 0..2, a wedge normal with | |n|^2 - 1 | > 2^-20 (in double from the float
+ * fields), a wedge none of whose box's eight corners c has n.c < d (in double), n < 0,
+ * n > SPH_HIP_MAX_OBSTACLES, a null list with n > 0, and on a slab between
+ * sph_hip_slab_step_begin and sph_hip_slab_step_end.  Valid in REF, FULL and FULL_FAST and on slab
+ * contexts; without obstacles every step is bit-identical to one on a context that never had any.
  * sph_hip_get_obstacles copies up to `capacity` entries to `out` (NULL with capacity 0) and returns
- * how many the context holds (or a negative status). */
+ * how many the context holds (or a negative status).
+ * SPH_HIP_OBSTACLE_WEDGE was added without a change of SPH_HIP_ABI_VERSION: no struct and no prototype
+ * changed; a library without it refuses the kind as unknown. */
 #define SPH_HIP_OBSTACLE_SPHERE   0
 #define SPH_HIP_OBSTACLE_BOX      1
 #define SPH_HIP_OBSTACLE_CYLINDER 2
+#define SPH_HIP_OBSTACLE_WEDGE    3
 #define SPH_HIP_MAX_OBSTACLES     64
 typedef struct sph_hip_obstacle {   /* field order is ABI: 48 bytes */
    int32_t kind;                    /* SPH_HIP_OBSTACLE_* */
    int32_t axis;                    /* cylinder only */
-   float center[3];                 /* sphere, cylinder */
-   float radius;                    /* sphere, cylinder */
-   float lo[3], hi[3];              /* box; cylinder: its caps on `axis` */
+   float center[3];                 /* sphere, cylinder; wedge: the cut face's unit normal */
+   float radius;                    /* sphere, cylinder; wedge: the plane's offset d */
+   float lo[3], hi[3];              /* box, wedge; cylinder: its caps on `axis` */
 } sph_hip_obstacle;
 int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, int n);
 int sph_hip_get_obstacles(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity);

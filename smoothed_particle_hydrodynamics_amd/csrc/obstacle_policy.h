@@ -13,6 +13,8 @@
 //              box: lo[a] < q[a] < hi[a] on every axis a.
 //              cylinder (axis a, u = (a+1)%3, w = (a+2)%3): lo[a] < q[a] < hi[a] and
 //              du*du + dw*dw < r*r with d = q - center.
+//              wedge (the box cut by a plane: n = center, d = radius, axis ignored): the box's test and
+//              (n0*q0 + n1*q1) + n2*q2 < d.  Every n.x below is formed like this one.
 //              A particle that is not inside is left untouched, bit for bit.
 //   entry      along the line p + v*s:
 //              box: for every axis with v[a] != 0, t_a = ((v[a] > 0 ? lo[a] : hi[a]) - p[a]) / v[a]
@@ -30,6 +32,11 @@
 //              when d0u*d0u + d0w*d0w < r*r, else a miss).  t = the later of tc0 and tr0, the cap
 //              on a tie; t_exit = the smaller of tc1 and tr1.  n: the cap's -sign(v[a]) e_a, or the
 //              side's (inter_u - center_u) / r, (inter_w - center_w) / r with n_a = 0.
+//              wedge: the box's three slabs with the box's ties give t, t_exit and the axis; then the
+//              plane: g = n.v, f = (n.p) - d.  g == 0: a miss unless f < 0.  g < 0: s_pl = (-f) / g is an
+//              entry candidate and replaces t only when s_pl > t (a box face wins a tie); otherwise
+//              (g > 0) s_pl = (-f) / g is an exit candidate and replaces t_exit only when s_pl < t_exit.
+//              n: the slab's -sign(v[a]) e_a, or the plane's n = center as stored.
 //              The entry is valid only when p is not inside, v != 0, the line meets the obstacle
 //              and 0 <= t < t_exit.
 //   response   (a valid entry: SPH::applyBoundary, reference src/sph.cpp:1124-1148, as coded)
@@ -45,6 +52,9 @@
 //              (r - len, len = sqrtf(du*du + dw*dw)); the first smallest wins.  A cap sets q[a] to
 //              its plane; the side sets q_u = center_u + n_u*r, q_w = center_w + n_w*r with
 //              n = (du / len, dw / len) (len == 0: n = e_u).
+//              wedge: the box's six candidates in the box's order, then the plane's dpl = d - n.q; the
+//              first smallest wins.  A box face as the box; the plane sets q_c = q_c + n_c*dpl per
+//              component with the normal n = center.
 //              dot = (v0*n0 + v1*n1) + v2*n2, m = dot if dot < 0 else 0, v = v - n*(m*2) per
 //              component: only an inward component is reflected, without damping.
 // The result is not strictly inside the obstacle except by the rounding of the last formula applied
@@ -58,7 +68,9 @@
 //              above (no "+ 0": a -0 field keeps its sign).
 //   shift      s(tau) = (tau < start ? start : tau > stop ? stop : tau) - start;
 //              D_c(tau) = velocity[c] * s(tau); the obstacle at tau is the list entry with D_c added to
-//              center[c], lo[c] and hi[c] on all three axes, the unused fields included.
+//              center[c], lo[c] and hi[c] on all three axes, the unused fields included.  A wedge's
+//              center holds its normal and stays untouched: lo[c] and hi[c] get D_c and
+//              radius = radius + ((n0*D0 + n1*D1) + n2*D2).
 //   response   D0 = D(tau0), D1 = D(tau1), o1 = the obstacle at tau1.  q not strictly inside o1: the
 //              particle is untouched, bit for bit.  d_c = D1_c - D0_c.  All three d_c == 0 (not started,
 //              stopped, dt == 0): the response above with o1; nothing is divided.  Otherwise
@@ -119,7 +131,8 @@ inline const char* obstacle_check(const sph_hip_obstacle* list, int n)
    if (n > 0 && !list) return "null obstacle list";
    for (int i = 0; i < n; i++) {
       const sph_hip_obstacle& o = list[i];
-      if (o.kind != SPH_HIP_OBSTACLE_SPHERE && o.kind != SPH_HIP_OBSTACLE_BOX && o.kind != SPH_HIP_OBSTACLE_CYLINDER)
+      if (o.kind != SPH_HIP_OBSTACLE_SPHERE && o.kind != SPH_HIP_OBSTACLE_BOX && o.kind != SPH_HIP_OBSTACLE_CYLINDER &&
+          o.kind != SPH_HIP_OBSTACLE_WEDGE)
          return "unknown obstacle kind";
       bool finite = isfinite(o.radius);
       for (int a = 0; a < 3; a++) finite = finite && isfinite(o.center[a]) && isfinite(o.lo[a]) && isfinite(o.hi[a]);
@@ -129,6 +142,17 @@ inline const char* obstacle_check(const sph_hip_obstacle* list, int n)
       } else if (o.kind == SPH_HIP_OBSTACLE_BOX) {
          for (int a = 0; a < 3; a++)
             if (!(o.lo[a] < o.hi[a])) return "a box needs lo < hi on every axis";
+      } else if (o.kind == SPH_HIP_OBSTACLE_WEDGE) {
+         for (int a = 0; a < 3; a++)
+            if (!(o.lo[a] < o.hi[a])) return "a wedge needs lo < hi on every axis";
+         const double n0 = o.center[0], n1 = o.center[1], n2 = o.center[2];
+         if (!(fabs(((n0 * n0 + n1 * n1) + n2 * n2) - 1.0) <= 0x1p-20)) return "a wedge's normal must have unit length";
+         bool some = false;   // a corner of the box on the solid's side of the plane
+         for (int k = 0; k < 8; k++) {
+            const double c0 = k & 1 ? o.hi[0] : o.lo[0], c1 = k & 2 ? o.hi[1] : o.lo[1], c2 = k & 4 ? o.hi[2] : o.lo[2];
+            some = some || (n0 * c0 + n1 * c1) + n2 * c2 < (double)o.radius;
+         }
+         if (!some) return "a wedge's plane leaves nothing of its box";
       } else {
          if (o.axis < 0 || o.axis > 2) return "a cylinder's axis must be 0, 1 or 2";
          if (!(o.radius > 0.0f)) return "a cylinder's radius must be > 0";
@@ -136,6 +160,12 @@ inline const char* obstacle_check(const sph_hip_obstacle* list, int n)
       }
    }
    return nullptr;
+}
+
+// n.x of a wedge's plane (n = center)
+OBST_HD inline float obstacle_plane_dot(const sph_hip_obstacle& o, const float x[3])
+{
+   return (o.center[0] * x[0] + o.center[1] * x[1]) + o.center[2] * x[2];
 }
 
 OBST_HD inline bool obstacle_inside(const sph_hip_obstacle& o, const float x[3])
@@ -147,6 +177,9 @@ OBST_HD inline bool obstacle_inside(const sph_hip_obstacle& o, const float x[3])
    if (o.kind == SPH_HIP_OBSTACLE_BOX)
       return o.lo[0] < x[0] && x[0] < o.hi[0] && o.lo[1] < x[1] && x[1] < o.hi[1] && o.lo[2] < x[2] &&
              x[2] < o.hi[2];
+   if (o.kind == SPH_HIP_OBSTACLE_WEDGE)
+      return o.lo[0] < x[0] && x[0] < o.hi[0] && o.lo[1] < x[1] && x[1] < o.hi[1] && o.lo[2] < x[2] &&
+             x[2] < o.hi[2] && obstacle_plane_dot(o, x) < o.radius;
    const int a = o.axis, u = (a + 1) % 3, w = (a + 2) % 3;
    const float du = x[u] - o.center[u], dw = x[w] - o.center[w];
    return o.lo[a] < x[a] && x[a] < o.hi[a] && du * du + dw * dw < o.radius * o.radius;
@@ -174,9 +207,10 @@ OBST_HD inline void obstacle_respond(const sph_hip_obstacle& o, const float p[3]
    float n[3] = {0.0f, 0.0f, 0.0f};
    float t = 0.0f, t_exit = 0.0f;
    bool hit = !obstacle_inside(o, p) && (v[0] != 0.0f || v[1] != 0.0f || v[2] != 0.0f);
-   int kind_n = -1;   // entry normal: axis 0..2 (slab), 3 (sphere), 4 (cylinder side)
+   const bool wedge = o.kind == SPH_HIP_OBSTACLE_WEDGE;
+   int kind_n = -1;   // entry normal: axis 0..2 (slab), 3 (sphere), 4 (cylinder side), 5 (wedge plane)
    if (hit) {
-      if (o.kind == SPH_HIP_OBSTACLE_BOX) {
+      if (o.kind == SPH_HIP_OBSTACLE_BOX || wedge) {
          t = -INFINITY;
          t_exit = INFINITY;
          for (int a = 0; a < 3 && hit; a++) {
@@ -187,6 +221,23 @@ OBST_HD inline void obstacle_respond(const sph_hip_obstacle& o, const float p[3]
                kind_n = a;
             }
             if (t1 < t_exit) t_exit = t1;
+         }
+         if (wedge && hit) {
+            const float g = obstacle_plane_dot(o, v);
+            const float f = obstacle_plane_dot(o, p) - r;
+            if (g == 0.0f) {
+               if (!(f < 0.0f)) hit = false;
+            } else {
+               const float s_pl = (-f) / g;
+               if (g < 0.0f) {
+                  if (s_pl > t) {
+                     t = s_pl;
+                     kind_n = 5;
+                  }
+               } else if (s_pl < t_exit) {
+                  t_exit = s_pl;
+               }
+            }
          }
       } else if (o.kind == SPH_HIP_OBSTACLE_SPHERE) {
          const float d0x = p[0] - o.center[0], d0y = p[1] - o.center[1], d0z = p[2] - o.center[2];
@@ -240,6 +291,8 @@ OBST_HD inline void obstacle_respond(const sph_hip_obstacle& o, const float p[3]
          n[kind_n] = v[kind_n] > 0.0f ? -1.0f : 1.0f;
       } else if (kind_n == 3) {
          for (int c = 0; c < 3; c++) n[c] = (inter[c] - o.center[c]) / r;
+      } else if (kind_n == 5) {
+         for (int c = 0; c < 3; c++) n[c] = o.center[c];
       } else {
          const int a = o.axis, u = (a + 1) % 3, w = (a + 2) % 3;
          n[u] = (inter[u] - o.center[u]) / r;
@@ -268,7 +321,7 @@ OBST_HD inline void obstacle_respond(const sph_hip_obstacle& o, const float p[3]
          n[0] = 1.0f;
       }
       for (int c = 0; c < 3; c++) q[c] = o.center[c] + n[c] * r;
-   } else if (o.kind == SPH_HIP_OBSTACLE_BOX) {
+   } else if (o.kind == SPH_HIP_OBSTACLE_BOX || wedge) {
       float best = INFINITY;
       int face = 0;
       for (int a = 0; a < 3; a++) {
@@ -282,8 +335,14 @@ OBST_HD inline void obstacle_respond(const sph_hip_obstacle& o, const float p[3]
             face = 2 * a + 1;
          }
       }
+      const float dpl = wedge ? r - obstacle_plane_dot(o, q) : INFINITY;
       const int a = face >> 1;
-      if (face & 1) {
+      if (dpl < best) {
+         for (int c = 0; c < 3; c++) {
+            n[c] = o.center[c];
+            q[c] = q[c] + n[c] * dpl;
+         }
+      } else if (face & 1) {
          q[a] = o.hi[a];
          n[a] = 1.0f;
       } else {
@@ -371,11 +430,13 @@ OBST_HD inline void obstacle_displacement(const sph_hip_obstacle_motion& m, floa
 OBST_HD inline sph_hip_obstacle obstacle_shifted(const sph_hip_obstacle& o, const float D[3])
 {
    sph_hip_obstacle s = o;
+   const bool wedge = o.kind == SPH_HIP_OBSTACLE_WEDGE;   // its center is a normal: the plane's offset moves
    for (int c = 0; c < 3; c++) {
-      s.center[c] = o.center[c] + D[c];
+      s.center[c] = wedge ? o.center[c] : o.center[c] + D[c];
       s.lo[c] = o.lo[c] + D[c];
       s.hi[c] = o.hi[c] + D[c];
    }
+   if (wedge) s.radius = o.radius + obstacle_plane_dot(o, D);
    return s;
 }
 

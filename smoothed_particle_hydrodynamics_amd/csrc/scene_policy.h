@@ -128,6 +128,41 @@ RENDER_HD inline bool scene_hit_box(const sph_hip_obstacle& o, const float eye[3
    return true;
 }
 
+// the box cut by the plane n.x < off (n = center, off = radius): the box's interval narrowed by the plane's
+RENDER_HD inline bool scene_hit_wedge(const sph_hip_obstacle& o, const float eye[3], const float d[3], float& t,
+                                      float n[3])
+{
+   float nr[3], fr[3];
+   for (int a = 0; a < 3; a++) scene_slab(eye[a], d[a], o.lo[a], o.hi[a], nr[a], fr[a]);
+   const float b0 = fmaxf(fmaxf(nr[0], nr[1]), nr[2]);
+   const float b1 = fminf(fminf(fr[0], fr[1]), fr[2]);
+   const float g = obstacle_plane_dot(o, d);
+   const float f = obstacle_plane_dot(o, eye) - o.radius;
+   float near_p = -INFINITY, far_p = INFINITY;
+   if (g < 0.0f) {
+      near_p = (-f) / g;
+   } else if (g > 0.0f) {
+      far_p = (-f) / g;
+   } else if (!(f < 0.0f)) {
+      return false;
+   }
+   const float t0 = fmaxf(b0, near_p);
+   const float t1 = fminf(b1, far_p);
+   bool inside;
+   if (!scene_interval(t0, t1, d, t, n, inside)) return false;
+   if (!inside) {
+      if (t0 == b0) {   // a box face wins a tie with the cut face
+         const int ax = nr[0] == t0 ? 0 : nr[1] == t0 ? 1 : 2;
+         const float da = ax == 0 ? d[0] : ax == 1 ? d[1] : d[2];
+         const float s = da > 0.0f ? -1.0f : 1.0f;
+         for (int a = 0; a < 3; a++) n[a] = a == ax ? s : 0.0f;
+      } else {
+         for (int a = 0; a < 3; a++) n[a] = o.center[a];
+      }
+   }
+   return true;
+}
+
 // cylinder about axis A (a compile-time axis keeps every index into eye, d and n a constant)
 template <int A>
 RENDER_HD inline bool scene_hit_cylinder_axis(const sph_hip_obstacle& o, const float eye[3], const float d[3],
@@ -177,6 +212,7 @@ RENDER_HD inline bool scene_hit(const sph_hip_obstacle& o, const float eye[3], c
 {
    if (o.kind == SPH_HIP_OBSTACLE_SPHERE) return scene_hit_sphere(o, eye, d, t, n);
    if (o.kind == SPH_HIP_OBSTACLE_BOX) return scene_hit_box(o, eye, d, t, n);
+   if (o.kind == SPH_HIP_OBSTACLE_WEDGE) return scene_hit_wedge(o, eye, d, t, n);
    if (o.axis == 0) return scene_hit_cylinder_axis<0>(o, eye, d, t, n);
    if (o.axis == 1) return scene_hit_cylinder_axis<1>(o, eye, d, t, n);
    return scene_hit_cylinder_axis<2>(o, eye, d, t, n);

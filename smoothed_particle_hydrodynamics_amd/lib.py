@@ -237,6 +237,8 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+OBSTACLE_SPHERE, OBSTACLE_BOX, OBSTACLE_CYLINDER, OBSTACLE_WEDGE = (   # SPH_HIP_OBSTACLE_*
+    _obstacles.SPHERE, _obstacles.BOX, _obstacles.CYLINDER, _obstacles.WEDGE)
 LOAD_SOLIDS = 6 + _obstacles.MAX_OBSTACLES   # SPH_HIP_LOAD_SOLIDS
 LOAD_QUANTUM_LOG2 = -24                      # the default quantum of a load recording
 LOAD_NAMES = tuple(["x-lo", "x-hi", "y-lo", "y-hi", "z-lo", "z-hi"] +

@@ -1,8 +1,9 @@
 """Static analytic obstacles (include/sph_hip.h: sph_hip_set_obstacles).
 
-`Sphere`, `Box` and `Cylinder` describe the solids a context's particles collide with; `as_struct()`
-gives the C ABI's sph_hip_obstacle, `signed_distance(points)` the numpy distance to the surface
-(negative inside), for placing obstacles and checking results.  `Motion` is the constant velocity an
+`Sphere`, `Box`, `Cylinder` and `Wedge` (a box cut by one plane: the way to a slope) describe the solids
+a context's particles collide with; `as_struct()` gives the C ABI's sph_hip_obstacle,
+`signed_distance(points)` the numpy distance to the surface (negative inside), for placing obstacles
+and checking results.  `Motion` is the constant velocity an
 obstacle is driven at between two readings of the context's motion clock
 (sph_hip_set_obstacle_motion); `Body` makes it a free body that the fluid's own loads move
 (sph_hip_set_bodies).  The collision response itself is csrc/obstacle_policy.h and runs on the GPU.
@@ -15,7 +16,7 @@ import math
 
 import numpy as np
 
-SPHERE, BOX, CYLINDER = 0, 1, 2   # SPH_HIP_OBSTACLE_* (include/sph_hip.h)
+SPHERE, BOX, CYLINDER, WEDGE = 0, 1, 2, 3   # SPH_HIP_OBSTACLE_* (include/sph_hip.h)
 MAX_OBSTACLES = 64                # SPH_HIP_MAX_OBSTACLES
 
 
@@ -121,14 +122,76 @@ class Cylinder:
         return "Cylinder(%d, %s, %g, %g, %g)" % (self.axis, list(self.center), self.radius, self.lo, self.hi)
 
 
+class Wedge:
+    """Axis-aligned box [lo, hi] cut by a plane: the part of the box with normal . x < offset.  `normal` is
+    the outward normal of the cut face; it is normalised in float64, then rounded to fp32, which is what
+    the C ABI stores (center = normal, radius = offset)."""
+
+    kind = WEDGE
+
+    def __init__(self, lo, hi, normal, offset):
+        self.lo, self.hi = _vec3(lo), _vec3(hi)
+        n = np.asarray(normal, np.float64).reshape(3)
+        length = math.sqrt(float((n * n).sum()))
+        if not (length > 0.0 and math.isfinite(length)):
+            raise ValueError("normal must be finite and not zero")
+        self.normal = (n / length).astype(np.float32)
+        self.offset = np.float32(offset)
+
+    @classmethod
+    def ramp(cls, lo, hi, run, up, rising=True):
+        """The box [lo, hi] cut by the plane through its lower edge (along `up`) at one end of axis `run`
+        and its upper edge at the other: a slope that rises towards hi[run] (`rising`) or falls."""
+        run, up = int(run), int(up)
+        if run not in (0, 1, 2) or up not in (0, 1, 2) or run == up:
+            raise ValueError("run and up must be two different axes out of 0, 1, 2")
+        lo64, hi64 = _vec3(lo).astype(np.float64), _vec3(hi).astype(np.float64)
+        length, height = hi64[run] - lo64[run], hi64[up] - lo64[up]
+        n = np.zeros(3)
+        n[up] = length
+        n[run] = -height if rising else height
+        n /= math.sqrt(float((n * n).sum()))
+        foot = lo64.copy()                      # a point of the plane: the lower edge
+        foot[run] = lo64[run] if rising else hi64[run]
+        return cls(lo, hi, n, float((n * foot).sum()))
+
+    def as_struct(self):
+        s = SphObstacle()
+        s.kind = WEDGE
+        s.center[:] = [float(v) for v in self.normal]
+        s.radius = float(self.offset)
+        s.lo[:] = [float(v) for v in self.lo]
+        s.hi[:] = [float(v) for v in self.hi]
+        return s
+
+    def signed_distance(self, points):
+        """The larger of the box's distance and the plane's (float64): negative exactly inside, a lower
+        bound of the distance outside."""
+        p = _points(points)
+        plane = p @ self.normal.astype(np.float64) - float(self.offset)
+        return np.maximum(Box(self.lo, self.hi).signed_distance(p), plane)
+
+    def __repr__(self):
+        return "Wedge(%s, %s, %s, %g)" % (list(self.lo), list(self.hi), list(self.normal), self.offset)
+
+
+def _wedge_from_struct(s):
+    w = Wedge.__new__(Wedge)                    # the stored fields as they are: no second normalisation
+    w.lo, w.hi = _vec3(list(s.lo)), _vec3(list(s.hi))
+    w.normal, w.offset = _vec3(list(s.center)), np.float32(s.radius)
+    return w
+
+
 def from_struct(s):
-    """The Sphere / Box / Cylinder an sph_hip_obstacle describes."""
+    """The Sphere / Box / Cylinder / Wedge an sph_hip_obstacle describes."""
     if s.kind == SPHERE:
         return Sphere(list(s.center), s.radius)
     if s.kind == BOX:
         return Box(list(s.lo), list(s.hi))
     if s.kind == CYLINDER:
         return Cylinder(s.axis, list(s.center), s.radius, s.lo[s.axis], s.hi[s.axis])
+    if s.kind == WEDGE:
+        return _wedge_from_struct(s)
     raise ValueError("unknown obstacle kind %d" % s.kind)
 
 

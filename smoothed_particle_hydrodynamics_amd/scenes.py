@@ -230,6 +230,27 @@ def dam_break_ramp(n, slope_deg=20.0, length=0.6, thickness=0.1, gap=0.25, surge
     return p, pos, vel, mass, [ramp], [tilt]
 
 
+def dam_break_beach(n, slope_deg=20.0, length=0.6, gap=0.25, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0),
+                    neighbors=32.0, seed=42, gravity=-9.81):
+    """dam_break_ramp's set-up - the surging dam column of dam_break_pillar, gravity along -y, the walls on, the
+    surge along +x - running up a beach that a context takes: a Wedge standing on the floor across the whole
+    box along z, whose foot lies `gap` kernel radii from the column's face and whose face rises downstream at
+    `slope_deg` degrees over `length`.  Particles that would start inside it are dropped (carve).  Returns
+    (params, pos, vel, mass, [Wedge]): setObstacles."""
+    from .obstacles import Wedge
+    p, pos, vel, mass = dam_break(n, box, fill, neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    vel.reshape(-1, 3)[:, 0] = np.float32(surge)
+    h = float(p.h)
+    x0 = box[0] * fill[0] + gap * h
+    rise = length * math.tan(math.radians(slope_deg))
+    beach = Wedge.ramp((x0, 0.0, -h), (x0 + length, rise, float(p.max_z) + h), 0, 1)
+    pos, vel, mass = carve(pos, vel, mass, [beach])
+    return p, pos, vel, mass, [beach]
+
+
 def stirred_tank(n, rate, depth=0.5, blade=(0.6, 0.08), start=0.0, stop=math.inf, box=(1.0, 1.0, 1.0),
                  neighbors=32.0, seed=42, gravity=-9.81):
     """A block of fluid at rest filling the tank to `depth` of its height (gravity along -y, the walls on),
@@ -393,3 +414,24 @@ def channel_flow(n, box=(2.0, 0.5, 0.5), depth=0.5, speed=1.0, neighbors=32.0, g
     top = (float(p.max_x), float(p.max_y), float(p.max_z))
     sink = Sink((box[0] - 2.0 * h, -h, -h), (top[0] + h, top[1] + h, top[2] + h))
     return p, pos, vel, mass, [emitter], [sink]
+
+
+def channel_weir(n, crest=0.6, at=0.45, ramps=(0.3, 0.2), top=0.1, box=(2.0, 0.5, 0.5), depth=0.5, speed=1.0,
+                 neighbors=32.0, gravity=-9.81):
+    """channel_flow's open channel with a trapezoidal weir across it, built from three solids in a row along x:
+    a Wedge rising downstream over ramps[0], a Box `top` long, a Wedge falling over ramps[1]; the crest stands
+    `crest` of the water's depth above the floor and the upstream foot `at` of the channel's length from the
+    upstream wall; every solid reaches one kernel radius beyond the side walls.  Particles that would start
+    inside the weir are dropped (carve).  Returns (params, pos, vel, mass, [Wedge, Box, Wedge], [Emitter],
+    [Sink]): setParticles, setObstacles, then setPorts."""
+    from .obstacles import Box, Wedge
+    p, pos, vel, mass, emitters, sinks = channel_flow(n, box, depth, speed, neighbors, gravity)
+    h = float(p.h)
+    height = crest * depth * box[1]
+    x0 = at * box[0]
+    x1, x2, x3 = x0 + ramps[0], x0 + ramps[0] + top, x0 + ramps[0] + top + ramps[1]
+    z0, z1 = -h, float(p.max_z) + h
+    weir = [Wedge.ramp((x0, 0.0, z0), (x1, height, z1), 0, 1, rising=True), Box((x1, 0.0, z0), (x2, height, z1)),
+            Wedge.ramp((x2, 0.0, z0), (x3, height, z1), 0, 1, rising=False)]
+    pos, vel, mass = carve(pos, vel, mass, weir)
+    return p, pos, vel, mass, weir, emitters, sinks
