@@ -303,7 +303,9 @@ int sph_hip_download_neighbor_lists(sph_hip_context* ctx, uint32_t* neighbors, f
  * them NULL the probes are still evaluated: timing); arrays are host memory; the call
  * synchronises.  SPH_HIP_ERR_INVALID for a REF context, a slab context (sph_hip_create_slab with
  * neighbours, or one that has exchanged), n < 0, dims <= 0, a non-finite origin, a non-finite or
- * non-positive spacing, and a lattice of more than 2^31 - 1 points.  n == 0 does nothing. */
+ * non-positive spacing, and a lattice of more than 2^31 - 1 points.  n == 0 does nothing.
+ * These two calls return density, velocity and count; the pressure at a probe is
+ * sph_hip_sample_pressure_points / _lattice (below: pressure readings). */
 /* n probes, xyz interleaved; density[n], velocity_xyz[3n], count[n] */
 int sph_hip_sample_points(sph_hip_context* ctx, int n, const float* xyz,
                           float* density, float* velocity_xyz, int32_t* count);
@@ -792,13 +794,16 @@ int sph_hip_get_tracer_path(sph_hip_context* ctx, int first_row, int n_rows, flo
  *              sph_hip_step, sph_hip_run and the phase calls give the same bits: the stand-alone
  *              sph_hip_integrate reads the gauges first, after bringing the cell structure up to date as
  *              the sampler does.  With no recording a step launches nothing for gauges.
- *   not done   slab contexts and REF mode are refused; there is no pressure reading; gauges do not move with
- *              an obstacle or a body, and solids do not shade a probe.
+ *   pressure   PRESSURE and PRESSURE_PATCH read the pressure field (below: pressure readings); they take the
+ *              values 4 and 5 - 3 stays refused as an unknown kind, which callers and tests rely on.
+ *   not done   slab contexts and REF mode are refused; pressures are not clamped or density-corrected; gauges
+ *              do not move with an obstacle or a body, and solids do not shade a probe.
  * sph_hip_set_gauges replaces the set (n = 0 clears it), ends a recording and waits for the steps already
  * queued.  SPH_HIP_ERR_INVALID, the previous set and recording kept, for a REF or slab context, n < 0,
  * n > SPH_HIP_MAX_GAUGES, a null list with n > 0, an unknown kind, an axis outside 0..2, any float field
  * that is not finite (unused fields included), a used spacing that is not > 0, a used count < 1, more than
- * SPH_HIP_MAX_GAUGE_PROBES probes in one gauge, and an iso that is not > 0 for COLUMN and SECTION.  The
+ * SPH_HIP_MAX_GAUGE_PROBES probes in one gauge, and an iso that is not > 0 for COLUMN, SECTION and
+ * PRESSURE_PATCH.  The
  * set survives sph_hip_upload, sph_hip_set_params and sph_hip_set_arithmetic, and a recording goes on
  * across them.
  * sph_hip_get_gauges copies up to `capacity` gauges and returns how many are set.
@@ -818,15 +823,18 @@ int sph_hip_get_tracer_path(sph_hip_context* ctx, int first_row, int n_rows, flo
 #define SPH_HIP_GAUGE_POINT   0
 #define SPH_HIP_GAUGE_COLUMN  1
 #define SPH_HIP_GAUGE_SECTION 2
+#define SPH_HIP_GAUGE_PRESSURE       4  /* (3 is not a kind: it stays "unknown gauge kind") */
+#define SPH_HIP_GAUGE_PRESSURE_PATCH 5
 #define SPH_HIP_MAX_GAUGES        4096
 #define SPH_HIP_MAX_GAUGE_PROBES  4096
 typedef struct sph_hip_gauge {      /* field order is ABI: 40 bytes */
    int32_t kind;
-   int32_t axis;        /* COLUMN: the axis it climbs; SECTION: its normal; POINT: 0 */
-   float origin[3];     /* POINT: the point; COLUMN: the base; SECTION: the corner, origin[axis] = the plane */
-   float spacing[2];    /* COLUMN: [0]; SECTION: along the two other axes, ascending axis order */
-   int32_t count[2];    /* COLUMN: count[0] = m; SECTION: nu, nv */
-   float iso;           /* COLUMN, SECTION: a probe is wet when rho > iso (strictly; NaN is dry) */
+   int32_t axis;        /* COLUMN: the axis it climbs; SECTION, PRESSURE_PATCH: its normal; POINT, PRESSURE: 0 */
+   float origin[3];     /* POINT, PRESSURE: the point; COLUMN: the base; SECTION, PRESSURE_PATCH: the corner,
+                           origin[axis] = the plane */
+   float spacing[2];    /* COLUMN: [0]; SECTION, PRESSURE_PATCH: along the two other axes, ascending axis order */
+   int32_t count[2];    /* COLUMN: count[0] = m; SECTION, PRESSURE_PATCH: nu, nv */
+   float iso;           /* COLUMN, SECTION, PRESSURE_PATCH: a probe is wet when rho > iso (strictly; NaN is dry) */
 } sph_hip_gauge;
 typedef struct sph_hip_gauge_reading {   /* 24 bytes */
    float v[4];
@@ -839,6 +847,56 @@ int sph_hip_read_gauges(sph_hip_context* ctx, sph_hip_gauge_reading* out);
 int sph_hip_record_gauges(sph_hip_context* ctx, int rows, int every);
 int sph_hip_get_gauge_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_gauge_reading* out,
                              int32_t* steps_done);
+
+/* ---- pressure readings ------------------------------------------------------------------------ *
+ *
+ * The pressure at sensors on a wall or an obstacle - the second time series of a dam-break experiment -
+ * read on the device: at points and lattices (the two calls below) and by two gauge kinds that are set,
+ * read and recorded like the others.  No counterpart in the reference.  The operation-by-operation
+ * contract is in csrc/gauge_policy.h; all arithmetic is fp32, unfused, in the order written.
+ *   particle   rho_j is the FULL density pass's density of particle j in the state S: the particle itself
+ *              excluded, canonical order, the same bits in FULL and FULL_FAST and on every route (tiled,
+ *              give-up, SPH_HIP_UNTILED=1).  P_j = (rho_j - rho0) * stiffness, the pressure the
+ *              acceleration pass forms, with the context's constants at the time of the call or at the time
+ *              the step is enqueued.  P is NOT clamped: it is negative wherever rho_j < rho0, as in the
+ *              reference.
+ *   probe      over the sampler's members of x with the sampler's terms t_j (a particle at x included):
+ *              pw = sum of t_j * P_j in canonical order beside the sampler's rho and count;
+ *              pressure = rho > 0 ? pw / rho : 0 - Shepard normalisation, the velocity's rule.  A probe at a
+ *              wall has half its support empty: the normalisation is what makes that reading a pressure.
+ *              A non-finite or out-of-box probe gives 0, 0, 0 as in the sampler.
+ *   kinds      PRESSURE        one probe at origin: v = {pressure, rho, pw, 0}, n = count, k = 0:
+ *                              sph_hip_sample_pressure_points there, bit for bit.
+ *              PRESSURE_PATCH  a sensor face or wall panel: SECTION's rectangle of probes, the same fields
+ *                              and probe order, lane l taking probes l, l + 64, ...  A probe is wet when
+ *                              rho > iso (strictly; NaN is dry).  A wet probe adds its pressure (the quotient
+ *                              of that probe) to the lane's a and its rho to r, both from 0.0f; a dry or
+ *                              missing probe adds nothing; the lanes are summed by SECTION's butterfly.
+ *                              area = spacing[0] * spacing[1]; v = {a_sum * area (the force along the normal
+ *                              by the pressure integral), (float)n * area (the wetted area),
+ *                              n > 0 ? a_sum / (float)n : 0 (the mean pressure over the wet probes), r_sum},
+ *                              n = the wet probes, k = 0.
+ *   when       in a step that fills a record row the pressure kinds are read after that step's density pass
+ *              and before its acceleration pass, from the densities that pass has just formed for the state
+ *              S_k the other gauges saw, into the same row; the other kinds are read where they were.
+ *              sph_hip_read_gauges, the two calls below and the stand-alone sph_hip_integrate form the
+ *              densities of the current state themselves, into a buffer of the context's own (4 bytes per
+ *              particle of the capacity, allocated at the first use), and trust no earlier
+ *              sph_hip_compute_density: both routes give the same bits.  Queued steps stay queued; no
+ *              particle, density, acceleration, count or energy changes by a bit.  A context without a
+ *              pressure kind launches what it launched before.
+ *   contexts   REF and slab contexts are refused.  With ports or obstacles the pressure kinds do what the
+ *              other gauges do: they read the fluid particles resident in that state and nothing else -
+ *              solids carry no density and do not shade a probe.
+ * sph_hip_sample_pressure_points / _lattice follow sph_hip_sample_points / _lattice: their refusals, any
+ * output may be NULL, the lattice's index order, the call synchronises and does not change the simulation.
+ * These entry points and kinds were added without a change of SPH_HIP_ABI_VERSION: no struct and no
+ * existing prototype changed. */
+/* n probes, xyz interleaved; pressure[n], density[n], count[n] */
+int sph_hip_sample_pressure_points(sph_hip_context* ctx, int n, const float* xyz, float* pressure, float* density,
+                                   int32_t* count);
+int sph_hip_sample_pressure_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                                    const int32_t dims[3], float* pressure, float* density, int32_t* count);
 
 /* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
  *

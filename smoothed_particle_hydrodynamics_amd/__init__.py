@@ -9,6 +9,6 @@ from .sph import SPH, Particle, SurfaceMesh, write_ply, Camera, RenderResult, wr
 from .lib import TIMING_OFF, TIMING_SUMS, TIMING_PHASES  # noqa: F401
 from .lib import Loads, LOAD_SOLIDS  # noqa: F401
 from .lib import Tracers, TracerPath  # noqa: F401
-from .gauges import PointGauge, ColumnGauge, SectionGauge, GaugeReadings, GaugeRecord  # noqa: F401
+from .gauges import PointGauge, ColumnGauge, SectionGauge, PressureGauge, PressurePatch, GaugeReadings, GaugeRecord  # noqa: F401
 from .ports import Emitter, Sink, PortTotals  # noqa: F401
 from . import gauges, obstacles, ports, scenes  # noqa: F401

@@ -23,6 +23,7 @@
 #include "scene_kernels.h"
 #include "tracer_kernels.h"
 #include "gauge_kernels.h"
+#include "pressure_kernels.h"
 #include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
@@ -373,11 +374,17 @@ struct sph_hip_context {
    std::unique_ptr<sph_hip_gauge[]> gauges_host;
    DevBuf<sph_hip_gauge> gauges_dev;
    DevBuf<sph_hip_gauge_reading> gauge_now;
+   // how many of them each kernel reads (gauge_policy.h: gauge_set_counts)
+   int n_gauges_field = 0, n_gauges_pressure = 0;
+   // the pressure kinds and samplers outside a step: the densities of the current sorted state, f32[capacity]
+   // (k_particle_density), allocated at the first use
+   DevBuf<float> rho_own;
    // recording (sph_hip_record_gauges): grec_rows rows of one reading per gauge; grec_step = steps enqueued
    // since the call, grec_filled = rows those steps have filled
    DevBuf<sph_hip_gauge_reading> grec_dev;
    int grec_rows = 0, grec_every = 1, grec_filled = 0;
    long long grec_step = 0;
+   int grec_row_now = -1;   // the row the step being enqueued fills (its pressure kinds follow its density pass)
 
    // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
    // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the

@@ -5,7 +5,9 @@
 // one trip of the wave each; a column makes one more trip in which lanes 0 and 1 walk its topmost wet probe and
 // the one above it again (a walk's result has one possible set of bits), so the whole kernel has one call
 // site of sample_walk.  Every branch on the gauge's kind and every trip count is the same in all 64 lanes.
-// Reads positions, masses and velocities of the state (posm, velp, cell_start); writes one reading per gauge.
+// Reads positions, masses and velocities of the state (posm, velp, cell_start); writes one reading per gauge
+// of a field kind.  A gauge of a pressure kind is k_gauges_pressure's (pressure_kernels.h): its wave returns at
+// once, nothing walked and nothing stored.
 #pragma once
 
 #include "cell_build.h"
@@ -25,7 +27,8 @@ k_gauges_read(const sph_hip_gauge* __restrict__ gauges, int n_gauges, const floa
    const int gi = blockIdx.x * GAUGES_PER_BLOCK + threadIdx.x / SPH_WAVE;
    if (gi >= n_gauges) return;   // (the whole wave)
    const sph_hip_gauge G = gauges[gi];
-   const int probes = gauge_probes(G);
+   if (gauge_read_by(G.kind) != GAUGE_LAUNCH_FIELD) return;   // (the whole wave) k_gauges_pressure's: nothing walked or stored
+   const int probes = gauge_field_probes(G);
    const int trips = gauge_trips(probes);
    const bool column = G.kind == SPH_HIP_GAUGE_COLUMN;
    const int all_trips = trips + (column ? 1 : 0);

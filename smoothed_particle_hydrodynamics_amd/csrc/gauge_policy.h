@@ -26,6 +26,25 @@
 //            summed by the butterfly x = x + x[lane ^ d], d = 1, 2, 4, 8, 16, 32; area = spacing[0] *
 //            spacing[1]; v = {a_sum * area, (float)n * area, r_sum, 0}, n = wet probes, k = 0
 // With no particle resident every walk gives zeros.
+//
+// The pressure kinds (PRESSURE = 4, PRESSURE_PATCH = 5; 3 stays refused as an unknown kind).  rho_j is the FULL
+// density pass's density of particle j in the state S (the particle itself excluded, canonical order,
+// density_untiled's arithmetic: the same bits in FULL and FULL_FAST and on every route), and
+//   P_j      = (rho_j - rho0) * stiffness: gauge_particle_pressure, the first line of neighbor_terms, with the
+//            context's constants at the time of the call or at the time the step is enqueued; not clamped
+//   pwalk(S, p): the sampler's members and terms t_j at p (a particle at p included) and, beside rho and count,
+//            pw = sum of t_j * P_j in canonical order (sample_walk_pressure: pressure_kernels.h)
+//   pressure = rho > 0 ? pw / rho : 0: gauge_pressure_quotient, the Shepard normalisation of the velocity.  A
+//            probe at a wall has half its support empty; the quotient is what makes that reading a pressure.
+//   PRESSURE        one probe at the origin: v = {pressure, rho, pw, 0}, n = count, k = 0
+//   PRESSURE_PATCH  SECTION's rectangle of probes, lane l taking probes l, l + 64, ...; every lane keeps
+//            a = r = 0.0f and, for its WET probes in order, a = a + pressure (the quotient of that probe),
+//            r = r + rho; a dry or missing probe adds nothing.  The 64 lane values are summed by SECTION's
+//            butterfly; area = spacing[0] * spacing[1]; v = {a_sum * area (the force along the normal),
+//            (float)n * area (the wetted area), n > 0 ? a_sum / (float)n : 0 (the mean pressure), r_sum},
+//            n = wet probes, k = 0
+// The field kinds are read by k_gauges_read and the pressure kinds by k_gauges_pressure (gauge_read_by); a
+// kernel walks and stores nothing for a gauge of the other family (gauge_field_probes, gauge_pressure_probes).
 #pragma once
 
 #include <math.h>
@@ -53,10 +72,53 @@ GAUGE_HD GAUGE_INLINE inline float gauge_pick(float a0, float a1, float a2, int 
    return axis == 0 ? a0 : axis == 1 ? a1 : a2;
 }
 
+// the pressure kinds: read by k_gauges_pressure, with the particle densities of the state
+GAUGE_HD GAUGE_INLINE inline bool gauge_is_pressure(int kind)
+{
+   return kind == SPH_HIP_GAUGE_PRESSURE || kind == SPH_HIP_GAUGE_PRESSURE_PATCH;
+}
+
+// the kinds whose probes are SECTION's rectangle
+GAUGE_HD GAUGE_INLINE inline bool gauge_is_rectangle(int kind)
+{
+   return kind == SPH_HIP_GAUGE_SECTION || kind == SPH_HIP_GAUGE_PRESSURE_PATCH;
+}
+
 // probes of one gauge (checked: at most SPH_HIP_MAX_GAUGE_PROBES)
 GAUGE_HD GAUGE_INLINE inline int gauge_probes(const sph_hip_gauge& g)
 {
-   return g.kind == SPH_HIP_GAUGE_COLUMN ? g.count[0] : g.kind == SPH_HIP_GAUGE_SECTION ? g.count[0] * g.count[1] : 1;
+   return g.kind == SPH_HIP_GAUGE_COLUMN ? g.count[0] : gauge_is_rectangle(g.kind) ? g.count[0] * g.count[1] : 1;
+}
+
+// which launch reads a gauge: the field kinds by k_gauges_read, the pressure kinds by k_gauges_pressure
+#define GAUGE_LAUNCH_FIELD 0
+#define GAUGE_LAUNCH_PRESSURE 1
+GAUGE_HD GAUGE_INLINE inline int gauge_read_by(int kind) { return gauge_is_pressure(kind) ? GAUGE_LAUNCH_PRESSURE : GAUGE_LAUNCH_FIELD; }
+
+// the probes a kernel walks for a gauge: none for a gauge the other kernel reads (and then it stores nothing)
+GAUGE_HD GAUGE_INLINE inline int gauge_field_probes(const sph_hip_gauge& g)
+{
+   return gauge_read_by(g.kind) == GAUGE_LAUNCH_FIELD ? gauge_probes(g) : 0;
+}
+
+GAUGE_HD GAUGE_INLINE inline int gauge_pressure_probes(const sph_hip_gauge& g)
+{
+   return gauge_read_by(g.kind) == GAUGE_LAUNCH_PRESSURE ? gauge_probes(g) : 0;
+}
+
+// how many gauges of a (checked) set each launch reads: out[GAUGE_LAUNCH_FIELD], out[GAUGE_LAUNCH_PRESSURE]
+inline void gauge_set_counts(const sph_hip_gauge* list, int n, int out[2])
+{
+   out[0] = out[1] = 0;
+   for (int i = 0; i < n; i++) out[gauge_read_by(list[i].kind)]++;
+}
+
+// whether a set holds a pressure kind
+inline bool gauge_set_has_pressure(const sph_hip_gauge* list, int n)
+{
+   int c[2];
+   gauge_set_counts(list, n, c);
+   return c[GAUGE_LAUNCH_PRESSURE] > 0;
 }
 
 // trips of the wave over a gauge's probes
@@ -79,7 +141,7 @@ GAUGE_HD GAUGE_INLINE inline void gauge_probe(const sph_hip_gauge& g, int q, flo
       px = g.axis == 0 ? c : px;
       py = g.axis == 1 ? c : py;
       pz = g.axis == 2 ? c : pz;
-   } else if (g.kind == SPH_HIP_GAUGE_SECTION) {
+   } else if (gauge_is_rectangle(g.kind)) {
       const int i = q % g.count[0], j = q / g.count[0];
       // the other two axes in ascending order: (1, 2), (0, 2), (0, 1)
       const float cu = (g.axis == 0 ? g.origin[1] : g.origin[0]) + (float)i * g.spacing[0];
@@ -161,6 +223,51 @@ GAUGE_HD GAUGE_INLINE inline sph_hip_gauge_reading gauge_section_reading(const s
    return r;
 }
 
+// the pressure of a particle of density rho_j: the first line of neighbor_terms (pair_math.h); not clamped
+GAUGE_HD GAUGE_INLINE inline float gauge_particle_pressure(float rho_j, float rho0, float stiffness)
+{
+   return (rho_j - rho0) * stiffness;
+}
+
+// Shepard normalisation of a probe's pressure sum (SampleSum::store's rule for the velocity)
+GAUGE_HD GAUGE_INLINE inline float gauge_pressure_quotient(float pw, float rho) { return rho > 0.0f ? pw / rho : 0.0f; }
+
+// rho, pw, count: the raw sums of the probe's pressure walk
+GAUGE_HD GAUGE_INLINE inline sph_hip_gauge_reading gauge_pressure_reading(float rho, float pw, int count)
+{
+   sph_hip_gauge_reading r;
+   r.v[0] = gauge_pressure_quotient(pw, rho);
+   r.v[1] = rho;
+   r.v[2] = pw;
+   r.v[3] = 0.0f;
+   r.n = count;
+   r.k = 0;
+   return r;
+}
+
+// what a probe adds to its lane's accumulators of a patch: its pressure and its density when wet, nothing when
+// dry or missing
+GAUGE_HD GAUGE_INLINE inline void gauge_patch_add(bool wet, float rho, float pw, float& a, float& r)
+{
+   const float pr = gauge_pressure_quotient(pw, rho);
+   a = wet ? a + pr : a;
+   r = wet ? r + rho : r;
+}
+
+// n wet probes; a_sum, r_sum: the butterfly sums of the lanes' accumulators
+GAUGE_HD GAUGE_INLINE inline sph_hip_gauge_reading gauge_patch_reading(const sph_hip_gauge& g, int n, float a_sum, float r_sum)
+{
+   const float area = g.spacing[0] * g.spacing[1];
+   sph_hip_gauge_reading r;
+   r.v[0] = a_sum * area;
+   r.v[1] = (float)n * area;
+   r.v[2] = n > 0 ? a_sum / (float)n : 0.0f;
+   r.v[3] = r_sum;
+   r.n = n;
+   r.k = 0;
+   return r;
+}
+
 // ---- checks ---------------------------------------------------------------------------------------------
 // Why a gauge set is refused, or nullptr.
 inline const char* gauge_check(const sph_hip_gauge* list, int n)
@@ -170,13 +277,14 @@ inline const char* gauge_check(const sph_hip_gauge* list, int n)
    if (n > 0 && !list) return "null gauge list";
    for (int i = 0; i < n; i++) {
       const sph_hip_gauge& g = list[i];
-      if (g.kind != SPH_HIP_GAUGE_POINT && g.kind != SPH_HIP_GAUGE_COLUMN && g.kind != SPH_HIP_GAUGE_SECTION)
+      if (g.kind != SPH_HIP_GAUGE_POINT && g.kind != SPH_HIP_GAUGE_COLUMN && g.kind != SPH_HIP_GAUGE_SECTION &&
+          !gauge_is_pressure(g.kind))
          return "unknown gauge kind";
       if (g.axis < 0 || g.axis > 2) return "axis must be 0, 1 or 2";
       if (!(gauge_finite(g.origin[0]) && gauge_finite(g.origin[1]) && gauge_finite(g.origin[2]) &&
             gauge_finite(g.spacing[0]) && gauge_finite(g.spacing[1]) && gauge_finite(g.iso)))
          return "a field that is not finite";
-      if (g.kind == SPH_HIP_GAUGE_POINT) continue;
+      if (g.kind == SPH_HIP_GAUGE_POINT || g.kind == SPH_HIP_GAUGE_PRESSURE) continue;
       const int used = g.kind == SPH_HIP_GAUGE_COLUMN ? 1 : 2;
       long long probes = 1;
       for (int a = 0; a < used; a++) {
@@ -185,7 +293,7 @@ inline const char* gauge_check(const sph_hip_gauge* list, int n)
          probes *= g.count[a];
       }
       if (probes > SPH_HIP_MAX_GAUGE_PROBES) return "more than SPH_HIP_MAX_GAUGE_PROBES probes in one gauge";
-      if (!(g.iso > 0.0f)) return "iso must be > 0";
+      if (!(g.iso > 0.0f)) return g.kind == SPH_HIP_GAUGE_PRESSURE_PATCH ? "a pressure patch's iso must be > 0" : "iso must be > 0";
    }
    return nullptr;
 }

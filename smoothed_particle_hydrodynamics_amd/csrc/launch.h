@@ -754,11 +754,13 @@ int launch_tracers(sph_hip_context* ctx)
 }
 
 // ---- gauges (gauge_kernels.h; decisions: gauge_policy.h) -------------------------------------------------
-// Every gauge evaluated once in the sorted state a cell build has just produced, into `row` (one reading per
-// gauge).  Nothing here synchronises.
+// Every gauge of a field kind evaluated once in the sorted state a cell build has just produced, into `row`
+// (one reading per gauge; the entries of the pressure kinds are launch_gauges_pressure_into's, and a set
+// without a field kind launches nothing here).  Nothing here synchronises.
 int launch_gauges_into(sph_hip_context* ctx, sph_hip_gauge_reading* row)
 {
    const int n = ctx->n_gauges;
+   if (!gauges_launch_field(ctx->n_gauges_field)) return SPH_HIP_OK;
    const sph_hip_params& p = ctx->prm;
    const PairConsts k = pair_consts(p, ctx->fast != 0);
    bind_flags([&](auto U) {
@@ -770,14 +772,71 @@ int launch_gauges_into(sph_hip_context* ctx, sph_hip_gauge_reading* row)
    return SPH_HIP_OK;
 }
 
-// One step of a gauge recording: the step is counted, and where it fills a row the gauges are read into it.
+// The densities of the current sorted state into the context's own buffer (allocated here at the first
+// use): behind a cell build, outside a step.  Writes nothing else.
+int launch_particle_density(sph_hip_context* ctx)
+{
+   const int n = ctx->n;
+   if (n == 0) return SPH_HIP_OK;
+   if (!ctx->rho_own) {
+      if (dev_alloc(ctx->rho_own, (size_t)ctx->capacity) != hipSuccess) {
+         (void)hipGetLastError();
+         ctx->err = "pressure readings: cannot allocate the density buffer of " + std::to_string(ctx->capacity) + " particles";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+   }
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   bind_flags([&](auto U) {
+      hipLaunchKernelGGL((k_particle_density<U.value>), dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,
+                         ctx->posm[ctx->cur], ctx->cell_start, ctx->meta, ctx->grid, k, ctx->rho_own);
+   }, unit_scale(ctx->prm));
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// The pressure kinds: k_gauges_pressure into `row`, with the particle densities of `source`
+// (launch_policy.h: gauge_density_source).  A set without a pressure kind launches nothing.
+int launch_gauges_pressure_into(sph_hip_context* ctx, sph_hip_gauge_reading* row, int source)
+{
+   const int n = ctx->n_gauges;
+   if (!gauges_launch_pressure(ctx->n_gauges_pressure)) return SPH_HIP_OK;
+   if (source == GAUGE_DENSITY_OWN) {
+      int rc = launch_particle_density(ctx);
+      if (rc) return rc;
+   }
+   const float* prho = source == GAUGE_DENSITY_OF_STEP ? ctx->rho.get() : ctx->rho_own.get();
+   const sph_hip_params& p = ctx->prm;
+   const PairConsts k = pair_consts(p, ctx->fast != 0);
+   bind_flags([&](auto U) {
+      hipLaunchKernelGGL((k_gauges_pressure<U.value>), dim3(div_up(n, GAUGES_PER_BLOCK)), dim3(256), 0, ctx->stream,
+                         ctx->gauges_dev, n, ctx->posm[ctx->cur], prho, ctx->cell_start, ctx->grid, k,
+                         ctx->n > 0 ? 1 : 0, row);
+   }, unit_scale(p));
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// One step of a gauge recording: the step is counted, and where it fills a row the field kinds are read into
+// it; the row is remembered for the pressure kinds (launch_gauges_pressure).
 int launch_gauges(sph_hip_context* ctx)
 {
+   ctx->grec_row_now = -1;
    if (ctx->grec_rows == 0) return SPH_HIP_OK;
    const int r = gauge_record_row(++ctx->grec_step, ctx->grec_every, ctx->grec_rows);
    if (r < 0) return SPH_HIP_OK;
+   ctx->grec_row_now = r;
    ctx->grec_filled = r + 1;
    return launch_gauges_into(ctx, ctx->grec_dev.get() + (size_t)r * (size_t)ctx->n_gauges);
+}
+
+// The pressure kinds of the row launch_gauges has just opened, if any: behind the step's density pass
+// (GAUGE_DENSITY_OF_STEP) or, in the stand-alone integrate, with the context's own densities.
+int launch_gauges_pressure(sph_hip_context* ctx, int source)
+{
+   const int r = ctx->grec_row_now;
+   ctx->grec_row_now = -1;
+   if (!step_reads_pressure(r, ctx->n_gauges_pressure)) return SPH_HIP_OK;
+   return launch_gauges_pressure_into(ctx, ctx->grec_dev.get() + (size_t)r * (size_t)ctx->n_gauges, source);
 }
 
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
@@ -868,6 +927,8 @@ int step_impl(sph_hip_context* ctx, bool timed)
    if ((rc = launch_find_neighbors(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 2, st))) return rc;
    if ((rc = launch_density(ctx))) return rc;
+   // the pressure kinds of a row this step fills: with the densities of S_k the pass has just formed
+   if (ctx->grec_row_now >= 0 && (rc = launch_gauges_pressure(ctx, gauge_density_source(true)))) return rc;
    if ((rc = mark_phase(ctx, se, 3, st))) return rc;
    // a context that holds the whole grid and has never exchanged anything: the integrate also
    // hashes and counts for the next cell build - and the tiled acceleration pass does both itself

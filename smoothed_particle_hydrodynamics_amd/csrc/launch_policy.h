@@ -320,6 +320,25 @@ inline bool ports_must_tighten(int bound, int m, int capacity) { return (long lo
 // partial layer is ever emitted)
 inline bool ports_layer_fits(int live, int m, int capacity) { return (long long)live + m <= (long long)capacity; }
 
+// ---- gauges (gauge_policy.h) -------------------------------------------------------------------
+// Which kernels one evaluation of a gauge set launches: k_gauges_read where the set holds a field kind,
+// k_gauges_pressure where it holds a pressure kind (gauge_set_counts).  A set without a pressure kind
+// launches what it always launched.
+inline bool gauges_launch_field(int n_field) { return n_field > 0; }
+inline bool gauges_launch_pressure(int n_pressure) { return n_pressure > 0; }
+
+// Where the pressure kinds' particle densities come from.  Inside a step, after its density pass, the
+// pass's own array (of exactly the state the other gauges saw); everywhere else - sph_hip_read_gauges,
+// the pressure samplers, the stand-alone sph_hip_integrate - the context's own buffer, filled by
+// k_particle_density behind the cell build, whatever an earlier sph_hip_compute_density left.
+#define GAUGE_DENSITY_OF_STEP 0
+#define GAUGE_DENSITY_OWN 1
+inline int gauge_density_source(bool behind_step_density) { return behind_step_density ? GAUGE_DENSITY_OF_STEP : GAUGE_DENSITY_OWN; }
+
+// Whether a step reads pressure gauges between its density and acceleration passes: it fills row `row`
+// of a recording (-1: none) and the set holds a pressure kind.
+inline bool step_reads_pressure(int row, int n_pressure) { return row >= 0 && gauges_launch_pressure(n_pressure); }
+
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
 // slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary

@@ -876,6 +876,9 @@ int sph_hip_integrate(sph_hip_context* ctx)
       if (ctx->n > 0 && (rc = sample_prepare(ctx))) return rc;
       if (ctx->n_tracers > 0 && (rc = launch_tracers(ctx))) return rc;
       if (ctx->grec_rows > 0 && (rc = launch_gauges(ctx))) return rc;
+      // the pressure kinds, with densities formed here: whatever the caller's last sph_hip_compute_density left
+      // in the context is not trusted
+      if (ctx->grec_row_now >= 0 && (rc = launch_gauges_pressure(ctx, gauge_density_source(false)))) return rc;
    }
    if ((rc = drop_prehash(ctx))) return rc;   // the state moves on without a new hash
    return launch_integrate(ctx);
@@ -1030,6 +1033,7 @@ void stop_gauge_recording(sph_hip_context* ctx)
    ctx->grec_rows = ctx->grec_filled = 0;
    ctx->grec_every = 1;
    ctx->grec_step = 0;
+   ctx->grec_row_now = -1;
 }
 } // namespace
 
@@ -1059,6 +1063,10 @@ int sph_hip_set_gauges(sph_hip_context* ctx, const sph_hip_gauge* list, int n)
    ctx->gauges_dev = std::move(dev);
    ctx->gauge_now = std::move(now);
    ctx->n_gauges = n;
+   int reads[2];
+   gauge_set_counts(ctx->gauges_host.get(), n, reads);
+   ctx->n_gauges_field = reads[GAUGE_LAUNCH_FIELD];
+   ctx->n_gauges_pressure = reads[GAUGE_LAUNCH_PRESSURE];
    stop_gauge_recording(ctx);
    return SPH_HIP_OK;
 }
@@ -1082,6 +1090,7 @@ int sph_hip_read_gauges(sph_hip_context* ctx, sph_hip_gauge_reading* out)
    if (!out) return refuse(ctx, "sph_hip_read_gauges", "null output array");
    if (ctx->n > 0 && (rc = sample_prepare(ctx))) return rc;
    if ((rc = launch_gauges_into(ctx, ctx->gauge_now))) return rc;
+   if ((rc = launch_gauges_pressure_into(ctx, ctx->gauge_now, gauge_density_source(false)))) return rc;
    SPH_TRY(hipMemcpyAsync(out, ctx->gauge_now, sizeof(sph_hip_gauge_reading) * (size_t)n, hipMemcpyDeviceToHost,
                           ctx->stream));
    SPH_TRY(hipStreamSynchronize(ctx->stream));
@@ -1758,6 +1767,118 @@ int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const fl
             if (density) SPH_TRY(copy_out(density, srho, sizeof(float)));
             if (velocity_xyz) SPH_TRY(copy_out(velocity_xyz, svel, 3 * sizeof(float)));
             if (count) SPH_TRY(copy_out(count, scnt, sizeof(int32_t)));
+         }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// ---- pressure samplers (pressure_kernels.h; contract: gauge_policy.h) ------------------------------
+// The sampler's calls with the pressure walk: behind the cell build the densities of the current state
+// are formed into the context's own buffer (launch_particle_density), then the probes are walked.
+
+int sph_hip_sample_pressure_points(sph_hip_context* ctx, int n, const float* xyz, float* pressure, float* density,
+                                   int32_t* count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (n < 0 || (n > 0 && !xyz)) {
+      ctx->err = "sph_hip_sample_pressure_points: negative count or null probe array";
+      return SPH_HIP_ERR_INVALID;
+   }
+   if ((rc = sample_check(ctx, "sph_hip_sample_pressure_points"))) return rc;
+   if (n == 0) return SPH_HIP_OK;
+   if (ctx->n == 0) {
+      if (pressure) memset(pressure, 0, sizeof(float) * (size_t)n);
+      return sample_zero((size_t)n, density, nullptr, count);
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   if ((rc = launch_particle_density(ctx))) return rc;
+   const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS);
+   if ((rc = ctx->sample_buf.reserve(ctx, (size_t)chunk * 6))) return rc;
+   float* sxyz = ctx->sample_buf;
+   float* sprs = sxyz + 3 * (size_t)chunk;
+   float* srho = sprs + (size_t)chunk;
+   int32_t* scnt = reinterpret_cast<int32_t*>(srho + (size_t)chunk);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   hipStream_t st = ctx->stream;
+   for (int p0 = 0; p0 < n; p0 += chunk) {
+      const int m = n - p0 < chunk ? n - p0 : chunk;
+      SPH_TRY(hipMemcpyAsync(sxyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+      bind_flags([&](auto U) {
+         hipLaunchKernelGGL((k_sample_pressure_points<U.value>), dim3(div_up(m, 256)), dim3(256), 0, st, sxyz, m,
+                            ctx->posm[ctx->cur], ctx->rho_own, ctx->cell_start, ctx->grid, k, sprs, srho, scnt);
+      }, unit_scale(ctx->prm));
+      SPH_TRY(hipGetLastError());
+      if (pressure) SPH_TRY(hipMemcpyAsync(pressure + p0, sprs, sizeof(float) * m, hipMemcpyDeviceToHost, st));
+      if (density) SPH_TRY(hipMemcpyAsync(density + p0, srho, sizeof(float) * m, hipMemcpyDeviceToHost, st));
+      if (count) SPH_TRY(hipMemcpyAsync(count + p0, scnt, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+   }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+int sph_hip_sample_pressure_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                                    const int32_t dims[3], float* pressure, float* density, int32_t* count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, "sph_hip_sample_pressure_lattice", why);
+   if ((rc = sample_check(ctx, "sph_hip_sample_pressure_lattice"))) return rc;
+   if (ctx->n == 0) {
+      const size_t total = (size_t)dims[0] * dims[1] * dims[2];
+      if (pressure) memset(pressure, 0, sizeof(float) * total);
+      return sample_zero(total, density, nullptr, count);
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   if ((rc = launch_particle_density(ctx))) return rc;
+   double cells[3];
+   sample_spacing_cells(spacing, ctx->grid.inv, cells);
+   const SampleBrick brick = sample_brick(dims, cells);
+   const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
+   const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
+   if ((rc = ctx->sample_buf.reserve(ctx, chunk_points * 3))) return rc;
+   float* sprs = ctx->sample_buf;
+   float* srho = sprs + chunk_points;
+   int32_t* scnt = reinterpret_cast<int32_t*>(srho + chunk_points);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const bool unit = unit_scale(ctx->prm);
+   hipStream_t st = ctx->stream;
+   SampleLattice L = lattice_of(origin, spacing, brick);
+   // (sph_hip_sample_lattice's copy of a chunk's box into the caller's arrays; every array is 4 bytes a point)
+   auto copy_out = [&](void* dst, const void* src) -> hipError_t {
+      const size_t elem = sizeof(float);
+      char* d = (char*)dst;
+      const char* s = (const char*)src;
+      const size_t plane = (size_t)dims[0] * dims[1];
+      if (L.ex == dims[0] && L.ey == dims[1])
+         return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem,
+                               hipMemcpyDeviceToHost, st);
+      for (int z = 0; z < L.ez; z++) {
+         const hipError_t e = hipMemcpy2DAsync(
+             d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
+             s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
+             hipMemcpyDeviceToHost, st);
+         if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
+   };
+   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += c.ez)
+      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += c.ey)
+         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += c.ex) {
+            L.ex = dims[0] - L.i0 < c.ex ? dims[0] - L.i0 : c.ex;
+            L.ey = dims[1] - L.j0 < c.ey ? dims[1] - L.j0 : c.ey;
+            L.ez = dims[2] - L.k0 < c.ez ? dims[2] - L.k0 : c.ez;
+            L.bricks_x = div_up(L.ex, L.bx);
+            L.bricks_y = div_up(L.ey, L.by);
+            const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
+            bind_flags([&](auto U) {
+               hipLaunchKernelGGL((k_sample_pressure_lattice<U.value>), dim3(bricks), dim3(SAMPLE_THREADS), 0, st, L,
+                                  ctx->posm[ctx->cur], ctx->rho_own, ctx->cell_start, ctx->grid, k, sprs, srho, scnt);
+            }, unit);
+            SPH_TRY(hipGetLastError());
+            if (pressure) SPH_TRY(copy_out(pressure, sprs));
+            if (density) SPH_TRY(copy_out(density, srho));
+            if (count) SPH_TRY(copy_out(count, scnt));
          }
    SPH_TRY(hipStreamSynchronize(st));
    return SPH_HIP_OK;

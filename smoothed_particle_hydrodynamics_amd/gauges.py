@@ -1,6 +1,6 @@
 """Gauges (include/sph_hip.h: sph_hip_set_gauges): fixed instruments that read the field inside the step.
 
-PointGauge, ColumnGauge and SectionGauge describe one instrument each; SPH.setGauges takes a list of them,
+PointGauge, ColumnGauge, SectionGauge, PressureGauge and PressurePatch describe one instrument each; SPH.setGauges takes a list of them,
 SPH.readGauges evaluates them now, SPH.recordGauges keeps one row of readings per recorded step on the device
 and SPH.getGaugeRecord returns the rows as a GaugeRecord.  The arithmetic of every reading is in
 csrc/gauge_policy.h."""
@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 
 POINT, COLUMN, SECTION = 0, 1, 2       # SPH_HIP_GAUGE_*
+PRESSURE, PRESSURE_PATCH = 4, 5        # (3 is not a kind: the library refuses it as unknown)
 MAX_GAUGES = 4096                      # SPH_HIP_MAX_GAUGES
 MAX_GAUGE_PROBES = 4096                # SPH_HIP_MAX_GAUGE_PROBES
 
@@ -62,6 +63,25 @@ class SectionGauge(collections.namedtuple("SectionGauge", ["corner", "axis", "sp
         return _struct(SECTION, self.axis, self.corner, self.spacing, self.shape, self.iso)
 
 
+class PressureGauge(collections.namedtuple("PressureGauge", ["point"])):
+    """The Shepard-normalised pressure at `point` - the members' (rho_j - rho0) * stiffness weighted by the
+    sampler's terms - with the sampler's density, the raw pressure sum and the member count."""
+    __slots__ = ()
+
+    def to_struct(self):
+        return _struct(PRESSURE, 0, self.point)
+
+
+class PressurePatch(collections.namedtuple("PressurePatch", ["corner", "axis", "spacing", "shape", "iso"])):
+    """A sensor face or wall panel: SectionGauge's rectangle of probes on the plane through `corner` with normal
+    `axis`.  Over the probes whose density exceeds `iso`: the force along the normal (the sum of their pressures
+    times the area of a probe), the wetted area, the mean pressure and the sum of the densities."""
+    __slots__ = ()
+
+    def to_struct(self):
+        return _struct(PRESSURE_PATCH, self.axis, self.corner, self.spacing, self.shape, self.iso)
+
+
 def from_struct(g):
     o = tuple(g.origin)
     if g.kind == POINT:
@@ -70,11 +90,16 @@ def from_struct(g):
         return ColumnGauge(o, g.axis, g.spacing[0], g.count[0], g.iso)
     if g.kind == SECTION:
         return SectionGauge(o, g.axis, tuple(g.spacing), tuple(g.count), g.iso)
+    if g.kind == PRESSURE:
+        return PressureGauge(o)
+    if g.kind == PRESSURE_PATCH:
+        return PressurePatch(o, g.axis, tuple(g.spacing), tuple(g.count), g.iso)
     raise ValueError("unknown gauge kind %d" % g.kind)
 
 
 def as_array(gauges):
-    """(SphGauge array or None, n) of a list of PointGauge / ColumnGauge / SectionGauge / SphGauge."""
+    """(SphGauge array or None, n) of a list of PointGauge / ColumnGauge / SectionGauge / PressureGauge /
+    PressurePatch / SphGauge."""
     gauges = list(gauges)
     n = len(gauges)
     if n == 0:
@@ -85,15 +110,41 @@ def as_array(gauges):
     return arr, n
 
 
-# sph_hip_read_gauges' answer, one entry per gauge in list order: v float32 (n, 4), n and k int32 (n,)
-GaugeReadings = collections.namedtuple("GaugeReadings", ["v", "n", "k"])
+def _pressure_column(readings, i, gauge):
+    """where gauge i keeps its pressure: a point's v[0], a patch's mean v[2].  The kind is `gauge` (a kind value
+    or a PressureGauge / PressurePatch) where given, else the one SPH.readGauges / getGaugeRecord noted."""
+    kind = gauge
+    if kind is None:
+        if readings.kinds is None:
+            raise ValueError("the kinds of these readings are not known: pass the gauge")
+        kind = readings.kinds[i]
+    if kind == PRESSURE or isinstance(kind, PressureGauge):
+        return 0
+    if kind == PRESSURE_PATCH or isinstance(kind, PressurePatch):
+        return 2
+    raise ValueError("gauge %d is not a pressure gauge" % i)
+
+
+class GaugeReadings(collections.namedtuple("GaugeReadings", ["v", "n", "k"])):
+    """sph_hip_read_gauges' answer, one entry per gauge in list order: v float32 (n, 4), n and k int32 (n,).
+    `kinds` (not a field) holds the gauges' kinds where SPH.readGauges made the readings."""
+    kinds = None
+
+    def pressure(self, i, gauge=None):
+        """the pressure of gauge i: a PressureGauge's reading, or the mean over the wet probes of a PressurePatch"""
+        return self.v[i, _pressure_column(self, i, gauge)]
+
+    def force(self, i):
+        """a pressure patch's force along its normal"""
+        return self.v[i, 0]
 
 
 class GaugeRecord(collections.namedtuple("GaugeRecord", ["steps", "v", "n", "k"])):
     """The rows of a gauge recording (sph_hip_get_gauge_record): steps int32 (rows,), the steps completed since
     recordGauges when each row was read (row 0: the state at the call); the raw readings v float32
-    (rows, gauges, 4), n and k int32 (rows, gauges).  The helpers return the time series of gauge i."""
-    __slots__ = ()
+    (rows, gauges, 4), n and k int32 (rows, gauges).  The helpers return the time series of gauge i.  `kinds`
+    (not a field) holds the gauges' kinds where SPH.getGaugeRecord made the record."""
+    kinds = None
 
     def level(self, i):
         """a column's free-surface level along its axis"""
@@ -110,3 +161,12 @@ class GaugeRecord(collections.namedtuple("GaugeRecord", ["steps", "v", "n", "k"]
     def probe(self, i):
         """a point gauge's (density, velocity[3]) series"""
         return self.v[:, i, 0], self.v[:, i, 1:4]
+
+    def pressure(self, i, gauge=None):
+        """the pressure series of gauge i: a PressureGauge's reading, or the mean over the wet probes of a
+        PressurePatch"""
+        return self.v[:, i, _pressure_column(self, i, gauge)]
+
+    def force(self, i):
+        """a pressure patch's force along its normal: the sum of its wet probes' pressures times a probe's area"""
+        return self.v[:, i, 0]

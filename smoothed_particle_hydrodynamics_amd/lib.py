@@ -124,6 +124,9 @@ PROTOTYPES = {
     "sph_hip_download_grid_counts": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_download_neighbor_lists": (C.c_int, [_ctx, C.c_void_p, C.c_void_p]),
     "sph_hip_sample_points": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_sample_pressure_points": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_sample_pressure_lattice": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3),
+                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_sample_lattice": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3),
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_extract_surface": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3), C.c_float,

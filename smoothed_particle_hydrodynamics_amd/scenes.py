@@ -369,6 +369,37 @@ def dam_break_gauged(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), n
     return p, pos, vel, mass, gauges
 
 
+def dam_break_sensors(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42, gravity=-9.81,
+                      points=16):
+    """The surging dam of dam_break_gauged with the pressure sensors of a dam-break experiment: `points`
+    PressureGauges up the downstream wall - the wall the simulation keeps, x = params.max_x, the voxel grid's
+    edge at or beyond box[0] - on the column's mid-plane in z, one kernel radius apart from half a radius above
+    the floor; one PressurePatch over the lower quarter of that wall (normal x) and one on the floor under the
+    column (normal y), h/2 between probes (coarser where a patch would exceed its probe limit).  iso is
+    dam_break_gauged's: half the sampler's density deep inside the column.  Returns (params, pos, vel, mass,
+    gauges): setParticles, then setGauges."""
+    from .gauges import MAX_GAUGE_PROBES, PressureGauge, PressurePatch
+    p, pos, vel, mass, gauged = dam_break_gauged(n, surge, box, fill, neighbors, seed, gravity)
+    iso = gauged[0].iso
+    h = float(p.h)
+    column = [box[c] * fill[c] for c in range(3)]
+    wall = (float(p.max_x), float(p.max_y), float(p.max_z))
+    gauges = [PressureGauge((wall[0], (0.5 + i) * h, 0.5 * box[2])) for i in range(int(points))
+              if (0.5 + i) * h <= wall[1]]
+
+    def patch(corner, axis, extent):
+        s = 0.5 * h
+        shape = [int(math.floor(e / s)) + 1 for e in extent]
+        while shape[0] * shape[1] > MAX_GAUGE_PROBES:
+            s *= 2.0
+            shape = [int(math.floor(e / s)) + 1 for e in extent]
+        return PressurePatch(corner, axis, (s, s), tuple(shape), iso)
+
+    gauges.append(patch((wall[0], 0.0, 0.0), 0, (0.25 * wall[1], wall[2])))     # u = y, v = z
+    gauges.append(patch((0.0, 0.0, 0.0), 1, (column[0], column[2])))            # u = x, v = z
+    return p, pos, vel, mass, gauges
+
+
 def filling_tank(capacity, box=(1.0, 1.0, 1.0), inlet=1.0 / 3.0, speed=2.0, neighbors=32.0, gravity=-9.81):
     """An empty tank (gravity along -y, the walls on) that fills through an inlet under its lid: one Emitter with
     normal y, a square lattice `inlet` of the tank's width across, centred, one kernel radius below the lid,

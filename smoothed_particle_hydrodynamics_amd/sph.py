@@ -359,8 +359,9 @@ class SPH(Context):
 
     # ---- gauges (sph_hip_set_gauges) -------------------------------------------------------------
     def setGauges(self, gauges):
-        """Replace the gauges with `gauges` (gauges.PointGauge / ColumnGauge / SectionGauge; an empty list clears
-        them): fixed instruments evaluated on the device (include/sph_hip.h: gauges).  A recording ends."""
+        """Replace the gauges with `gauges` (gauges.PointGauge / ColumnGauge / SectionGauge / PressureGauge /
+        PressurePatch; an empty list clears them): fixed instruments evaluated on the device (include/sph_hip.h:
+        gauges).  A recording ends."""
         arr, n = _G.as_array(gauges)
         self.call("sph_hip_set_gauges", arr, n)
 
@@ -373,6 +374,12 @@ class SPH(Context):
         self.call("sph_hip_get_gauges", arr, n)
         return [_G.from_struct(arr[i]) for i in range(n)]
 
+    def _gauge_kinds(self, n):
+        arr = (_G.SphGauge * max(n, 1))()
+        if n:
+            self.call("sph_hip_get_gauges", arr, n)
+        return tuple(int(arr[i].kind) for i in range(n))
+
     def readGauges(self):
         """Every gauge evaluated now, in the current state, as a GaugeReadings (sph_hip_read_gauges; synchronises;
         the simulation is not changed by the call)."""
@@ -380,7 +387,9 @@ class SPH(Context):
         out = np.zeros(n, _G.READING)
         if n:
             self.call("sph_hip_read_gauges", _ptr(out))
-        return _G.GaugeReadings(out["v"].copy(), out["n"].copy(), out["k"].copy())
+        got = _G.GaugeReadings(out["v"].copy(), out["n"].copy(), out["k"].copy())
+        got.kinds = self._gauge_kinds(n)
+        return got
 
     def recordGauges(self, rows, every=1):
         """Keep the gauges' readings in the state at this call and after every `every`-th step from it, `rows`
@@ -397,7 +406,9 @@ class SPH(Context):
         out = np.zeros((rows, n), _G.READING)
         if rows:
             self.call("sph_hip_get_gauge_record", 0, rows, _ptr(out), _ptr(steps))
-        return _G.GaugeRecord(steps, out["v"].copy(), out["n"].copy(), out["k"].copy())
+        got = _G.GaugeRecord(steps, out["v"].copy(), out["n"].copy(), out["k"].copy())
+        got.kinds = self._gauge_kinds(n)
+        return got
 
     # ---- slots ---------------------------------------------------------------------------------
     def step(self):
@@ -489,6 +500,33 @@ class SPH(Context):
         self.call("sph_hip_sample_lattice", C.byref(o), C.byref(s), C.byref(d), _ptr(rho), _ptr(vel),
                   _ptr(cnt))
         return rho, vel, cnt
+
+    def samplePressure(self, points):
+        """The pressure of the current state at `points` ((n, 3) float32): (pressure[n], density[n], count[n]).
+        Every particle's pressure is (rho_j - rho0) * stiffness with the density pass's rho_j of this state, not
+        clamped; a probe's is their Shepard-normalised sum over the sampler's members (include/sph_hip.h:
+        pressure readings).  The simulation is not changed by the call."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        prs = np.zeros(n, np.float32)
+        rho = np.zeros(n, np.float32)
+        cnt = np.zeros(n, np.int32)
+        self.call("sph_hip_sample_pressure_points", n, _ptr(pts), _ptr(prs), _ptr(rho), _ptr(cnt))
+        return prs, rho, cnt
+
+    def samplePressureLattice(self, origin, spacing, shape):
+        """The same on sampleLattice's lattice, shape = (nx, ny, nz): (pressure[nz, ny, nx],
+        density[nz, ny, nx], count[nz, ny, nx])."""
+        o, s, d, dims = _lattice(origin, spacing, shape)
+        grid = (max(dims[2], 0), max(dims[1], 0), max(dims[0], 0))
+        if grid[0] * grid[1] * grid[2] >= 2 ** 31:
+            raise ValueError("a lattice of more than 2^31 - 1 points")
+        prs = np.zeros(grid, np.float32)
+        rho = np.zeros(grid, np.float32)
+        cnt = np.zeros(grid, np.int32)
+        self.call("sph_hip_sample_pressure_lattice", C.byref(o), C.byref(s), C.byref(d), _ptr(prs), _ptr(rho),
+                  _ptr(cnt))
+        return prs, rho, cnt
 
     def extractSurface(self, origin, spacing, shape, iso, normals=True, velocity=False):
         """The surface {density > iso} of the lattice sampleLattice(origin, spacing, shape) would

@@ -1,0 +1,481 @@
+"""GPU: pressure readings (include/sph_hip.h: pressure readings).  k_particle_density, the pressure samplers and
+k_gauges_pressure - inside sph_hip_step, sph_hip_run and the phase calls, and in sph_hip_read_gauges - equal the
+numpy restatement (tests/pressure_emulation.py) on the state each step starts from, bit for bit; the step route
+(the density pass's own array) and the stand-alone route (k_particle_density) give the same bits on every density
+route; nothing a caller can read changes; recordings, constants, refusals and empty contexts.
+
+The scene is tests/test_gpu_gauges.py's - scenes.dam_break(20000, speed=4), gravity (0, -9.81, 0), walls on,
+h = 0.031 - with rho0 set to 0.9 of the median particle density: with the default rho0 = 0.1 no pressure of this
+scene is negative, and the contract's unclamped negative pressures would go unseen.
+
+The figures CPU_* are what the same scene gives on the CPU, the oracle's FULL step driving the restatement;
+`python tests/test_gpu_pressure.py` prints them again and tests/test_pressure_cpu.py checks them.  FULL mode is
+bit-identical to the oracle, so its counts equal them; FULL_FAST's arithmetic differs in the particles, so there
+every class must occur and the counts are printed."""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+import gauge_emulation as G
+import pressure_emulation as P
+import sample_emulation as SE
+from helpers import to_oracle_params
+
+pytestmark = pytest.mark.gpu
+
+F32 = np.float32
+STEPS = 30
+SPEED = 4.0
+
+# cpu_figures(): gauge evaluations of each class over the STEPS + 1 states (pressure_emulation.Info: patches fully
+# wet, partly wet and dry; points with a positive and with a negative pressure; points with count == 0)
+CPU_FULL = 88
+CPU_PARTIAL = 279
+CPU_DRY = 36
+CPU_POSITIVE = 123
+CPU_NEGATIVE = 360
+CPU_EMPTY = 75
+CPU_FIGURES = (CPU_FULL, CPU_PARTIAL, CPU_DRY, CPU_POSITIVE, CPU_NEGATIVE, CPU_EMPTY)
+
+PATCH_SHAPES = ((1, 1), (5, 13), (32, 32), (64, 64))
+
+
+def spread(extent, shape):
+    """the spacing that spreads `shape` probes over `extent` (one probe: any positive spacing)"""
+    return tuple(float(e) / (n - 1) if n > 1 else 0.1 for e, n in zip(extent, shape))
+
+
+@functools.lru_cache(maxsize=None)
+def scene():
+    """(params, pos, vel, mass, iso, gauges, field): the gauges' list and the indices in it of the existing kinds."""
+    from smoothed_particle_hydrodynamics_amd import scenes
+    from smoothed_particle_hydrodynamics_amd.gauges import ColumnGauge, PointGauge, PressureGauge, PressurePatch, SectionGauge
+    p, pos, vel, mass = scenes.dam_break(20000, speed=SPEED)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, -9.81, 0.0
+    p.rho0 = float(F32(0.9) * F32(np.median(P.particle_density(p, pos, vel, mass))))
+    x = pos.reshape(-1, 3)
+    own = SE.Grid(p, pos, vel, mass).sample(x, velocity=False)[0]
+    iso = float(F32(0.5) * F32(np.median(own)))
+    iso_wall = float(F32(0.5) * F32(iso))           # a probe on a wall has half its support empty
+    h = float(F32(p.h))
+    s = float(F32(0.5) * F32(p.h))
+    on = x[int(np.argmin(((x - np.array([0.05, 0.3, 0.5], F32)) ** 2).sum(1)))]
+    gauges = []
+    # 16 pressure points up the wall x = 0 behind the column, the upper ones above the free surface
+    for i in range(16):
+        gauges.append(PressureGauge((0.0, (0.5 + i) * 0.055, 0.5)))
+    gauges.append(PressureGauge(tuple(float(c) for c in on)))             # on a particle
+    gauges.append(PressureGauge((0.7, 0.5, 0.5)))                         # in empty space
+    gauges.append(ColumnGauge((0.05, 0.0, 0.5), 1, s, 65, iso))
+    for shape in PATCH_SHAPES:
+        # on the wall x = 0 behind the column
+        gauges.append(PressurePatch((0.0, h, h), 0, spread((0.6 - h, 1.0 - 2 * h), shape), shape, iso_wall))
+        # on the floor under the column
+        gauges.append(PressurePatch((0.01, 0.0, h), 1, spread((0.08, 1.0 - 2 * h), shape), shape, iso_wall))
+        # through the column, straddling its free surface at y = 0.75
+        gauges.append(PressurePatch((0.05, 0.6, 0.05), 0, spread((0.3, 0.9), shape), shape, iso))
+    gauges.append(SectionGauge((0.1 + h, 0.0, 0.0), 0, (0.8 / 31, 1.0 / 31), (32, 32), iso))
+    gauges.append(PressurePatch((0.7, 0.0, 0.0), 0, spread((0.8, 1.0), (32, 32)), (32, 32), iso))     # in the empty half
+    gauges.append(PointGauge(tuple(float(c) for c in on)))
+    gauges.append(PointGauge((0.05, 0.3, 0.5)))
+    field = tuple(i for i, g in enumerate(gauges) if isinstance(g, (ColumnGauge, SectionGauge, PointGauge)))
+    return p, pos, vel, mass, iso, tuple(gauges), field
+
+
+def emu(gauges):
+    return [G.of(g) for g in gauges]
+
+
+def check_classes(total):
+    """The run is not vacuous: every class of reading occurred."""
+    info = P.Info(*[int(v) for v in total])
+    assert min(info) > 0, info
+
+
+def cpu_figures():
+    """scene() stepped by the oracle's FULL step, the restatement (with its own particle densities) reading the
+    gauges in each of the STEPS + 1 states: the classes summed, every one of them present."""
+    from oracle.oracle import Oracle, build
+    build(ref=False)
+    orc = Oracle()
+    p, pos, vel, mass, iso, gauges, field = scene()
+    op = to_oracle_params(p)
+    eg = emu(gauges)
+    pos, vel = pos.copy(), vel.copy()
+    total = np.zeros(len(P.Info._fields), np.int64)
+    for k in range(STEPS + 1):
+        total += np.array(P.evaluate(p, pos, vel, mass, eg, with_info=True)[1])
+        if k < STEPS:
+            orc.step(op, pos, vel, mass, mode="full")
+    check_classes(total)
+    return tuple(int(v) for v in total)
+
+
+def mode_of(S, name):
+    return {"full": S.MODE_FULL, "fast": S.MODE_FULL_FAST}[name]
+
+
+def particles(sph):
+    part = sph.getParticles()
+    return part.mPosition.copy(), part.mVelocity.copy()
+
+
+def row_of(rec, r):
+    return G.Readings(rec.v[r], rec.n[r], rec.k[r])
+
+
+def fresh(S, mode="full", gauges="all"):
+    p, pos, vel, mass, _, every, field = scene()
+    sph = S.SPH(mass.size, p, mode=mode_of(S, mode))
+    sph.setParticles(pos, vel, mass)
+    if gauges == "all":
+        sph.setGauges(every)
+    elif gauges == "field":
+        sph.setGauges([every[i] for i in field])
+    return sph
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def full_state(sph):
+    part = sph.getParticles()
+    return [part.mPosition.copy(), part.mVelocity.copy(), part.mDensity.copy(), part.mAcceleration.copy(),
+            part.mNeighborCount.copy()], sph.energy()
+
+
+def sample_probes():
+    """4 096 particle positions, 64 points in the empty half, 8 outside the box or at +-3e38"""
+    p, pos, vel, mass, iso, gauges, field = scene()
+    x = pos.reshape(-1, 3)
+    rng = np.random.default_rng(23)
+    far = np.array([(-0.001, 0.3, 0.5), (0.05, -0.001, 0.5), (0.05, 0.3, 1.001), (1.5, 1.5, 1.5), (3e38, 0.3, 0.5),
+                    (0.05, -3e38, 0.5), (3e38, 3e38, 3e38), (-3e38, -3e38, -3e38)], F32)
+    return np.concatenate([x[rng.choice(len(x), 4096, replace=False)],
+                           (np.array([0.5, 0.1, 0.1], F32) + rng.random((64, 3)) * np.array([0.4, 0.8, 0.8])).astype(F32), far])
+
+
+# ---- the samplers ------------------------------------------------------------------------------------------------
+def test_point_sampler_equals_the_restatement_in_both_modes(hiplib):
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, iso, gauges, field = scene()
+    probes = sample_probes()
+    want = P.sample(p, pos, vel, mass, probes)
+    # (the three probes just outside the box are within h of the fluid: the sampler's clamped cells find it)
+    assert (want[2][:4096] > 0).all() and not want[2][4096:4160].any() and want[2][4160:4163].all() and not want[2][4163:].any()
+    assert (want[0] > 0).any() and (want[0] < 0).any()
+    for a in want:
+        assert not a[4096:4160].any() and not a[4163:].any()
+    got = {}
+    for mode in ("full", "fast"):
+        with fresh(S, mode, gauges=None) as sph:
+            got[mode] = sph.samplePressure(probes)
+            for a, b in zip(got[mode], want):
+                assert same_bits(a, b), mode
+            # a few steps on, against the restatement on the state downloaded
+            sph.run(3)
+            gpos, gvel = particles(sph)
+            later = sph.samplePressure(probes)
+            for a, b in zip(later, P.sample(p, gpos, gvel, mass, probes)):
+                assert same_bits(a, b), mode
+            # any output may be NULL
+            only = np.zeros(len(probes), F32)
+            sph.call("sph_hip_sample_pressure_points", len(probes), probes.ctypes.data, only.ctypes.data, None, None)
+            assert same_bits(only, later[0])
+            sph.call("sph_hip_sample_pressure_points", len(probes), probes.ctypes.data, None, None, None)
+    for a, b in zip(got["full"], got["fast"]):
+        assert same_bits(a, b)
+
+
+def test_lattice_sampler_equals_the_restatement_and_the_point_call(hiplib):
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, iso, gauges, field = scene()
+    s = float(F32(0.5) * F32(p.h))
+    origin, shape = (0.1 - 16 * s, 0.75 - 8 * s, 0.4), (33, 17, 9)      # over the column's free corner
+    pts = SE.lattice_points(origin, (s, s, s), shape).reshape(-1, 3)
+    with fresh(S, "fast", gauges=None) as sph:
+        sph.run(2)
+        gpos, gvel = particles(sph)
+        prs, rho, cnt = sph.samplePressureLattice(origin, (s, s, s), shape)
+        assert prs.shape == rho.shape == cnt.shape == (9, 17, 33)
+        want = P.sample(p, gpos, gvel, mass, pts)
+        assert (want[2] > 0).any() and (want[2] == 0).any() and (want[0] < 0).any() and (want[0] > 0).any()
+        for a, b, c in zip((prs, rho, cnt), want, sph.samplePressure(pts)):
+            assert same_bits(a.reshape(-1), b) and same_bits(a.reshape(-1), c)
+        # the densities and counts are the sampler's
+        frho, _, fcnt = sph.sampleLattice(origin, (s, s, s), shape, velocity=False)
+        assert same_bits(frho, rho) and same_bits(fcnt, cnt)
+
+
+@pytest.mark.parametrize("mode", ["full", "fast"])
+def test_a_call_leaves_the_simulation_alone(hiplib, mode):
+    import smoothed_particle_hydrodynamics_amd as S
+    probes = sample_probes()[:512]
+    out = []
+    for with_calls in (False, True):
+        with fresh(S, mode) as sph:
+            sph.run(5)
+            if with_calls:
+                before = full_state(sph)[0], sph.neighborStats()
+                sph.samplePressure(probes)
+                sph.readGauges()
+                sph.samplePressureLattice((0.0, 0.6, 0.4), (0.01, 0.01, 0.01), (12, 20, 6))
+                sph.syncParticles()
+                after = full_state(sph)[0], sph.neighborStats()
+                for a, b in zip(before[0], after[0]):
+                    assert same_bits(a, b)
+                assert before[1] == after[1]
+            sph.run(20)
+            out.append(full_state(sph))
+    for a, b in zip(out[0][0], out[1][0]):
+        assert same_bits(a, b)
+    assert out[0][1] == out[1][1]
+
+
+# ---- per-step pin, and the figures -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["full", "fast"])
+def test_every_row_equals_the_restatement(hiplib, mode):
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, iso, gauges, field = scene()
+    eg = emu(gauges)
+    with fresh(S, mode) as sph:
+        assert [type(g) for g in sph.getGauges()] == [type(g) for g in gauges]
+        sph.recordGauges(STEPS + 1)
+        want, total = [], np.zeros(len(P.Info._fields), np.int64)
+        gpos, gvel = particles(sph)
+        for k in range(STEPS):
+            sph.step()
+            part = sph.getParticles()
+            # the density this step's pass formed for the state it started from: pinned to the oracle by the
+            # existing suite, it may serve for the rows between; the first and the last row use the restatement's
+            density = None if k in (0, STEPS - 1) else part.mDensity.copy()
+            out, info = P.evaluate(p, gpos, gvel, mass, eg, density=density, with_info=True)
+            want.append(out)
+            total += np.array(info)
+            gpos, gvel = part.mPosition.copy(), part.mVelocity.copy()
+        rec = sph.getGaugeRecord()
+        assert rec.steps.tolist() == list(range(STEPS)) and rec.v.shape == (STEPS, len(gauges), 4)
+        for r in range(STEPS):
+            assert G.same_readings(row_of(rec, r), want[r]), "row %d" % r
+        # the stand-alone route (k_particle_density) in the final state, by the rule of the rows
+        out, info = P.evaluate(p, gpos, gvel, mass, eg, with_info=True)
+        total += np.array(info)
+        now = sph.readGauges()
+        assert G.same_readings(now, out)
+        assert now.kinds == tuple(g.kind for g in eg) and rec.kinds == now.kinds
+        assert same_bits(rec.pressure(0), rec.v[:, 0, 0]) and same_bits(rec.pressure(19), rec.v[:, 19, 2])
+        assert same_bits(rec.force(19), rec.v[:, 19, 0])
+    print("pressure classes %r (CPU %r)" % (P.Info(*[int(v) for v in total]), CPU_FIGURES))
+    check_classes(total)
+    if mode == "full":
+        assert tuple(int(v) for v in total) == CPU_FIGURES
+
+
+def test_pressure_points_equal_the_sampler_and_field_gauges_read_what_they_read(hiplib):
+    import smoothed_particle_hydrodynamics_amd as S
+    from smoothed_particle_hydrodynamics_amd.gauges import PressureGauge
+    p, pos, vel, mass, iso, gauges, field = scene()
+    points = [i for i, g in enumerate(gauges) if isinstance(g, PressureGauge)]
+    pts = np.array([gauges[i].point for i in points], F32)
+    with fresh(S, "fast") as both, fresh(S, "fast", gauges="field") as alone:
+        both.recordGauges(12)
+        alone.recordGauges(12)
+        for k in range(3):
+            got = both.readGauges()
+            prs, rho, cnt = both.samplePressure(pts)
+            assert same_bits(got.v[points, 0], prs) and same_bits(got.v[points, 1], rho) and np.array_equal(got.n[points], cnt)
+            assert not got.v[points, 3].any() and not got.k[points].any()
+            both.run(4)
+            alone.run(4)
+        a, b = both.getGaugeRecord(), alone.getGaugeRecord()
+        assert a.steps.tolist() == b.steps.tolist() == list(range(12))
+        f = list(field)
+        assert same_bits(a.v[:, f], b.v) and same_bits(a.n[:, f], b.n) and same_bits(a.k[:, f], b.k) and b.n.any()
+        assert same_bits(both.readGauges().v[f], alone.readGauges().v)
+
+
+# ---- routes ------------------------------------------------------------------------------------------------------------
+def record_of(S, mode, route):
+    with fresh(S, mode) as sph:
+        sph.recordGauges(STEPS)
+        if route == "run":
+            sph.run(STEPS)
+        for _ in range(STEPS if route != "run" else 0):
+            if route == "step":
+                sph.step()
+            else:
+                sph.voxelizeParticles()
+                sph.findNeighbors()
+                sph.computeDensity()
+                sph.computeAcceleration()
+                sph.integrate()
+        return sph.getGaugeRecord(), sph.readGauges()
+
+
+@pytest.mark.parametrize("mode", ["full", "fast"])
+def test_every_route_gives_the_same_record(hiplib, mode, monkeypatch):
+    import smoothed_particle_hydrodynamics_amd as S
+    for k in ("SPH_HIP_UNTILED", "SPH_HIP_TILE_CAP", "SPH_HIP_LIST_CAP"):
+        monkeypatch.delenv(k, raising=False)
+    first, first_now = record_of(S, mode, "run")
+    assert first.steps.tolist() == list(range(STEPS)) and first.n.any()
+    others = [record_of(S, mode, "step"), record_of(S, mode, "phases")]
+    monkeypatch.setenv("SPH_HIP_UNTILED", "1")
+    others.append(record_of(S, mode, "run"))
+    monkeypatch.delenv("SPH_HIP_UNTILED")
+    monkeypatch.setenv("SPH_HIP_TILE_CAP", "512")        # every workgroup of this scene gives up its tile
+    others.append(record_of(S, mode, "run"))
+    for rec, now in others:
+        assert np.array_equal(rec.steps, first.steps) and G.same_readings(rec, first) and G.same_readings(now, first_now)
+
+
+# ---- no effect on the particles ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["full", "fast"])
+def test_pressure_gauges_and_a_recording_change_no_particle(hiplib, mode):
+    import smoothed_particle_hydrodynamics_amd as S
+    out = []
+    for with_gauges in (False, True):
+        with fresh(S, mode, gauges="all" if with_gauges else None) as sph:
+            if with_gauges:
+                sph.recordGauges(60)
+            sph.run(25)
+            if with_gauges:
+                sph.readGauges()
+            sph.run(25)
+            if with_gauges:
+                assert len(sph.getGaugeRecord().steps) == 50
+            out.append(full_state(sph))
+    for a, b in zip(out[0][0], out[1][0]):
+        assert same_bits(a, b)
+    assert out[0][1] == out[1][1]
+
+
+# ---- constants and the recording's arithmetic ------------------------------------------------------------------------
+def test_new_constants_and_rows_every_third_step(hiplib):
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, iso, gauges, field = scene()
+    eg = emu(gauges)
+    with fresh(S, "full") as sph:
+        sph.recordGauges(10, 3)
+        seen = {}
+        for s in range(STEPS):
+            if s == 12:
+                q = sph.getParams()
+                q.rho0 = float(F32(0.5) * F32(p.rho0))
+                q.stiffness = float(F32(3.0) * F32(p.stiffness))
+                sph._params = q.copy()
+                sph._push()
+            if s % 3 == 0:
+                gpos, gvel = particles(sph)
+                seen[s] = P.evaluate(sph.getParams(), gpos, gvel, mass, eg)
+                if s in (9, 15):
+                    assert G.same_readings(sph.readGauges(), seen[s])
+            sph.step()
+        rec = sph.getGaugeRecord()
+        assert rec.steps.tolist() == list(range(0, 28, 3)) and rec.v.shape == (10, len(gauges), 4)
+        for r, s in enumerate(rec.steps):
+            assert G.same_readings(row_of(rec, r), seen[int(s)]), "row %d" % r
+        # the later rows follow the new constants: the same state read with the old ones differs
+        old = P.evaluate(p, *particles(sph), mass, eg)
+        assert not G.same_readings(sph.readGauges(), old)
+
+
+# ---- refusals and empty contexts -----------------------------------------------------------------------------------------
+def test_refusals_keep_the_old_set(hiplib):
+    import smoothed_particle_hydrodynamics_amd as S
+    from smoothed_particle_hydrodynamics_amd import SphHipError, scenes
+    from smoothed_particle_hydrodynamics_amd import gauges as PG
+    from smoothed_particle_hydrodynamics_amd.slab import HipSlab
+    p, pos, vel, mass, iso, gauges, field = scene()
+    pt, pa = gauges[0], gauges[19]
+    assert isinstance(pt, PG.PressureGauge) and isinstance(pa, PG.PressurePatch)
+    nan, inf = float("nan"), float("inf")
+    bad = [(pa._replace(axis=3), "axis"), (pt._replace(point=(inf, 0.0, 0.0)), "not finite"),
+           (pa._replace(corner=(0.0, nan, 0.0)), "not finite"), (pa._replace(spacing=(0.01, -inf)), "not finite"),
+           (pa._replace(iso=nan), "not finite"), (pa._replace(spacing=(0.01, -0.01)), "spacing"),
+           (pa._replace(shape=(4, 0)), "count"), (pa._replace(shape=(64, 65)), "probes"),
+           (pa._replace(iso=0.0), "pressure patch's iso"), (pa._replace(iso=-1.0), "pressure patch's iso")]
+    for kind in (3, -1, 6):
+        unknown = pt.to_struct()
+        unknown.kind = kind
+        bad.append((unknown, "unknown gauge kind"))
+    unused = pt.to_struct()               # an unused field that is not finite
+    unused.spacing[1] = nan
+    bad.append((unused, "not finite"))
+    with fresh(S, "full") as sph:
+        sph.recordGauges(40)
+        sph.run(3)
+        kept = sph.getGauges()
+        assert [type(g) for g in kept] == [type(g) for g in gauges]
+        for g, why in bad:
+            with pytest.raises(SphHipError, match=why):
+                sph.setGauges(list(gauges[:3]) + [g])
+            assert sph.getGauges() == kept
+        sph.run(2)
+        rec = sph.getGaugeRecord()
+        assert rec.steps.tolist() == [0, 1, 2, 3, 4] and rec.v.shape[1] == len(gauges)
+        for call, args in (("sph_hip_sample_pressure_points", (-1, None, None, None, None)),
+                           ("sph_hip_sample_pressure_points", (4, None, None, None, None))):
+            with pytest.raises(SphHipError, match="negative count or null"):
+                sph.call(call, *args)
+        for shape, spacing in (((0, 4, 4), (0.1, 0.1, 0.1)), ((4, 4, 4), (0.1, 0.0, 0.1)), ((4, 4, 4), (0.1, nan, 0.1))):
+            with pytest.raises(SphHipError):
+                sph.samplePressureLattice((0.0, 0.0, 0.0), spacing, shape)
+        assert sph.samplePressure(np.zeros((0, 3), F32))[0].shape == (0,)
+    q, rpos, rvel, rmass = scenes.dense_block(2000)
+    with S.SPH(rmass.size, q, mode=S.MODE_REF) as ref:
+        ref.setParticles(rpos, rvel, rmass)
+        with pytest.raises(SphHipError, match="FULL"):
+            ref.setGauges([pt, pa])
+        assert ref.getGauges() == []
+        with pytest.raises(SphHipError, match="FULL"):
+            ref.samplePressure(rpos.reshape(-1, 3)[:4])
+        with pytest.raises(SphHipError, match="FULL"):
+            ref.samplePressureLattice((1.0, 1.0, 1.0), (0.1, 0.1, 0.1), (2, 2, 2))
+    with HipSlab(p, 0, p.full_cells_z // 2, 20000, 1024, has_left=False) as slab:
+        arr, n = PG.as_array([pt, pa])
+        with pytest.raises(SphHipError, match="slab"):
+            slab.call("sph_hip_set_gauges", arr, n)
+        probe = np.zeros(3, F32)
+        with pytest.raises(SphHipError, match="slab"):
+            slab.call("sph_hip_sample_pressure_points", 1, probe.ctypes.data, None, None, None)
+
+
+def test_an_empty_context_reads_zeros(hiplib):
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, iso, gauges, field = scene()
+    eg = emu(gauges)
+    want = P.evaluate(p, pos[:0], vel[:0], mass[:0], eg)
+    pres = [i for i, g in enumerate(eg) if P.is_pressure(g)]
+    assert not want.n[pres].any() and not want.v[pres].any() and not want.k[pres].any()
+    probes = sample_probes()[:100]
+    with S.SPH(mass.size, p, mode=S.MODE_FULL) as sph:
+        sph.setGauges(gauges)
+        sph.recordGauges(3)
+        assert G.same_readings(sph.readGauges(), want)
+        assert not any(a.any() for a in sph.samplePressure(probes))
+        assert not any(a.any() for a in sph.samplePressureLattice((0.0, 0.0, 0.0), (0.1, 0.1, 0.1), (3, 4, 5)))
+        sph.run(3)
+        rec = sph.getGaugeRecord()
+        assert rec.steps.tolist() == [0, 1, 2]
+        for r in range(3):
+            assert G.same_readings(row_of(rec, r), want)
+        # after particles were resident and are gone again, the same
+        sph.setParticles(pos, vel, mass)
+        sph.step()
+        assert sph.readGauges().n[pres].any() and sph.samplePressure(probes)[2].any()
+        sph.setParticles(pos[:0], vel[:0], mass[:0])
+        assert G.same_readings(sph.readGauges(), want)
+        assert not any(a.any() for a in sph.samplePressure(probes))
+
+
+if __name__ == "__main__":
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    print(dict(zip(P.Info._fields, cpu_figures())))
