@@ -598,6 +598,68 @@ int sph_hip_set_obstacle_motion(sph_hip_context* ctx, const sph_hip_obstacle_mot
 int sph_hip_get_obstacle_motion(sph_hip_context* ctx, sph_hip_obstacle_motion* out, int capacity, float* clock);
 int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int capacity);
 
+/* ---- motion paths -------------------------------------------------------------------------- *
+ *
+ * Wavemakers, lifted gates, sloshing walls, paddles driven by a measured record: obstacle i of the list
+ * follows path i, a piecewise linear displacement given by keys (t, d) on the motion clock.  The fluid
+ * does not act back on it.  The operation-by-operation contract is in csrc/obstacle_policy.h (fourth
+ * part), all of it fp32, unfused, in the order written:
+ *   ownership  path i belongs to obstacle i; count == 0: no path, the entry takes exactly the turn it
+ *              takes without this call (static, or its motion's).  Otherwise its keys are
+ *              keys[first .. first + count), t[0] == 0 and t strictly increasing.
+ *   path time  T = t[count-1]; u = tau - start, u < 0 becomes 0.  cycle == 0: u > T becomes T.
+ *              cycle != 0: if u >= T then k = floorf(u / T), u = u - k * T; after that u < 0 becomes 0
+ *              and u >= T becomes 0 (the path repeats with period T).
+ *   segment    j: the largest index in [0, count-2] with t[j] <= u.
+ *   shift      w = (u - t[j]) / (t[j+1] - t[j]); D_c(tau) = d[j][c] + w * (d[j+1][c] - d[j][c]).  The
+ *              obstacle at tau is the list entry shifted by D as a moving obstacle is (a wedge's plane
+ *              offset moves with it).  An entry with a path is always shifted, also by D == 0.
+ *   turn       D0 = D(tau0), D1 = D(tau1) for the step's clock pair; the moving obstacle's response
+ *              with these two shifts: a particle that ends the step inside the obstacle as it stands at
+ *              tau1 gets the static response in the frame that moves with the solid during the step.
+ *              The loads record the turn as they record a moving entry's.
+ *   velocity   (scene renderer) (d[j+1] - d[j]) / (t[j+1] - t[j]) per component of the segment in force
+ *              at the clock; 0 before `start` and after the end of a path that does not cycle.
+ *   clock      the motion clock of the moving obstacles.  A successful sph_hip_set_obstacle_paths sets it
+ *              to 0; it advances with every integrate enqueued while some entry moves or has a path.
+ * The shifts of a step are formed on the device by one single-wave launch in front of the step's
+ * integrate (lane i = obstacle i), from the clock pair it gets by value: queued steps stay queued and
+ * nothing synchronises.  It runs also when the context holds no particle.
+ * sph_hip_set_obstacle_paths: n is the obstacle count, or 0 to clear all paths; `keys` holds the n_keys
+ * keys of all paths, at most SPH_HIP_MAX_PATH_KEYS; ordered on the context's stream like
+ * sph_hip_set_obstacles.  Refused with SPH_HIP_ERR_INVALID, the previous paths and clock kept: an n that
+ * is neither 0 nor the obstacle count; null lists with counts > 0; n_keys outside
+ * [0, SPH_HIP_MAX_PATH_KEYS]; count == 1 or count < 0; a range that leaves [0, n_keys); t[0] != 0; t not
+ * strictly increasing or not finite; a d that is not finite; a start that is not finite or < 0; a
+ * cyclic path whose last d differs from its first in any component; a path on an obstacle whose motion
+ * moves (and sph_hip_set_obstacle_motion then refuses a moving motion on an obstacle with a path); any
+ * path in a list that holds a free body (and sph_hip_set_bodies then refuses a body in a list with
+ * paths); any slab context - paths on slabs are not built -; between sph_hip_slab_step_begin and _end.
+ * A context with paths refuses sph_hip_slab_pack, _unpack and _step_begin.  Rotations are not built.
+ * sph_hip_set_obstacles clears the paths as it clears the motions.
+ * sph_hip_get_obstacle_paths copies up to `capacity` paths and `key_capacity` keys (either array may be
+ * NULL) and returns how many paths are set (0 or the obstacle count).  With `shifts` non-null it
+ * synchronises and copies, for every obstacle of the list, the D0 and D1 the device used in the last
+ * enqueued step (six floats per obstacle; zeros for an entry without a path, and before the first step
+ * after a set).  sph_hip_get_obstacles_now shifts an entry with a path to the current clock on the host,
+ * by the function the device uses.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no
+ * existing prototype changed. */
+#define SPH_HIP_MAX_PATH_KEYS 16384     /* over all paths of a context */
+typedef struct sph_hip_motion_key {     /* field order is ABI: 16 bytes */
+   float t;                         /* on the path's own time: t[0] == 0, strictly increasing */
+   float d[3];                      /* the displacement at t, position units */
+} sph_hip_motion_key;
+typedef struct sph_hip_motion_path {    /* field order is ABI: 16 bytes */
+   int32_t first, count;            /* keys[first .. first + count); count == 0: no path */
+   float start;                     /* the motion clock at which the path begins */
+   int32_t cycle;                   /* != 0: repeat with period t[count-1] */
+} sph_hip_motion_path;
+int sph_hip_set_obstacle_paths(sph_hip_context* ctx, const sph_hip_motion_path* paths, int n,
+                               const sph_hip_motion_key* keys, int n_keys);
+int sph_hip_get_obstacle_paths(sph_hip_context* ctx, sph_hip_motion_path* paths, int capacity,
+                               sph_hip_motion_key* keys, int key_capacity, float* shifts);
+
 /* ---- loads on walls and obstacles --------------------------------------------------------- *
  *
  * The impulse the fluid gives to each domain wall and each obstacle, step by step, summed on the

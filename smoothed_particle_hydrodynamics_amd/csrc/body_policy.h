@@ -106,6 +106,17 @@ inline const char* body_rotation_check(const sph_hip_obstacle_rotation* rot, int
    return nullptr;
 }
 
+// Why paths and bodies do not go together (either list may be empty), or nullptr: a list with a path holds
+// no body, so that k_integrate_bodies never meets a path and the path kernels never a body (one function
+// for both directions).
+inline const char* path_body_check(const sph_hip_motion_path* paths, int n_paths, const sph_hip_body* bodies,
+                                   int n_bodies)
+{
+   if (paths_count(paths, n_paths) > 0 && bodies_count(bodies, n_bodies) > 0)
+      return "paths and free bodies in one obstacle list (paths beside bodies are not built)";
+   return nullptr;
+}
+
 // The quantum rule, both directions.  n_bodies: bodies in force with quantum body_quantum_log2.
 inline const char* body_refuses_recording(int n_bodies, int body_quantum_log2, int rows, int quantum_log2)
 {

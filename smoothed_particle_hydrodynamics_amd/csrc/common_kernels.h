@@ -246,6 +246,31 @@ struct BodyLoadHook : LoadHook {
    }
 };
 
+// The obstacle and load hooks for a list with motion paths (obstacle_policy.h, fourth part): an entry
+// takes the path turn with the two shifts its PathShift holds (written by k_paths_eval earlier on the
+// stream, read wave-uniformly), the turn of its motion (`motion` is null when no motions are set), or the
+// static turn.  Only after() differs.
+struct PathObstacleHook : ObstacleHook {
+   const sph_hip_obstacle_motion* motion;
+   float tau0, tau1;
+   const PathShift* shift;
+   __device__ void after(const float* p, float* v, float* q, float) const
+   {
+      obstacles_respond_path(list, motion, shift, n, p, v, q, dt, damping, tau0, tau1);
+   }
+};
+
+struct PathLoadHook : LoadHook {
+   const sph_hip_obstacle_motion* motion;
+   float tau0, tau1;
+   const PathShift* shift;
+   __device__ void after(const float* p, float* v, float* q, float m) const
+   {
+      load_obstacles_respond_path(list, motion, shift, n, p, v, q, dt, damping, tau0, tau1, m,
+                                  static_cast<const LoadHook&>(*this));
+   }
+};
+
 // The call the tuned kernels make, with the signature they always had (a hook parameter with a
 // default changed the code of k_full_accel_lists: tools/kernel_isa_diff.py).
 template <bool UNIT_SCALE>
@@ -427,6 +452,53 @@ k_integrate_bodies(float4* __restrict__ posm, float4* __restrict__ velp, const f
    const bool live = p < meta[META_OWN_END];
    const BodyLoadHook hook = {{obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live}, motion, tau0, tau1,
                               bodies, state};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
+}
+
+// Motion paths (obstacle_policy.h, fourth part; launch_policy.h: use_path_kernels).  One wave in front of
+// every integrate of a context with paths: lane i forms the shifts of obstacle i at the step's clock pair
+// (path_shift_of_step: two searches of its own keys by value) and stores its own 32 bytes of `shift`.
+// The host has checked every key range against the key list (path_check).
+__global__ void __launch_bounds__(SPH_WAVE)
+k_paths_eval(const sph_hip_motion_path* __restrict__ paths, const sph_hip_motion_key* __restrict__ keys, int n_obst,
+             float tau0, float tau1, PathShift* __restrict__ shift)
+{
+   const int lane = threadIdx.x;
+   if (lane >= n_obst) return;
+   const sph_hip_motion_path P = paths[lane];
+   shift[lane] = path_shift_of_step(P, keys, tau0, tau1);
+}
+
+// k_integrate_obst_moving and k_integrate_loads_moving for a list with paths: `shift` holds one entry per
+// obstacle, `motion` too or is null.
+template <bool UNIT_SCALE, bool HASH>
+__global__ void __launch_bounds__(RED_THREADS)
+k_integrate_obst_path(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
+                      const int32_t* __restrict__ meta, PairConsts k, double* __restrict__ epart, CellGrid g,
+                      uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                      uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                      const sph_hip_obstacle_motion* __restrict__ motion, float tau0, float tau1,
+                      const PathShift* __restrict__ shift)
+{
+   const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   const PathObstacleHook hook = {{obst, n_obst, k.dt, k.damping}, motion, tau0, tau1, shift};
+   integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, p < meta[META_OWN_END], hook);
+}
+
+template <bool UNIT_SCALE, bool HASH>
+__global__ void __launch_bounds__(RED_THREADS)
+k_integrate_loads_path(float4* __restrict__ posm, float4* __restrict__ velp, const float4* __restrict__ acc,
+                       const int32_t* __restrict__ meta, PairConsts k, double* __restrict__ epart, CellGrid g,
+                       uint32_t* __restrict__ key, uint32_t* __restrict__ slot,
+                       uint32_t* __restrict__ cell_count, const sph_hip_obstacle* __restrict__ obst, int n_obst,
+                       unsigned long long* __restrict__ row, int quantum_log2,
+                       const sph_hip_obstacle_motion* __restrict__ motion, float tau0, float tau1,
+                       const PathShift* __restrict__ shift)
+{
+   const int p = meta[META_OWN_BEGIN] + blockIdx.x * blockDim.x + threadIdx.x;
+   const bool live = p < meta[META_OWN_END];
+   const PathLoadHook hook = {{obst, n_obst, k.dt, k.damping, row, load_scale(quantum_log2), live}, motion, tau0, tau1,
+                              shift};
    integrate_block<UNIT_SCALE, HASH>(posm, velp, acc, k, epart, g, key, slot, cell_count, p, live, hook);
 }
 

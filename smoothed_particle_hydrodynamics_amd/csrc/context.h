@@ -11,6 +11,7 @@
 #include <memory>
 #include <new>
 #include <utility>
+#include <vector>
 
 #include "cell_build.h"
 #include "common_kernels.h"
@@ -324,6 +325,23 @@ struct sph_hip_context {
    float motion_tau = 0.0f;
    float step_tau[2] = {0.0f, 0.0f};
    int step_tau_taken = 0;
+
+   // motion paths (sph_hip_set_obstacle_paths): one path per obstacle (n_path_entries = 0 or n_obst),
+   // n_paths of them with keys; paths and keys are staged and copied like the motion list, their buffers
+   // allocated with the context's first set.  path_shift_dev: the shifts k_paths_eval writes in front
+   // of every integrate, single-buffered - the next eval is behind this step's integrate on the stream
+   sph_hip_motion_path paths_host[SPH_HIP_MAX_OBSTACLES];
+   std::vector<sph_hip_motion_key> path_keys_host;
+   int n_path_entries = 0, n_paths = 0;
+   DevBuf<sph_hip_motion_path> paths_dev;
+   PinnedBuf<sph_hip_motion_path> paths_stage;
+   Event ev_paths_copied;
+   int paths_copy_pending = 0;
+   DevBuf<sph_hip_motion_key> path_keys_dev;
+   PinnedBuf<sph_hip_motion_key> path_keys_stage;
+   Event ev_path_keys_copied;
+   int path_keys_copy_pending = 0;
+   DevBuf<PathShift> path_shift_dev;
 
    // load recording (sph_hip_record_loads): loads_rows rows of LOAD_ROW_WORDS int64, the next integrate
    // enqueued fills row loads_next (load_row below)

@@ -635,16 +635,24 @@ void motion_tick(sph_hip_context* ctx, float tau[2])
 // into the next row (an integrate without particles uses its row up too: the rows of the slabs of
 // one run stay in step); while some obstacle moves, their _moving forms with the step's motion clock,
 // which a slab's early pack has already taken (an integrate without particles advances it too); while
-// some obstacle is a free body, k_bodies_advance and k_integrate_bodies (with zero particles the advance alone)
+// some obstacle is a free body, k_bodies_advance and k_integrate_bodies (with zero particles the advance alone);
+// while some obstacle has a motion path, k_paths_eval and the _path forms (with zero particles the eval alone)
 int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
 {
    const int n = ctx->n;
    unsigned long long* load_row = nullptr;
    if (loads_pending(ctx)) load_row = ctx->loads_dev.get() + (size_t)ctx->loads_next++ * LOAD_ROW_WORDS;
    const bool moving = use_moving_kernels(ctx->n_obst, ctx->n_moving);
-   if (moving && !ctx->step_tau_taken) motion_tick(ctx, ctx->step_tau);
+   const bool paths = use_path_kernels(ctx->n_obst, ctx->n_paths);
+   if (path_clock_runs(ctx->n_obst, ctx->n_moving, ctx->n_paths) && !ctx->step_tau_taken) motion_tick(ctx, ctx->step_tau);
    ctx->step_tau_taken = 0;
    const float tau0 = ctx->step_tau[0], tau1 = ctx->step_tau[1];
+   // motion paths: this step's shifts, behind the previous step's integrate on the stream
+   if (paths) {
+      hipLaunchKernelGGL(k_paths_eval, dim3(1), dim3(SPH_WAVE), 0, ctx->stream, ctx->paths_dev, ctx->path_keys_dev,
+                         ctx->n_obst, tau0, tau1, ctx->path_shift_dev);
+      if (n == 0) SPH_TRY(hipGetLastError());
+   }
    // free bodies: the advance from the row the last integrate filled, then an integrate that always
    // records - into the caller's row, or into the internal row the advance has just zeroed
    const bool bodies = use_body_kernels(ctx->n_obst, ctx->n_bodies);
@@ -662,8 +670,19 @@ int launch_integrate(sph_hip_context* ctx, bool with_hash = false)
    if (n == 0) return SPH_HIP_OK;
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const int blocks = div_up(n, RED_THREADS);
+   const sph_hip_obstacle_motion* motion_or_null = ctx->n_motion > 0 ? ctx->motion_dev.get() : nullptr;
    bind_flags([&](auto U, auto H) {
-      if (bodies)
+      if (paths && load_row)
+         hipLaunchKernelGGL((k_integrate_loads_path<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,
+                            load_row, ctx->loads_quantum, motion_or_null, tau0, tau1, ctx->path_shift_dev);
+      else if (paths)
+         hipLaunchKernelGGL((k_integrate_obst_path<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
+                            ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,
+                            motion_or_null, tau0, tau1, ctx->path_shift_dev);
+      else if (bodies)
          hipLaunchKernelGGL((k_integrate_bodies<U.value, H.value>), dim3(blocks), dim3(RED_THREADS), 0, ctx->stream,
                             ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->acc, ctx->meta, k, ctx->epart + 2,
                             ctx->grid, ctx->key, ctx->slot, ctx->cell_count, ctx->obst_dev, ctx->n_obst,

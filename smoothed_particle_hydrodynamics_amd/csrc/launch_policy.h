@@ -300,6 +300,20 @@ inline bool motion_clock_runs(int n_obstacles, int n_moving, int n_rotating)
    return n_obstacles > 0 && (n_moving > 0 || n_rotating > 0);
 }
 
+// Motion paths (obstacle_policy.h, fourth part).  Whether a step's integrate is k_paths_eval followed by
+// k_integrate_obst_path or k_integrate_loads_path: some entry of the path list has a path.  Asked ahead of
+// use_moving_kernels - the path kernels give an entry without a path the turn of its motion - and the
+// eval is launched with zero particles too (the shifts still advance).  Such a list holds no body
+// (body_policy.h: path_body_check).  A context without paths launches what it always launched.
+inline bool use_path_kernels(int n_obstacles, int n_paths) { return n_obstacles > 0 && n_paths > 0; }
+
+// Whether the motion clock advances with a step of a context that may hold paths: some entry moves
+// (use_moving_kernels) or has a path.
+inline bool path_clock_runs(int n_obstacles, int n_moving, int n_paths)
+{
+   return n_obstacles > 0 && (n_moving > 0 || n_paths > 0);
+}
+
 // ---- ports (port_policy.h) ------------------------------------------------------------------
 // Whether a step launches k_ports_apply in front of its cell build: some emitter or sink is set.  Then it
 // runs every step, because after a build meta[META_N_IN] is stale and must be reset to n_live even when

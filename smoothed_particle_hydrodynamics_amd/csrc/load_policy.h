@@ -168,3 +168,20 @@ struct LoadRowAdder {
       }
    }
 };
+
+// obstacles_respond_path (obstacle_policy.h) with rec called at every obstacle's turn: an entry with a path
+// is recorded as a moving entry is - q inside the obstacle as it stands at the end of the step, vb and va
+// the world velocities before and after that turn.
+template <class Rec>
+OBST_HD inline void load_obstacles_respond_path(const sph_hip_obstacle* list, const sph_hip_obstacle_motion* motion,
+                                                const PathShift* shift, int n, const float p[3], float v[3],
+                                                float q[3], float dt, float damping, float tau0, float tau1,
+                                                float m, const Rec& rec)
+{
+   for (int i = 0; i < n; i++) {
+      const float vb[3] = {v[0], v[1], v[2]};
+      const bool in = obstacle_turn_path(list[i], motion ? motion + i : nullptr, shift[i], p, v, q, dt, damping, tau0,
+                                         tau1);
+      rec(6 + i, in, m, vb, v);
+   }
+}

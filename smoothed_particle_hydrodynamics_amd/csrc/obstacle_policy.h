@@ -110,6 +110,24 @@
 //              coincides with the world at the end of the step, with a per-particle displacement: a face
 //              moving at omega * r into fluid at rest leaves it at 2 * omega * r along the normal.
 //   excluded   a posed entry on an obstacle whose motion moves; posed entries and free bodies in one list.
+//
+// Motion paths (include/sph_hip.h: sph_hip_set_obstacle_paths; k_paths_eval, k_integrate_obst_path,
+// k_integrate_loads_path; tests/test_paths_cpu.py against tests/path_emulation.py).  Path i belongs to
+// obstacle i; count == 0: no path, otherwise its keys (t, d[3]) are keys[first .. first + count).
+//   time       T = t[count-1]; u = tau - start; u < 0: u = 0.  cycle == 0: u > T: u = T.  cycle != 0:
+//              if u >= T then k = floorf(u / T), u = u - k * T; after that u < 0: u = 0, u >= T: u = 0.
+//              clamped: the first u was < 0, or cycle == 0 and it was > T.
+//   segment    j: the largest index in [0, count-2] with t[j] <= u (t[0] == 0 <= u always).
+//   shift      w = (u - t[j]) / (t[j+1] - t[j]); D_c(tau) = d[j][c] + w * (d[j+1][c] - d[j][c]): one
+//              function, path_displacement, for the device's k_paths_eval and the host.  The obstacle
+//              at tau is obstacle_shifted(o, D); an entry with a path is always shifted ("+ 0" included).
+//   velocity   (d[j+1][c] - d[j][c]) / (t[j+1] - t[j]) of that segment, 0 while clamped.
+//   turn       D0 = D(tau0), D1 = D(tau1) (PathShift, formed once per obstacle and step), o1 =
+//              obstacle_shifted(o, D1), then obstacle_respond_moved(o1, D0, D1, ...) as it is; the return
+//              value is "q strictly inside o1".  An entry without a path takes exactly the turn it takes
+//              without paths: static, or obstacle_turn with its motion.
+//   excluded   a path on an obstacle whose motion moves; any path in a list that holds a free body
+//              (body_policy.h: path_body_check); slab contexts; rotations stay withdrawn.
 #pragma once
 
 #include <math.h>
@@ -691,4 +709,192 @@ OBST_HD inline void obstacles_respond_posed(const sph_hip_obstacle* list, const 
 {
    for (int i = 0; i < n; i++)
       obstacle_turn_any(list[i], motion ? motion + i : nullptr, rot[i], pose[i], p, v, q, dt, damping, tau0, tau1);
+}
+
+// ---- motion paths (the contract's fourth part) ------------------------------------------------------
+
+OBST_HD inline bool path_is(const sph_hip_motion_path& P) { return P.count != 0; }
+
+// how many entries of a path list have a path
+inline int paths_count(const sph_hip_motion_path* paths, int n)
+{
+   int k = 0;
+   for (int i = 0; i < n; i++) k += path_is(paths[i]) ? 1 : 0;
+   return k;
+}
+
+// Why a path list for `n_obstacles` obstacles is refused, or nullptr.  n = 0 clears all paths.
+inline const char* path_check(const sph_hip_motion_path* paths, int n, const sph_hip_motion_key* keys, int n_keys,
+                              int n_obstacles)
+{
+   if (n != 0 && n != n_obstacles) return "the path count must be 0 or the obstacle count";
+   if (n == 0) return nullptr;
+   if (!paths) return "null path list";
+   if (n_keys < 0 || n_keys > SPH_HIP_MAX_PATH_KEYS) return "the key count must be in [0, 16384]";
+   if (n_keys > 0 && !keys) return "null key list";
+   for (int i = 0; i < n; i++) {
+      const sph_hip_motion_path& P = paths[i];
+      if (P.count < 0) return "a path's key count must be >= 0";
+      if (P.count == 1) return "a path needs at least two keys";
+      if (P.count == 0) continue;
+      if (P.first < 0 || P.first > n_keys || P.count > n_keys - P.first) return "a path's keys leave the key list";
+      if (!isfinite(P.start) || !(P.start >= 0.0f)) return "a path's start must be finite and >= 0";
+      const sph_hip_motion_key* k = keys + P.first;
+      if (k[0].t != 0.0f) return "a path's first key must be at t = 0";
+      for (int j = 0; j < P.count; j++) {
+         if (!isfinite(k[j].t) || (j > 0 && !(k[j].t > k[j - 1].t)))
+            return "a path's key times must be finite and strictly increasing";
+         if (!isfinite(k[j].d[0]) || !isfinite(k[j].d[1]) || !isfinite(k[j].d[2]))
+            return "a path's displacements must be finite";
+      }
+      if (P.cycle != 0)
+         for (int c = 0; c < 3; c++)
+            if (k[P.count - 1].d[c] != k[0].d[c]) return "a cyclic path must end at the displacement it begins with";
+   }
+   return nullptr;
+}
+
+// Why paths and motions do not go together (either list may be empty), or nullptr: one function for
+// both directions.
+inline const char* path_motion_check(const sph_hip_motion_path* paths, int n_paths, const sph_hip_obstacle_motion* motion,
+                                     int n_motion)
+{
+   for (int i = 0; i < n_paths && i < n_motion; i++)
+      if (path_is(paths[i]) && obstacle_moves(motion[i])) return "a path on an obstacle whose motion moves";
+   return nullptr;
+}
+
+// Where tau falls on a path: the segment j (relative to the path's first key), the path time u, and
+// whether u was clamped (before the start, or past the end of a path that does not cycle).
+struct PathSegment {
+   int j;
+   float u;
+   bool clamped;
+};
+
+OBST_HD inline PathSegment path_segment(const sph_hip_motion_path& P, const sph_hip_motion_key* keys, float tau)
+{
+   const sph_hip_motion_key* k = keys + P.first;
+   const float T = k[P.count - 1].t;
+   float u = tau - P.start;
+   bool clamped = false;
+   if (u < 0.0f) {
+      u = 0.0f;
+      clamped = true;
+   }
+   if (P.cycle == 0) {
+      if (u > T) {
+         u = T;
+         clamped = true;
+      }
+   } else {
+      if (u >= T) {
+         const float turns = floorf(u / T);
+         u = u - turns * T;
+      }
+      if (u < 0.0f) u = 0.0f;
+      if (u >= T) u = 0.0f;
+   }
+   int lo = 0, hi = P.count - 2;   // the largest j with t[j] <= u
+   while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (k[mid].t <= u) lo = mid;
+      else hi = mid - 1;
+   }
+   const PathSegment s = {lo, u, clamped};
+   return s;
+}
+
+// D(tau) of a path (path_is(P)): the one function the device's k_paths_eval and the host use.
+OBST_HD inline void path_displacement(const sph_hip_motion_path& P, const sph_hip_motion_key* keys, float tau, float D[3])
+{
+   const PathSegment s = path_segment(P, keys, tau);
+   const sph_hip_motion_key* k = keys + P.first + s.j;
+   const float w = (s.u - k[0].t) / (k[1].t - k[0].t);
+   for (int c = 0; c < 3; c++) D[c] = k[0].d[c] + w * (k[1].d[c] - k[0].d[c]);
+}
+
+// the velocity of the segment in force at tau, 0 while the path time is clamped
+inline void path_velocity(const sph_hip_motion_path& P, const sph_hip_motion_key* keys, float tau, float v[3])
+{
+   const PathSegment s = path_segment(P, keys, tau);
+   const sph_hip_motion_key* k = keys + P.first + s.j;
+   for (int c = 0; c < 3; c++) v[c] = s.clamped ? 0.0f : (k[1].d[c] - k[0].d[c]) / (k[1].t - k[0].t);
+}
+
+// One entry's shifts for a step: 32 bytes, formed once per obstacle and step (k_paths_eval), read
+// wave-uniformly by the integrate.
+struct PathShift {
+   float D0[3], D1[3];
+   int32_t has_path, pad;
+};
+
+OBST_HD inline PathShift path_shift_of_step(const sph_hip_motion_path& P, const sph_hip_motion_key* keys, float tau0,
+                                            float tau1)
+{
+   PathShift s = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0, 0};
+   if (!path_is(P)) return s;
+   path_displacement(P, keys, tau0, s.D0);
+   path_displacement(P, keys, tau1, s.D1);
+   s.has_path = 1;
+   return s;
+}
+
+// k_paths_eval's lane loop, lane i = obstacle i (the host's restatement of the launch)
+inline void paths_eval(const sph_hip_motion_path* paths, const sph_hip_motion_key* keys, int n, float tau0, float tau1,
+                       PathShift* out)
+{
+   for (int i = 0; i < n; i++) out[i] = path_shift_of_step(paths[i], keys, tau0, tau1);
+}
+
+// the obstacle at tau in a list with paths: shifted along its path, otherwise obstacle_at with its motion
+inline sph_hip_obstacle path_obstacle_at(const sph_hip_obstacle& o, const sph_hip_motion_path* P,
+                                         const sph_hip_motion_key* keys, const sph_hip_obstacle_motion* m, float tau)
+{
+   if (!P || !path_is(*P)) return obstacle_at(o, m, tau);
+   float D[3];
+   path_displacement(*P, keys, tau, D);
+   return obstacle_shifted(o, D);
+}
+
+// One entry's turn in a list with paths: the moved response with the shifts of `s` for an entry with a
+// path, otherwise the turn of its motion (`motion` may be null: no motions set) or the static one.
+// Returns whether q was strictly inside the obstacle as it stands at the end of the step.
+OBST_HD inline bool obstacle_turn_path(const sph_hip_obstacle& o, const sph_hip_obstacle_motion* motion,
+                                       const PathShift& s, const float p[3], float v[3], float q[3], float dt,
+                                       float damping, float tau0, float tau1)
+{
+   // (obstacle_turn written out, so that the two shifted turns share one call site and the static ones
+   // another: with a call site each the compiler kept o1 in scratch memory)
+   float D0[3], D1[3];
+   bool shifted = false;
+   if (s.has_path) {
+      for (int c = 0; c < 3; c++) {
+         D0[c] = s.D0[c];
+         D1[c] = s.D1[c];
+      }
+      shifted = true;
+   } else if (motion && obstacle_moves(*motion)) {
+      obstacle_displacement(*motion, tau0, D0);
+      obstacle_displacement(*motion, tau1, D1);
+      shifted = true;
+   }
+   if (shifted) {
+      const sph_hip_obstacle o1 = obstacle_shifted(o, D1);
+      const bool in = obstacle_inside(o1, q);
+      obstacle_respond_moved(o1, D0, D1, p, v, q, dt, damping);
+      return in;
+   }
+   const bool in = obstacle_inside(o, q);
+   obstacle_respond(o, p, v, q, dt, damping);
+   return in;
+}
+
+// Every obstacle of a list with paths, in order, with the shifts of this step (`shift`: one per obstacle).
+OBST_HD inline void obstacles_respond_path(const sph_hip_obstacle* list, const sph_hip_obstacle_motion* motion,
+                                           const PathShift* shift, int n, const float p[3], float v[3], float q[3],
+                                           float dt, float damping, float tau0, float tau1)
+{
+   for (int i = 0; i < n; i++)
+      obstacle_turn_path(list[i], motion ? motion + i : nullptr, shift[i], p, v, q, dt, damping, tau0, tau1);
 }

@@ -29,12 +29,21 @@ int refuse_bodies(sph_hip_context* ctx)
    return SPH_HIP_ERR_INVALID;
 }
 
+// motion paths (obstacle_policy.h, fourth part) are evaluated in front of launch_integrate only, not in
+// front of a slab's early pack: a context that holds some cannot be a slab
+int refuse_paths(sph_hip_context* ctx)
+{
+   ctx->err = "a context with paths (sph_hip_set_obstacle_paths) cannot exchange with neighbouring slabs";
+   return SPH_HIP_ERR_INVALID;
+}
+
 int slab_pack(sph_hip_context* ctx, void* left_device, void* right_device,
                       int capacity_records)
 {
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
+   if (ctx->n_paths > 0) return refuse_paths(ctx);
    if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
    hipStream_t st = ctx->stream;
    ctx->had_exchange = 1;
@@ -57,6 +66,7 @@ int slab_unpack(sph_hip_context* ctx, const void* left_device, const void* right
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
+   if (ctx->n_paths > 0) return refuse_paths(ctx);
    if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
    ctx->had_exchange = 1;
    // (a slab's fused step has hashed its owned entries for the next build, which hashes what is
@@ -77,6 +87,7 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
    int rc;
    if (ctx->mode != SPH_HIP_MODE_FULL || capacity_records < 0) return SPH_HIP_ERR_INVALID;
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
+   if (ctx->n_paths > 0) return refuse_paths(ctx);
    if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
    if (!ctx->use_tiled) {
       ctx->err = "sph_hip_slab_step_begin: needs the tiled kernels (SPH_HIP_UNTILED is set)";

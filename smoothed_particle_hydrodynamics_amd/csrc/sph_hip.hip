@@ -1229,6 +1229,7 @@ int sph_hip_set_obstacles(sph_hip_context* ctx, const sph_hip_obstacle* list, in
    ctx->n_motion = ctx->n_moving = 0;   // a new list stands still
    ctx->motion_tau = 0.0f;
    clear_bodies(ctx);                   // ... and is nobody's body
+   ctx->n_path_entries = ctx->n_paths = 0;   // ... and follows no path
    return SPH_HIP_OK;
 }
 
@@ -1258,6 +1259,8 @@ int sph_hip_set_obstacle_motion(sph_hip_context* ctx, const sph_hip_obstacle_mot
       ctx->err = std::string("sph_hip_set_obstacle_motion: ") + why;
       return SPH_HIP_ERR_INVALID;
    }
+   if (const char* why = path_motion_check(ctx->paths_host, ctx->n_path_entries, list, n))
+      return refuse(ctx, "sph_hip_set_obstacle_motion", why);
    if (ctx->slab_step_open) {
       ctx->err = "sph_hip_set_obstacle_motion: not between sph_hip_slab_step_begin and sph_hip_slab_step_end";
       return SPH_HIP_ERR_INVALID;
@@ -1293,7 +1296,9 @@ namespace {
 int obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int k, BodyState* st)
 {
    for (int i = 0; i < k; i++)
-      out[i] = obstacle_at(ctx->obst_host[i], i < ctx->n_motion ? &ctx->motion_host[i] : nullptr, ctx->motion_tau);
+      out[i] = path_obstacle_at(ctx->obst_host[i], i < ctx->n_path_entries ? &ctx->paths_host[i] : nullptr,
+                                ctx->path_keys_host.data(), i < ctx->n_motion ? &ctx->motion_host[i] : nullptr,
+                                ctx->motion_tau);
    if (ctx->n_bodies > 0 && k > 0) {   // a body stands where the device has moved it to
       BodyState mine[SPH_HIP_MAX_OBSTACLES];
       if (!st) st = mine;
@@ -1319,6 +1324,90 @@ int sph_hip_get_obstacles_now(sph_hip_context* ctx, sph_hip_obstacle* out, int c
    return ctx->n_obst;
 }
 
+// ---- motion paths (obstacle_policy.h, fourth part; routes: launch_policy.h use_path_kernels) ---------
+
+int sph_hip_set_obstacle_paths(sph_hip_context* ctx, const sph_hip_motion_path* paths, int n,
+                               const sph_hip_motion_key* keys, int n_keys)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_obstacle_paths";
+   if (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange || ctx->comm)
+      return refuse(ctx, who, "slab contexts (with neighbours, or that have exchanged) cannot have paths");
+   if (const char* why = path_check(paths, n, keys, n_keys, ctx->n_obst)) return refuse(ctx, who, why);
+   if (const char* why = path_motion_check(paths, n, ctx->motion_host, ctx->n_motion)) return refuse(ctx, who, why);
+   if (const char* why = path_body_check(paths, n, ctx->bodies_host, ctx->n_body_entries)) return refuse(ctx, who, why);
+   if (ctx->slab_step_open) return refuse(ctx, who, "not between sph_hip_slab_step_begin and sph_hip_slab_step_end");
+   if (n > 0) {
+      if (!ctx->path_shift_dev) {   // the first set of this context: the buffers of every later one
+         DevBuf<sph_hip_motion_path> pd;
+         PinnedBuf<sph_hip_motion_path> ps;
+         DevBuf<sph_hip_motion_key> kd;
+         PinnedBuf<sph_hip_motion_key> ks;
+         DevBuf<PathShift> sd;
+         Event ep, ek;
+         if (dev_alloc(pd, SPH_HIP_MAX_OBSTACLES) != hipSuccess || pinned_alloc(ps, SPH_HIP_MAX_OBSTACLES) != hipSuccess ||
+             dev_alloc(kd, SPH_HIP_MAX_PATH_KEYS) != hipSuccess || pinned_alloc(ks, SPH_HIP_MAX_PATH_KEYS) != hipSuccess ||
+             dev_alloc(sd, SPH_HIP_MAX_OBSTACLES) != hipSuccess || event_create(ep) != hipSuccess ||
+             event_create(ek) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->err = std::string(who) + ": cannot allocate the path buffers";
+            return SPH_HIP_ERR_CAPACITY;
+         }
+         ctx->paths_dev = std::move(pd);
+         ctx->paths_stage = std::move(ps);
+         ctx->path_keys_dev = std::move(kd);
+         ctx->path_keys_stage = std::move(ks);
+         ctx->ev_paths_copied = std::move(ep);
+         ctx->ev_path_keys_copied = std::move(ek);
+         ctx->path_shift_dev = std::move(sd);
+      }
+      // steps already queued keep the lists they were enqueued with: the copies go behind them
+      if ((rc = stage_list(ctx, paths, n, ctx->paths_stage, ctx->paths_dev, ctx->ev_paths_copied, ctx->paths_copy_pending)))
+         return rc;
+      if (n_keys > 0 && (rc = stage_list(ctx, keys, n_keys, ctx->path_keys_stage, ctx->path_keys_dev,
+                                         ctx->ev_path_keys_copied, ctx->path_keys_copy_pending)))
+         return rc;
+      SPH_TRY(hipMemsetAsync(ctx->path_shift_dev, 0, sizeof(PathShift) * SPH_HIP_MAX_OBSTACLES, ctx->stream));
+      memcpy(ctx->paths_host, paths, sizeof(sph_hip_motion_path) * (size_t)n);
+      ctx->path_keys_host.assign(keys, keys + n_keys);
+   } else {
+      ctx->path_keys_host.clear();
+   }
+   ctx->n_path_entries = n;   // the steps enqueued from here on take the routes of these paths
+   ctx->n_paths = paths_count(ctx->paths_host, n);
+   ctx->motion_tau = 0.0f;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_obstacle_paths(sph_hip_context* ctx, sph_hip_motion_path* paths, int capacity,
+                               sph_hip_motion_key* keys, int key_capacity, float* shifts)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (capacity < 0 || key_capacity < 0)
+      return refuse(ctx, "sph_hip_get_obstacle_paths", "capacity and key_capacity must be >= 0");
+   const int k = capacity < ctx->n_path_entries ? capacity : ctx->n_path_entries;
+   const int n_keys = (int)ctx->path_keys_host.size();
+   const int kk = key_capacity < n_keys ? key_capacity : n_keys;
+   if (paths && k > 0) memcpy(paths, ctx->paths_host, sizeof(sph_hip_motion_path) * (size_t)k);
+   if (keys && kk > 0) memcpy(keys, ctx->path_keys_host.data(), sizeof(sph_hip_motion_key) * (size_t)kk);
+   if (shifts) {
+      PathShift st[SPH_HIP_MAX_OBSTACLES];
+      memset(st, 0, sizeof(st));
+      if (ctx->n_paths > 0) {
+         SPH_TRY(hipStreamSynchronize(ctx->stream));
+         SPH_TRY(hipMemcpy(st, ctx->path_shift_dev, sizeof(PathShift) * (size_t)ctx->n_obst, hipMemcpyDeviceToHost));
+      }
+      for (int i = 0; i < ctx->n_obst; i++)
+         for (int c = 0; c < 3; c++) {
+            shifts[6 * i + c] = st[i].D0[c];
+            shifts[6 * i + 3 + c] = st[i].D1[c];
+         }
+   }
+   return ctx->n_path_entries;
+}
+
 // ---- free bodies (body_policy.h; routes: launch_policy.h use_body_kernels) --------------------------
 
 int sph_hip_set_bodies(sph_hip_context* ctx, const sph_hip_body* list, int n, int quantum_log2)
@@ -1332,6 +1421,7 @@ int sph_hip_set_bodies(sph_hip_context* ctx, const sph_hip_body* list, int n, in
    if (!why && n_bodies > 0 &&
        (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange || ctx->comm))
       why = "slab contexts (with neighbours, or that have exchanged) cannot hold bodies";
+   if (!why) why = path_body_check(ctx->paths_host, ctx->n_path_entries, list, n);
    if (!why && ctx->slab_step_open) why = "not between sph_hip_slab_step_begin and sph_hip_slab_step_end";
    if (why) {
       ctx->err = std::string("sph_hip_set_bodies: ") + why;
@@ -2208,6 +2298,8 @@ int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const 
       s.o = now[i];
       if (ctx->n_bodies > 0 && body_is(ctx->bodies_host[i]))
          for (int c = 0; c < 3; c++) s.vel[c] = st[i].V[c];
+      else if (i < ctx->n_path_entries && path_is(ctx->paths_host[i]))
+         path_velocity(ctx->paths_host[i], ctx->path_keys_host.data(), ctx->motion_tau, s.vel);
       else if (i < ctx->n_motion)
          scene_motion_velocity(ctx->motion_host[i], ctx->motion_tau, s.vel);
       else

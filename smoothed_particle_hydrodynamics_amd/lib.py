@@ -80,7 +80,8 @@ class SphSceneParams(C.Structure):
 
 
 from . import obstacles as _obstacles  # noqa: E402
-from .obstacles import SphBody, SphBodyState, SphObstacle, SphObstacleMotion  # noqa: E402  (mirrors of the C structs)
+from .obstacles import (SphBody, SphBodyState, SphMotionKey, SphMotionPath, SphObstacle,  # noqa: E402
+                        SphObstacleMotion)  # (mirrors of the C structs)
 from .gauges import GaugeReadings, GaugeRecord, SphGauge  # noqa: E402,F401
 from .ports import PortTotals, SphEmitter, SphSink  # noqa: E402,F401
 
@@ -142,6 +143,9 @@ PROTOTYPES = {
     "sph_hip_set_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int]),
     "sph_hip_get_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int, _P(C.c_float)]),
     "sph_hip_get_obstacles_now": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
+    "sph_hip_set_obstacle_paths": (C.c_int, [_ctx, _P(SphMotionPath), C.c_int, _P(SphMotionKey), C.c_int]),
+    "sph_hip_get_obstacle_paths": (C.c_int, [_ctx, _P(SphMotionPath), C.c_int, _P(SphMotionKey), C.c_int,
+                                             C.c_void_p]),
     "sph_hip_set_bodies": (C.c_int, [_ctx, _P(SphBody), C.c_int, C.c_int]),
     "sph_hip_get_bodies": (C.c_int, [_ctx, _P(SphBody), _P(SphBodyState), C.c_int]),
     "sph_hip_record_loads": (C.c_int, [_ctx, C.c_int, C.c_int]),
@@ -286,6 +290,11 @@ class Loads:
 Bodies = collections.namedtuple("Bodies", ["bodies", "displacement", "velocity", "skipped", "steps"])
 
 
+# sph_hip_get_obstacle_paths' answer: paths [MotionPath or None per obstacle], the motion clock, shifts float32
+# (n_obstacles, 2, 3) - D0 and D1 of the last enqueued step - or None when they were not asked for
+ObstaclePaths = collections.namedtuple("ObstaclePaths", ["paths", "clock", "shifts"])
+
+
 # sph_hip_get_tracers' answer, in the order given to set_tracers: position float32 (n, 3), wet_steps and
 # dry_steps int32 (n,)
 Tracers = collections.namedtuple("Tracers", ["position", "wet_steps", "dry_steps"])
@@ -389,7 +398,7 @@ class Context:
 
     def get_obstacles(self, now=False):
         """The context's obstacles, in list order: as they were set, or (now=True) displaced by their
-        motions to the current motion clock and, free bodies, to where the device has moved them
+        motions and paths to the current motion clock and, free bodies, to where the device has moved them
         (sph_hip_get_obstacles_now)."""
         arr = (SphObstacle * _obstacles.MAX_OBSTACLES)()
         n = self.call("sph_hip_get_obstacles_now" if now else "sph_hip_get_obstacles", arr, _obstacles.MAX_OBSTACLES)
@@ -408,6 +417,30 @@ class Context:
         clock = C.c_float()
         n = self.call("sph_hip_get_obstacle_motion", arr, _obstacles.MAX_OBSTACLES, C.byref(clock))
         return [_obstacles.motion_from_struct(arr[i]) for i in range(n)], clock.value
+
+    def set_obstacle_paths(self, paths):
+        """Drive the obstacles along keyframed displacements (sph_hip_set_obstacle_paths): one
+        obstacles.MotionPath per obstacle, None for one without a path; an empty list clears all paths.
+        Sets the motion clock to 0; steps already queued keep the paths and the clock they were enqueued
+        with.  Single contexts only, and not beside free bodies."""
+        arr, n, keys, n_keys = _obstacles.as_path_arrays(paths)
+        self.call("sph_hip_set_obstacle_paths", arr, n, keys, n_keys)
+
+    def get_obstacle_paths(self, shifts=True):
+        """ObstaclePaths(paths, clock, shifts): [MotionPath or None per obstacle] - empty when no paths are
+        set -, the motion clock, and (shifts=True; synchronises) float32 (n_obstacles, 2, 3): the shifts D0
+        and D1 the device used for each obstacle in the last enqueued step, zeros without a path."""
+        import numpy as np
+        arr = (SphMotionPath * _obstacles.MAX_OBSTACLES)()
+        keys = (SphMotionKey * _obstacles.MAX_PATH_KEYS)()
+        out = np.zeros((_obstacles.MAX_OBSTACLES, 2, 3), np.float32)
+        n = self.call("sph_hip_get_obstacle_paths", arr, _obstacles.MAX_OBSTACLES, keys, _obstacles.MAX_PATH_KEYS,
+                      _ptr(out) if shifts else None)
+        clock = C.c_float()
+        self.call("sph_hip_get_obstacle_motion", None, 0, C.byref(clock))
+        n_obst = self.call("sph_hip_get_obstacles", None, 0)
+        return ObstaclePaths(_obstacles.paths_from_arrays(arr, n, keys), clock.value,
+                             out[:n_obst].copy() if shifts else None)
 
     def record_loads(self, steps, quantum_log2=LOAD_QUANTUM_LOG2):
         """Record the impulse the next `steps` steps give to every wall and obstacle

@@ -5,7 +5,8 @@ a context's particles collide with; `as_struct()` gives the C ABI's sph_hip_obst
 `signed_distance(points)` the numpy distance to the surface (negative inside), for placing obstacles
 and checking results.  `Motion` is the constant velocity an
 obstacle is driven at between two readings of the context's motion clock
-(sph_hip_set_obstacle_motion); `Body` makes it a free body that the fluid's own loads move
+(sph_hip_set_obstacle_motion); `MotionPath` is a keyframed displacement it follows instead
+(sph_hip_set_obstacle_paths); `Body` makes it a free body that the fluid's own loads move
 (sph_hip_set_bodies).  The collision response itself is csrc/obstacle_policy.h and runs on the GPU.
 `Rotation` tilts an obstacle, or turns it at a constant angular rate, about a coordinate axis through a
 pivot: the contract (csrc/obstacle_policy.h, third part), scene building and carving only - no context
@@ -254,6 +255,142 @@ def as_motion_array(motions):
             m = Motion((0.0, 0.0, 0.0))
         arr[i] = m if isinstance(m, SphObstacleMotion) else m.as_struct()
     return arr, len(motions)
+
+
+MAX_PATH_KEYS = 16384             # SPH_HIP_MAX_PATH_KEYS
+
+
+class SphMotionKey(C.Structure):
+    """Mirror of sph_hip_motion_key (include/sph_hip.h): 16 bytes, field order is ABI."""
+
+    _fields_ = [("t", C.c_float), ("d", C.c_float * 3)]
+
+
+class SphMotionPath(C.Structure):
+    """Mirror of sph_hip_motion_path (include/sph_hip.h): 16 bytes, field order is ABI."""
+
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("start", C.c_float), ("cycle", C.c_int32)]
+
+
+class MotionPath:
+    """An obstacle following a keyframed displacement (sph_hip_set_obstacle_paths): `displacements`[k]
+    (position units) at `times`[k] after the motion clock reaches `start`, linear in between, held
+    before and after - or, with `cycle`, repeated with period times[-1].  times[0] is 0, times rise
+    strictly, at least two keys; a cyclic path ends at the displacement it begins with."""
+
+    def __init__(self, times, displacements, start=0.0, cycle=False):
+        self.times = np.array(times, np.float32).reshape(-1)
+        self.displacements = np.array(displacements, np.float32).reshape(-1, 3)
+        if self.times.size != self.displacements.shape[0]:
+            raise ValueError("one displacement per time")
+        self.start, self.cycle = np.float32(start), bool(cycle)
+
+    @classmethod
+    def sine(cls, amplitude_xyz, period, keys=64, start=0.0):
+        """One period of amplitude * sin(2 pi t / period), cyclic: `keys` segments of equal length, the
+        closing key a bitwise copy of the first.  Between keys the path is linear, so it stays within
+        amplitude * (2 pi / keys)**2 / 8 of the sine."""
+        keys = int(keys)
+        if keys < 2:
+            raise ValueError("keys must be at least 2")
+        amp = np.asarray(amplitude_xyz, np.float64).reshape(3)
+        phase = np.arange(keys + 1, dtype=np.float64) / keys
+        times = (phase * float(period)).astype(np.float32)
+        disp = (np.sin(2.0 * math.pi * phase)[:, None] * amp[None, :]).astype(np.float32)
+        times[0] = 0.0
+        disp[-1] = disp[0]
+        return cls(times, disp, start, True)
+
+    @classmethod
+    def stroke(cls, displacement_xyz, duration, start=0.0):
+        """Two keys: from rest to `displacement_xyz` in `duration`, and held there."""
+        return cls([0.0, duration], [(0.0, 0.0, 0.0), tuple(displacement_xyz)], start, False)
+
+    def segment(self, clock):
+        """(j, u, clamped): the segment in force at motion clock `clock`, the path time, and whether
+        that time was clamped - the contract's fp32 arithmetic (csrc/obstacle_policy.h: path_segment)."""
+        f = np.float32
+        t = self.times
+        T = t[-1]
+        with np.errstate(all="ignore"):
+            u = f(f(clock) - self.start)
+            clamped = bool(u < 0)
+            if u < 0:
+                u = f(0)
+            if not self.cycle:
+                if u > T:
+                    u, clamped = T, True
+            else:
+                if u >= T:
+                    k = f(np.floor(f(u / T)))
+                    u = f(u - f(k * T))
+                if u < 0:
+                    u = f(0)
+                if u >= T:
+                    u = f(0)
+        j = int(np.searchsorted(t, u, side="right")) - 1
+        return min(max(j, 0), t.size - 2), f(u), clamped
+
+    def displacement_at(self, clock):
+        """The shift at motion clock `clock`, float32[3], in the C ABI's fp32 arithmetic."""
+        f = np.float32
+        j, u, _ = self.segment(clock)
+        t, d = self.times, self.displacements
+        with np.errstate(all="ignore"):
+            w = f(f(u - t[j]) / f(t[j + 1] - t[j]))
+            return (d[j] + (w * (d[j + 1] - d[j]).astype(f)).astype(f)).astype(f)
+
+    def velocity_at(self, clock):
+        """The velocity of the segment in force at `clock`, float32[3]; 0 while the path time is clamped."""
+        f = np.float32
+        j, _, clamped = self.segment(clock)
+        if clamped:
+            return np.zeros(3, f)
+        t, d = self.times, self.displacements
+        with np.errstate(all="ignore"):
+            return ((d[j + 1] - d[j]).astype(f) / f(t[j + 1] - t[j])).astype(f)
+
+    def __eq__(self, other):
+        return (isinstance(other, MotionPath) and self.times.tobytes() == other.times.tobytes() and
+                self.displacements.tobytes() == other.displacements.tobytes() and
+                self.start.tobytes() == other.start.tobytes() and self.cycle == other.cycle)
+
+    def __repr__(self):
+        return "MotionPath(%d keys to t = %g, start %g%s)" % (self.times.size, self.times[-1], self.start,
+                                                              ", cyclic" if self.cycle else "")
+
+
+def as_path_arrays(paths):
+    """(ctypes array of sph_hip_motion_path, n, ctypes array of sph_hip_motion_key, n_keys) for a list of
+    MotionPath or None (no path): the keys of all paths one after the other."""
+    paths = list(paths)
+    n_keys = sum(p.times.size for p in paths if p is not None)
+    arr = (SphMotionPath * max(1, len(paths)))()
+    keys = np.zeros((max(1, n_keys), 4), np.float32)
+    first = 0
+    for i, p in enumerate(paths):
+        if p is None:
+            continue
+        k = p.times.size
+        arr[i].first, arr[i].count, arr[i].start, arr[i].cycle = first, k, float(p.start), int(p.cycle)
+        keys[first:first + k, 0] = p.times
+        keys[first:first + k, 1:] = p.displacements
+        first += k
+    karr = (SphMotionKey * max(1, n_keys)).from_buffer_copy(keys.tobytes())
+    return arr, len(paths), karr, n_keys
+
+
+def paths_from_arrays(arr, n, karr):
+    """The list of MotionPath / None that n sph_hip_motion_path structs over the keys `karr` describe."""
+    out = []
+    for i in range(n):
+        s = arr[i]
+        if s.count == 0:
+            out.append(None)
+            continue
+        ks = [karr[s.first + j] for j in range(s.count)]
+        out.append(MotionPath([k.t for k in ks], [list(k.d) for k in ks], s.start, s.cycle != 0))
+    return out
 
 
 class SphObstacleRotation(C.Structure):

@@ -251,6 +251,50 @@ def dam_break_beach(n, slope_deg=20.0, length=0.6, gap=0.25, surge=0.7, box=(1.0
     return p, pos, vel, mass, [beach]
 
 
+def wave_flume(n, stroke=0.06, period=0.4, slope_deg=15.0, box=(2.0, 0.5, 0.25), depth=0.5, gauges=4, keys=64,
+               neighbors=32.0, seed=42, gravity=-9.81):
+    """Still water in a long tank (gravity along -y, the walls on) filled to `depth` of its height, with a
+    piston wavemaker at the upstream end and a beach at the far one.  The piston is a Box two kernel radii
+    thick across the whole tank along z, from below the floor to above the tank, on a MotionPath.sine along x:
+    amplitude stroke / 2, `period` on the motion clock, `keys` segments per period; its back face stays half a
+    stroke inside the upstream wall at its rearmost.  The water starts at the piston's front face.  The beach is
+    a Wedge.ramp standing on the floor whose face rises downstream at `slope_deg` degrees to 1.25 times the
+    still water level and ends at the downstream wall (the walls are the voxel grid's: at least `box`).  `gauges` ColumnGauges stand evenly along the mid-line
+    between the piston's foremost position and the beach's foot.  Particles that would start inside a solid are
+    dropped (carve).  Returns (params, pos, vel, mass, [Box, Wedge], [MotionPath, None], [ColumnGauge, ...]):
+    setObstacles, then setObstaclePaths, then setGauges."""
+    from .gauges import ColumnGauge
+    from .obstacles import Box, MotionPath, Wedge
+    p, _ = dam_break_params(n, box, (1.0, depth, 1.0), neighbors)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    h = float(p.h)
+    length_x, width_z = float(p.max_x), float(p.max_z)   # the walls: the voxel grid's extent, at least `box`
+    level = box[1] * depth
+    back = stroke                                   # rearmost: back - stroke / 2 > 0
+    piston = Box((back, -h, -h), (back + 2.0 * h, float(p.max_y) + h, width_z + h))
+    rise = 1.25 * level
+    length = rise / math.tan(math.radians(slope_deg))
+    foot = length_x - length
+    if not foot > back + 2.0 * h + stroke:
+        raise ValueError("the tank is too short for this beach and stroke")
+    beach = Wedge.ramp((foot, 0.0, -h), (length_x, rise, width_z + h), 0, 1)
+    pos = box_fill(n, (back + 2.0 * h, 0.0, 0.0), (length_x, level, width_z), seed)
+    vel = np.zeros(3 * n, np.float32)
+    mass = np.ones(n, np.float32)
+    pos, vel, mass = carve(pos, vel, mass, [piston, beach])
+    path = MotionPath.sine((0.5 * stroke, 0.0, 0.0), period, keys)
+    x0, x1 = back + 2.0 * h + 0.5 * stroke, foot
+    samples = max(2, int(math.ceil(float(p.max_y) / (0.5 * h))))
+    # half the sampler's density deep inside the fill (as dam_break_gauged's columns)
+    number_density = n / ((length_x - back - 2.0 * h) * level * width_z)
+    iso = 0.5 * number_density * float(p.kernel1) * float(p.sim_scale) ** 6 * h ** 9 * 64.0 * math.pi / 315.0
+    cols = [ColumnGauge((x0 + (x1 - x0) * (g + 1) / (gauges + 1), 0.0, 0.5 * width_z), 1, 0.5 * h, samples, iso)
+            for g in range(gauges)]
+    return p, pos, vel, mass, [piston, beach], [path, None], cols
+
+
 def stirred_tank(n, rate, depth=0.5, blade=(0.6, 0.08), start=0.0, stop=math.inf, box=(1.0, 1.0, 1.0),
                  neighbors=32.0, seed=42, gravity=-9.81):
     """A block of fluid at rest filling the tank to `depth` of its height (gravity along -y, the walls on),

@@ -298,6 +298,7 @@ class SPH(Context):
 
     setObstacles, getObstacles = Context.set_obstacles, Context.get_obstacles
     setObstacleMotion, getObstacleMotion = Context.set_obstacle_motion, Context.get_obstacle_motion
+    setObstaclePaths, getObstaclePaths = Context.set_obstacle_paths, Context.get_obstacle_paths
     recordLoads, getLoads = Context.record_loads, Context.get_loads
 
     def setBodies(self, bodies, quantum_log2=-24):
