@@ -960,6 +960,74 @@ int sph_hip_sample_pressure_points(sph_hip_context* ctx, int n, const float* xyz
 int sph_hip_sample_pressure_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
                                     const int32_t dims[3], float* pressure, float* density, int32_t* count);
 
+/* ---- carried scalars ---------------------------------------------------------------------------- *
+ *
+ * Four channels per particle - a temperature, a dye concentration, a salinity - that move with the fluid,
+ * diffuse between neighbours and are read back or sampled.  No counterpart in the reference.  The
+ * operation-by-operation contract is in csrc/scalar_policy.h; all arithmetic is fp32, unfused, in the order
+ * written.
+ *   storage    one row {T0, T1, T2, T3} per particle ID (the upload row), not per sorted slot: the rows never
+ *              move, a channel with diffusivity 0 keeps its bits for as long as it is carried.
+ *   a step     every sph_hip_step and every queued step of sph_hip_run advances the scalars once, in that
+ *              step's state S_k, behind the step's density pass and before anything moves.  For particle i and
+ *              every channel c with kappa[c] > 0: sum = over i's neighbours j (the acceleration pass's pairs, in
+ *              canonical order) of V_j * (T_j,c - T_i,c) * L(d_ij), T_i,c' = T_i,c + (dt * kappa[c]) * sum, with
+ *              V_j = m_j / rho_j (rho_j the density pass's value; a neighbour whose rho_j is not > 0 contributes
+ *              nothing) and L(d) = kernel3 * (hscaled - d), the reference's viscosity Laplacian.  A channel with
+ *              kappa[c] == 0 is only carried.  The same bits in FULL and FULL_FAST and on every route.
+ *   stability  the scheme is explicit: per channel the update is a convex combination of T_i and its
+ *              neighbours while dt * kappa[c] * (sum over j of V_j * L(d_ij)) <= 1.  Nothing polices that.
+ *              rho_j does not include j itself, so a particle of the spray - its few neighbours all near its
+ *              rim - has next to no density and a volume without bound: V_j * L(d) grows like (h - d)^-2
+ *              there, no kappa > 0 keeps the step convex next to it, and a diffusing channel can overflow and
+ *              spread NaN from there.  A carried channel (kappa 0) is not touched by any of this.
+ *   sources    at most SPH_HIP_MAX_SCALAR_SOURCES boxes.  After the update, in list order, a particle whose S_k
+ *              position is STRICTLY inside [lo, hi] gets T_channel = value (HOLD: a heated plate, a dye
+ *              injector) or T_channel = T_channel + value * dt (ADD: a heater of a given power).
+ *   coupling   one way: no particle, density, acceleration, count or energy changes by a bit; no buoyancy.
+ *              Queued steps stay queued.  A context without scalars launches what it launched before.
+ *   not done   the stand-alone phase calls (sph_hip_compute_density .. sph_hip_integrate) do NOT advance the
+ *              scalars.  REF and slab contexts are refused.  Ports are refused both ways - sph_hip_set_ports
+ *              with an emitter or a sink on a context that carries scalars, sph_hip_set_scalars on a context
+ *              with ports - an emitter would need a value per layer.
+ * sph_hip_set_scalars gives every particle its row (values4: n rows of 4 floats, in ID order) and the
+ * channels their diffusivities kappa4[4]; it waits for the steps already queued.  values4 == NULL or n == 0
+ * switches the scalars off and drops the sources.  SPH_HIP_ERR_INVALID, the previous state kept, for a REF
+ * or slab context, ports, n < 0, n other than the particle count, a value that is not finite, a
+ * diffusivity that is not finite and >= 0.  The buffers (36 bytes per particle of the capacity) are
+ * allocated at the first call.  A new sph_hip_upload drops the scalars and the sources.
+ * sph_hip_get_scalars copies rows first .. first + n - 1, in ID order, after the steps queued so far.
+ * sph_hip_set_scalar_sources replaces the sources for the steps enqueued from now on (n = 0 clears them):
+ * SPH_HIP_ERR_INVALID for a context that carries no scalars, n < 0, n > SPH_HIP_MAX_SCALAR_SOURCES, a
+ * channel outside 0..3, an unknown kind, a box that is not finite or not lo < hi on every axis, a value
+ * that is not finite.  sph_hip_get_scalar_sources copies up to `capacity` of them and returns how many are set.
+ * sph_hip_sample_scalars_points / _lattice follow sph_hip_sample_points / _lattice - their refusals, any
+ * output may be NULL, the lattice's index order, the call synchronises and changes nothing - and return the
+ * Shepard-normalised channels, (sum of t_j * T_j,c) / rho where rho > 0, else 0, over the sampler's members
+ * and terms, beside the sampler's density and count: channels4 holds 4 floats per probe.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no struct and no existing
+ * prototype changed. */
+#define SPH_HIP_SCALAR_CHANNELS     4
+#define SPH_HIP_MAX_SCALAR_SOURCES  8
+#define SPH_HIP_SCALAR_HOLD 0
+#define SPH_HIP_SCALAR_ADD  1
+typedef struct sph_hip_scalar_source {   /* field order is ABI: 36 bytes */
+   float lo[3];
+   float hi[3];
+   int32_t channel;
+   int32_t kind;
+   float value;
+} sph_hip_scalar_source;
+int sph_hip_set_scalars(sph_hip_context* ctx, int n, const float* values4, const float* kappa4);
+int sph_hip_get_scalars(sph_hip_context* ctx, int first, int n, float* out4);
+int sph_hip_set_scalar_sources(sph_hip_context* ctx, const sph_hip_scalar_source* list, int n);
+int sph_hip_get_scalar_sources(sph_hip_context* ctx, sph_hip_scalar_source* out, int capacity);
+/* n probes, xyz interleaved; channels4[4n], density[n], count[n] */
+int sph_hip_sample_scalars_points(sph_hip_context* ctx, int n, const float* xyz, float* channels4, float* density,
+                                  int32_t* count);
+int sph_hip_sample_scalars_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                                   const int32_t dims[3], float* channels4, float* density, int32_t* count);
+
 /* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
  *
  * A particle count that changes while the steps stay queued: emitters append whole lattice layers

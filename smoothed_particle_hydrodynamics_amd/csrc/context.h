@@ -25,6 +25,7 @@
 #include "tracer_kernels.h"
 #include "gauge_kernels.h"
 #include "pressure_kernels.h"
+#include "scalar_kernels.h"
 #include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
@@ -404,6 +405,18 @@ struct sph_hip_context {
    long long grec_step = 0;
    int grec_row_now = -1;   // the row the step being enqueued fills (its pressure kinds follow its density pass)
 
+   // carried scalars (sph_hip_set_scalars): n_scalars rows of four channels by particle ID (scalar_T), and the
+   // stage of a step or a sampler call by sorted slot - the channels (scalar_Ts) and the volumes m / rho
+   // (scalar_Vs); all three hold the capacity and are allocated at the first set.  The diffusivities and the
+   // sources go to a pass by value.
+   int n_scalars = 0;
+   DevBuf<float4> scalar_T, scalar_Ts;
+   DevBuf<float> scalar_Vs;
+   float scalar_kappa[SPH_HIP_SCALAR_CHANNELS] = {0.0f, 0.0f, 0.0f, 0.0f};
+   int n_scalar_sources = 0;
+   sph_hip_scalar_source scalar_sources[SPH_HIP_MAX_SCALAR_SOURCES];
+   int scalar_force_rows = 0;      // SPH_HIP_SCALAR_ROWS=1, read at creation: every workgroup of the pass walks the rows
+
    // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
    // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the
    // emitted totals (host-known) and the removed totals (device, one int64 per sink)
@@ -514,6 +527,7 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    if (const char* v = getenv("SPH_HIP_SURFACE_PLANES")) ctx->surf_planes_forced = atoi(v) > 0 ? atoi(v) : 0;
    ctx->render_noskip = getenv_flag("SPH_HIP_RENDER_NOSKIP");
    ctx->tracer_sort_switch = tracer_sort_switch(getenv("SPH_HIP_TRACER_SORT"));
+   ctx->scalar_force_rows = getenv_flag("SPH_HIP_SCALAR_ROWS");
    ctx->device = device;
    ctx->capacity = capacity;
 

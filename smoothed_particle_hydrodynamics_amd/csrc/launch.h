@@ -858,6 +858,51 @@ int launch_gauges_pressure(sph_hip_context* ctx, int source)
    return launch_gauges_pressure_into(ctx, ctx->grec_dev.get() + (size_t)r * (size_t)ctx->n_gauges, source);
 }
 
+// ---- carried scalars (scalar_kernels.h; contract: scalar_policy.h; routes: launch_policy.h) ---------------
+// the constants, diffusivities and sources of the pass about to be enqueued: by value in its arguments, so a
+// later setter does not reach the steps already queued
+ScalarStep scalar_step_of(const sph_hip_context* ctx, const PairConsts& k)
+{
+   ScalarStep st = {};
+   st.hscaled = k.hscaled;
+   st.kernel3 = k.kernel3;
+   st.sim_scale = k.sim_scale;
+   st.dt = k.dt;
+   for (int c = 0; c < SPH_HIP_SCALAR_CHANNELS; c++) st.kappa[c] = ctx->scalar_kappa[c];
+   st.n_sources = ctx->n_scalar_sources;
+   for (int q = 0; q < ctx->n_scalar_sources; q++) st.sources[q] = ctx->scalar_sources[q];
+   return st;
+}
+
+// Ts (and, with_volumes, Vs from the step's densities) of the current sorted state
+int launch_scalars_stage(sph_hip_context* ctx, bool with_volumes)
+{
+   hipLaunchKernelGGL(k_scalars_stage, dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream, ctx->posm[ctx->cur],
+                      ctx->velp[ctx->cur], with_volumes ? ctx->rho.get() : (const float*)nullptr, ctx->meta,
+                      ctx->scalar_T, ctx->n_scalars, ctx->scalar_Ts, with_volumes ? ctx->scalar_Vs.get() : (float*)nullptr);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// One step of the scalars, behind the step's density pass: the stage, then the pass.  Nothing synchronises.
+int launch_scalars(sph_hip_context* ctx)
+{
+   if (!step_launches_scalars(ctx->n_scalars, ctx->n)) return SPH_HIP_OK;
+   int rc = launch_scalars_stage(ctx, true);
+   if (rc) return rc;
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const ScalarStep st = scalar_step_of(ctx, k);
+   static_assert(TILE_THREADS == 256, "the scalar pass maps one workgroup to 256 sorted particles");
+   bind_flags([&](auto U, auto W) {
+      hipLaunchKernelGGL((k_scalars_step<U.value, W.value>), dim3(div_up(ctx->n, TILE_THREADS)), dim3(TILE_THREADS), 0,
+                         ctx->stream, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->scalar_Ts, ctx->scalar_Vs, ctx->ncount,
+                         ctx->cell_start, ctx->meta, ctx->grid, k.h2, st, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow,
+                         ctx->list_cap, ctx->use_tiled ? 1 : 0, ctx->scalar_force_rows, ctx->scalar_T, ctx->n_scalars);
+   }, unit_scale(ctx->prm), ctx->caps.wide != 0);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
 // buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
 // (prehashed: 1 whole grid, 2 a slab's owned entries).
@@ -948,6 +993,7 @@ int step_impl(sph_hip_context* ctx, bool timed)
    if ((rc = launch_density(ctx))) return rc;
    // the pressure kinds of a row this step fills: with the densities of S_k the pass has just formed
    if (ctx->grec_row_now >= 0 && (rc = launch_gauges_pressure(ctx, gauge_density_source(true)))) return rc;
+   if (ctx->n_scalars > 0 && (rc = launch_scalars(ctx))) return rc;   // carried scalars: in S_k, with its densities and lists
    if ((rc = mark_phase(ctx, se, 3, st))) return rc;
    // a context that holds the whole grid and has never exchanged anything: the integrate also
    // hashes and counts for the next cell build - and the tiled acceleration pass does both itself

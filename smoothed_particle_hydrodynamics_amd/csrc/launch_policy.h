@@ -353,6 +353,37 @@ inline int gauge_density_source(bool behind_step_density) { return behind_step_d
 // of a recording (-1: none) and the set holds a pressure kind.
 inline bool step_reads_pressure(int row, int n_pressure) { return row >= 0 && gauges_launch_pressure(n_pressure); }
 
+// ---- carried scalars (scalar_policy.h) ----------------------------------------------------------
+// Whether a step launches the scalar pass (k_scalars_stage, k_scalars_step) between its density and its
+// acceleration pass: the context carries scalars and has particles.  A context without scalars launches
+// what it always launched.
+inline bool step_launches_scalars(int n_scalars, int n) { return n_scalars > 0 && n > 0; }
+
+// How a workgroup of the scalar pass, and a lane of it, meets its neighbours.  LISTS: the lane walks the
+// neighbour list the density pass wrote for the acceleration pass; ROWS: it walks the nine cell rows as
+// k_particle_density does.  Same pairs, same order, same arithmetic: same bits.  wg_flag is
+// nlist_overflow[wg] (neighbor_lists.h: LISTS_ALL 0, LISTS_NONE 1, LISTS_SOME 2); an untiled context
+// (SPH_HIP_UNTILED=1) has no lists at all, and force_rows (SPH_HIP_SCALAR_ROWS=1, read at creation: tests and
+// cost runs) sends every workgroup down the row walk.
+#define SCALAR_ROUTE_LISTS 0
+#define SCALAR_ROUTE_ROWS 1
+#define SCALAR_FLAG_LISTS_NONE 1u
+#define SCALAR_FLAG_LISTS_SOME 2u
+#define SCALAR_WORD_NO_LIST 0xffffffffu   // NLIST_NO_LIST: the first list word of a lane that went without a list
+constexpr inline int scalar_workgroup_route(bool tiled, bool force_rows, uint32_t wg_flag)
+{
+   return (tiled && !force_rows && wg_flag != SCALAR_FLAG_LISTS_NONE) ? SCALAR_ROUTE_LISTS : SCALAR_ROUTE_ROWS;
+}
+// a lane of a LISTS workgroup: count = its neighbours, first_word = the first 32 bits of its list (which mean
+// anything but entries only in a LISTS_SOME workgroup, for a lane with neighbours)
+constexpr inline int scalar_lane_route(int wg_route, uint32_t wg_flag, int count, uint32_t first_word)
+{
+   return (wg_route == SCALAR_ROUTE_ROWS ||
+           (wg_flag == SCALAR_FLAG_LISTS_SOME && count > 0 && first_word == SCALAR_WORD_NO_LIST))
+             ? SCALAR_ROUTE_ROWS
+             : SCALAR_ROUTE_LISTS;
+}
+
 // ---- timing --------------------------------------------------------------------------------
 // Phase boundary k of a timed step is marked by event phase_event(full, k) of the step's ring
 // slot.  An event record is a barrier packet (several microseconds on the stream), so a boundary

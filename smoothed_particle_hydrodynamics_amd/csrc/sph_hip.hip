@@ -379,6 +379,9 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    }
    ctx->ids_changed = 0;
    ctx->n_in_stale = 0;
+   // carried scalars belong to the rows of the upload they were set for: dropped with their sources
+   ctx->n_scalars = 0;
+   ctx->n_scalar_sources = 0;
    ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
    ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
    ports_mass_rule(ctx, n == 0);
@@ -1146,6 +1149,7 @@ int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int
    if (ctx->plane_lo != 0 || ctx->plane_hi != ctx->grid.nz_global || ctx->had_exchange)
       return refuse(ctx, who, "slab contexts (with neighbours, or that have exchanged) cannot have ports");
    if (const char* why = port_check(emitters, ne, sinks, ns, port_grid(ctx))) return refuse(ctx, who, why);
+   if (const char* why = scalar_ports_check(ctx->n_scalars, ne, ns)) return refuse(ctx, who, why);
    // a pending prehash counted for a build whose entries the ports may change first
    if ((rc = drop_prehash(ctx))) return rc;
    // steps already queued keep the lists they were enqueued with: the copies go behind them
@@ -1969,6 +1973,195 @@ int sph_hip_sample_pressure_lattice(sph_hip_context* ctx, const float origin[3],
             if (pressure) SPH_TRY(copy_out(pressure, sprs));
             if (density) SPH_TRY(copy_out(density, srho));
             if (count) SPH_TRY(copy_out(count, scnt));
+         }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// ---- carried scalars (scalar_kernels.h; contract and checks: scalar_policy.h) -----------------------
+
+int sph_hip_set_scalars(sph_hip_context* ctx, int n, const float* values4, const float* kappa4)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_scalars";
+   if ((rc = sample_check(ctx, who))) return rc;
+   if (const char* why = scalar_context_check(ports_active(ctx->n_emit, ctx->n_sink), ctx->ids_changed != 0))
+      return refuse(ctx, who, why);
+   if (const char* why = scalar_set_check(n, values4, kappa4, ctx->n_owned)) return refuse(ctx, who, why);
+   // steps already queued advance the old rows: wait for them before they go
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (!values4 || n == 0) {
+      ctx->n_scalars = 0;
+      ctx->n_scalar_sources = 0;
+      return SPH_HIP_OK;
+   }
+   if (!ctx->scalar_T) {
+      DevBuf<float4> rows, staged;
+      DevBuf<float> volumes;
+      if (dev_alloc(rows, (size_t)ctx->capacity) != hipSuccess || dev_alloc(staged, (size_t)ctx->capacity) != hipSuccess ||
+          dev_alloc(volumes, (size_t)ctx->capacity) != hipSuccess) {
+         (void)hipGetLastError();
+         ctx->err = "sph_hip_set_scalars: cannot allocate the scalars of " + std::to_string(ctx->capacity) + " particles";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      ctx->scalar_T = std::move(rows);
+      ctx->scalar_Ts = std::move(staged);
+      ctx->scalar_Vs = std::move(volumes);
+   }
+   SPH_TRY(hipMemcpy(ctx->scalar_T, values4, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice));
+   for (int c = 0; c < SPH_HIP_SCALAR_CHANNELS; c++) ctx->scalar_kappa[c] = kappa4[c];
+   ctx->n_scalars = n;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_scalars(sph_hip_context* ctx, int first, int n, float* out4)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_get_scalars";
+   if (const char* why = scalar_have_check(ctx->n_scalars)) return refuse(ctx, who, why);
+   if (const char* why = scalar_range_check(first, n, ctx->n_scalars)) return refuse(ctx, who, why);
+   if (n > 0 && !out4) return refuse(ctx, who, "null output array");
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (n > 0)
+      SPH_TRY(hipMemcpy(out4, ctx->scalar_T.get() + first, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost));
+   return SPH_HIP_OK;
+}
+
+int sph_hip_set_scalar_sources(sph_hip_context* ctx, const sph_hip_scalar_source* list, int n)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_scalar_sources";
+   if (const char* why = scalar_have_check(ctx->n_scalars)) return refuse(ctx, who, why);
+   if (const char* why = scalar_source_check(list, n)) return refuse(ctx, who, why);
+   // (a pass takes its sources by value: the steps already queued keep theirs)
+   for (int q = 0; q < n; q++) ctx->scalar_sources[q] = list[q];
+   ctx->n_scalar_sources = n;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_scalar_sources(sph_hip_context* ctx, sph_hip_scalar_source* out, int capacity)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (capacity < 0 || (capacity > 0 && !out))
+      return refuse(ctx, "sph_hip_get_scalar_sources", "negative capacity or null array");
+   const int m = ctx->n_scalar_sources < capacity ? ctx->n_scalar_sources : capacity;
+   for (int q = 0; q < m; q++) out[q] = ctx->scalar_sources[q];
+   return ctx->n_scalar_sources;
+}
+
+// The sampler's calls with the channel walk: behind the cell build the scalars are staged by sorted slot
+// (launch_scalars_stage, channels only), then the probes are walked.
+
+int sph_hip_sample_scalars_points(sph_hip_context* ctx, int n, const float* xyz, float* channels4, float* density,
+                                  int32_t* count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_sample_scalars_points";
+   if (n < 0 || (n > 0 && !xyz)) return refuse(ctx, who, "negative count or null probe array");
+   if ((rc = sample_check(ctx, who))) return rc;
+   if (const char* why = scalar_have_check(ctx->n_scalars)) return refuse(ctx, who, why);
+   if (n == 0) return SPH_HIP_OK;
+   if (ctx->n == 0) {
+      if (channels4) memset(channels4, 0, sizeof(float) * 4 * (size_t)n);
+      return sample_zero((size_t)n, density, nullptr, count);
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   if ((rc = launch_scalars_stage(ctx, false))) return rc;
+   // (36 bytes a probe against the sampler's 32: half its chunk keeps the scratch inside the 64 MiB budget)
+   const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS / 2);
+   if ((rc = ctx->sample_buf.reserve(ctx, (size_t)chunk * 9))) return rc;
+   // (the channels first: 16-byte stores)
+   float4* schan = reinterpret_cast<float4*>(ctx->sample_buf.get());
+   float* sxyz = ctx->sample_buf.get() + 4 * (size_t)chunk;
+   float* srho = sxyz + 3 * (size_t)chunk;
+   int32_t* scnt = reinterpret_cast<int32_t*>(srho + (size_t)chunk);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   hipStream_t st = ctx->stream;
+   for (int p0 = 0; p0 < n; p0 += chunk) {
+      const int m = n - p0 < chunk ? n - p0 : chunk;
+      SPH_TRY(hipMemcpyAsync(sxyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+      bind_flags([&](auto U) {
+         hipLaunchKernelGGL((k_sample_scalars_points<U.value>), dim3(div_up(m, 256)), dim3(256), 0, st, sxyz, m,
+                            ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start, ctx->grid, k, schan, srho, scnt);
+      }, unit_scale(ctx->prm));
+      SPH_TRY(hipGetLastError());
+      if (channels4)
+         SPH_TRY(hipMemcpyAsync(channels4 + 4 * (size_t)p0, schan, sizeof(float4) * m, hipMemcpyDeviceToHost, st));
+      if (density) SPH_TRY(hipMemcpyAsync(density + p0, srho, sizeof(float) * m, hipMemcpyDeviceToHost, st));
+      if (count) SPH_TRY(hipMemcpyAsync(count + p0, scnt, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
+   }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+int sph_hip_sample_scalars_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                                   const int32_t dims[3], float* channels4, float* density, int32_t* count)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_sample_scalars_lattice";
+   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, who, why);
+   if ((rc = sample_check(ctx, who))) return rc;
+   if (const char* why = scalar_have_check(ctx->n_scalars)) return refuse(ctx, who, why);
+   if (ctx->n == 0) {
+      const size_t total = (size_t)dims[0] * dims[1] * dims[2];
+      if (channels4) memset(channels4, 0, sizeof(float) * 4 * total);
+      return sample_zero(total, density, nullptr, count);
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   if ((rc = launch_scalars_stage(ctx, false))) return rc;
+   double cells[3];
+   sample_spacing_cells(spacing, ctx->grid.inv, cells);
+   const SampleBrick brick = sample_brick(dims, cells);
+   const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
+   const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
+   if ((rc = ctx->sample_buf.reserve(ctx, chunk_points * 6))) return rc;
+   float4* schan = reinterpret_cast<float4*>(ctx->sample_buf.get());
+   float* srho = ctx->sample_buf.get() + 4 * chunk_points;
+   int32_t* scnt = reinterpret_cast<int32_t*>(srho + chunk_points);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   const bool unit = unit_scale(ctx->prm);
+   hipStream_t st = ctx->stream;
+   SampleLattice L = lattice_of(origin, spacing, brick);
+   // (sph_hip_sample_lattice's copy of a chunk's box into the caller's arrays; elem bytes a point)
+   auto copy_out = [&](void* dst, const void* src, size_t elem) -> hipError_t {
+      char* d = (char*)dst;
+      const char* s = (const char*)src;
+      const size_t plane = (size_t)dims[0] * dims[1];
+      if (L.ex == dims[0] && L.ey == dims[1])
+         return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem,
+                               hipMemcpyDeviceToHost, st);
+      for (int z = 0; z < L.ez; z++) {
+         const hipError_t e = hipMemcpy2DAsync(
+             d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
+             s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
+             hipMemcpyDeviceToHost, st);
+         if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
+   };
+   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += c.ez)
+      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += c.ey)
+         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += c.ex) {
+            L.ex = dims[0] - L.i0 < c.ex ? dims[0] - L.i0 : c.ex;
+            L.ey = dims[1] - L.j0 < c.ey ? dims[1] - L.j0 : c.ey;
+            L.ez = dims[2] - L.k0 < c.ez ? dims[2] - L.k0 : c.ez;
+            L.bricks_x = div_up(L.ex, L.bx);
+            L.bricks_y = div_up(L.ey, L.by);
+            const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
+            bind_flags([&](auto U) {
+               hipLaunchKernelGGL((k_sample_scalars_lattice<U.value>), dim3(bricks), dim3(SAMPLE_THREADS), 0, st, L,
+                                  ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start, ctx->grid, k, schan, srho, scnt);
+            }, unit);
+            SPH_TRY(hipGetLastError());
+            if (channels4) SPH_TRY(copy_out(channels4, schan, sizeof(float4)));
+            if (density) SPH_TRY(copy_out(density, srho, sizeof(float)));
+            if (count) SPH_TRY(copy_out(count, scnt, sizeof(int32_t)));
          }
    SPH_TRY(hipStreamSynchronize(st));
    return SPH_HIP_OK;

@@ -510,3 +510,43 @@ def channel_weir(n, crest=0.6, at=0.45, ramps=(0.3, 0.2), top=0.1, box=(2.0, 0.5
             Wedge.ramp((x2, 0.0, z0), (x3, height, z1), 0, 1, rising=False)]
     pos, vel, mass = carve(pos, vel, mass, weir)
     return p, pos, vel, mass, weir, emitters, sinks
+
+
+def scalar_stable_kappa(p, fraction=0.25):
+    """A diffusivity for carried scalars that keeps a step convex deep inside a fluid at its rest spacing.  The
+    explicit update is a convex combination while dt * kappa * sum_j V_j * kernel3 * (h - d_ij) <= 1
+    (include/sph_hip.h: carried scalars); with volumes that tile the fluid the sum is the integral of
+    kernel3 * (h - r) over the kernel's support, kernel3 * pi * h^4 / 3 in scaled lengths.  Returns the kappa for
+    which the product is `fraction`.  Near a free surface volumes are larger than the bulk's: keep a margin."""
+    hs = float(p.hscaled)
+    total = float(p.kernel3) * math.pi * hs ** 4 / 3.0   # (densities, and so volumes, are per scaled length cubed)
+    return fraction / (float(p.time_step) * total)
+
+
+def heated_floor(n, depth=0.3, hot=1.0, box=(1.0, 1.0, 1.0), neighbors=32.0, seed=42, gravity=-9.81):
+    """Still water `depth` of the box deep, gravity along -y and the walls on, over a heated floor: channel 0 is
+    a temperature that starts at 0 and diffuses (scalar_stable_kappa), and one HOLD source - a slab one kernel
+    radius thick along the whole floor, reaching a radius beyond the walls - keeps it at `hot`.  Returns (params,
+    pos, vel, mass, values[n, 4], kappa[4], [ScalarSource]): setParticles, setScalars, then setScalarSources."""
+    from .scalars import ScalarSource
+    p, pos, vel, mass = dam_break(n, box, (1.0, depth, 1.0), neighbors, seed)
+    p.apply_gravity = 1
+    p.apply_walls = 1
+    p.gravity[0], p.gravity[1], p.gravity[2] = 0.0, gravity, 0.0
+    h = float(p.h)
+    values = np.zeros((n, 4), np.float32)
+    kappa = np.zeros(4, np.float32)
+    kappa[0] = scalar_stable_kappa(p)
+    slab = ScalarSource.hold((-h, -h, -h), (float(p.max_x) + h, h, float(p.max_z) + h), 0, hot)
+    return p, pos, vel, mass, values, kappa, [slab]
+
+
+def dam_break_dyed(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42, gravity=-9.81):
+    """The surging column of dam_break_dye with a dye concentration in place of the tracers: channel 0 is 1 in
+    the column's upstream half (x below half its width) and 0 in the other, with diffusivity 0 - every particle
+    carries its value unchanged, so the channel shows where the upstream water goes.  Returns (params, pos, vel,
+    mass, values[n, 4], kappa[4]): setParticles, then setScalars."""
+    p, pos, vel, mass, _ = dam_break_dye(n, 1.0, surge, box, fill, neighbors, seed, gravity)
+    values = np.zeros((n, 4), np.float32)
+    values[:, 0] = (pos.reshape(-1, 3)[:, 0] < np.float32(0.5 * box[0] * fill[0])).astype(np.float32)
+    return p, pos, vel, mass, values, np.zeros(4, np.float32)

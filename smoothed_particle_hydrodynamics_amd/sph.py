@@ -17,6 +17,7 @@ import numpy as np
 from . import gauges as _G
 from . import obstacles as _O
 from . import ports as _P
+from . import scalars as _S
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, TracerPath, Tracers, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
@@ -528,6 +529,69 @@ class SPH(Context):
         self.call("sph_hip_sample_pressure_lattice", C.byref(o), C.byref(s), C.byref(d), _ptr(prs), _ptr(rho),
                   _ptr(cnt))
         return prs, rho, cnt
+
+    # ---- carried scalars (sph_hip_set_scalars) --------------------------------------------------
+    def setScalars(self, values, diffusivity=0.0):
+        """Give every particle its carried scalars: `values` is (n,) or (n, c) with c <= 4 in particle order,
+        padded with zeros to four channels; `diffusivity` is one kappa for every channel or up to four of
+        them (padded with zeros; a channel with kappa 0 is only carried, its bits kept).  values=None
+        switches the scalars off.  From the next step on every step moves them with the fluid and diffuses
+        them between neighbours (include/sph_hip.h: carried scalars), explicitly: per channel a step is a
+        convex combination of a particle's value and its neighbours' while
+        dt * kappa * sum_j (m_j / rho_j) * kernel3 * (h - d_ij) <= 1, and nothing polices that condition - next to
+        a particle of the spray, whose density is next to nothing, it fails for any kappa > 0 and a diffusing
+        channel can overflow (scenes.scalar_stable_kappa gives a kappa for the bulk).  No particle changes by a bit.  A new setParticles drops the scalars and the sources."""
+        if values is None:
+            self.call("sph_hip_set_scalars", 0, None, None)
+            return
+        v = _S.pad_values(values)
+        k = _S.pad_diffusivity(diffusivity)
+        self.call("sph_hip_set_scalars", v.shape[0], _ptr(v), _ptr(k))
+
+    def getScalars(self):
+        """The carried scalars after every step enqueued so far, float32 (n, 4) in particle order
+        (sph_hip_get_scalars; synchronises)."""
+        n = self.mParticleCount
+        out = np.zeros((n, _S.CHANNELS), np.float32)
+        self.call("sph_hip_get_scalars", 0, n, _ptr(out))
+        return out
+
+    def setScalarSources(self, sources):
+        """Replace the scalar sources with `sources` (scalars.ScalarSource.hold / .add, at most 8; an empty
+        list clears them), for the steps enqueued from now on."""
+        arr, n = _S.as_array(sources)
+        self.call("sph_hip_set_scalar_sources", arr, n)
+
+    def getScalarSources(self):
+        arr = (_S.SphScalarSource * _S.MAX_SOURCES)()
+        n = self.call("sph_hip_get_scalar_sources", arr, _S.MAX_SOURCES)
+        return [_S.from_struct(arr[i]) for i in range(n)]
+
+    def sampleScalars(self, points):
+        """The carried scalars of the current state at `points` ((n, 3) float32): (channels[n, 4], density[n],
+        count[n]) - the Shepard-normalised sums over the sampler's members, 0 where there are none.  The
+        simulation is not changed by the call."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        chan = np.zeros((n, _S.CHANNELS), np.float32)
+        rho = np.zeros(n, np.float32)
+        cnt = np.zeros(n, np.int32)
+        self.call("sph_hip_sample_scalars_points", n, _ptr(pts), _ptr(chan), _ptr(rho), _ptr(cnt))
+        return chan, rho, cnt
+
+    def sampleScalarLattice(self, origin, spacing, shape):
+        """The same on sampleLattice's lattice, shape = (nx, ny, nz): (channels[nz, ny, nx, 4],
+        density[nz, ny, nx], count[nz, ny, nx])."""
+        o, s, d, dims = _lattice(origin, spacing, shape)
+        grid = (max(dims[2], 0), max(dims[1], 0), max(dims[0], 0))
+        if grid[0] * grid[1] * grid[2] >= 2 ** 31:
+            raise ValueError("a lattice of more than 2^31 - 1 points")
+        chan = np.zeros(grid + (_S.CHANNELS,), np.float32)
+        rho = np.zeros(grid, np.float32)
+        cnt = np.zeros(grid, np.int32)
+        self.call("sph_hip_sample_scalars_lattice", C.byref(o), C.byref(s), C.byref(d), _ptr(chan), _ptr(rho),
+                  _ptr(cnt))
+        return chan, rho, cnt
 
     def extractSurface(self, origin, spacing, shape, iso, normals=True, velocity=False):
         """The surface {density > iso} of the lattice sampleLattice(origin, spacing, shape) would
