@@ -507,6 +507,72 @@ int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const 
                          uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
                          int32_t* first_inside, int32_t* solid_id);
 
+/* ---- scalar renderer ----------------------------------------------------------------------- *
+ *
+ * The frame of sph_hip_render_scene - of sph_hip_render when sp is NULL - in which every pixel that
+ * shows fluid is coloured by one carried channel (carried scalars, below) through a colour table.
+ * The fluid pass and the solids pass are the two renderers', unchanged; a pass of its own (k_tint_surface
+ * or k_tint_column) then overwrites rgba on the fluid pixels and writes `scalar`.  csrc/tint_policy.h
+ * holds the functions, one set for the device and the host.  All arithmetic is fp32, unfused, in the
+ * order written; fminf / fmaxf follow C99.
+ *   pixels     a pixel whose first_inside >= 0 after the fluid pass and the solids pass is a fluid hit
+ *              that no solid took: it is tinted.  Every other pixel keeps the bits of
+ *              sph_hip_render_scene (with sp NULL: of sph_hip_render, and solid_id is -1 everywhere) and
+ *              its scalar is 0.
+ *   ray        d, tnear, tfar and t_k = tnear + (float)k * step exactly as the renderer forms them;
+ *              t_hit is the depth output; p_hit = eye + t_hit * d per component.
+ *   walk       walk(p) is the scalar sampler's walk over the sampler's members in canonical order:
+ *              rho = sum of t_j, a_c = sum of t_j * T_j,c, count - what sph_hip_sample_scalars_points
+ *              forms at p, on the channels staged by sorted slot once per call.
+ *   SURFACE    v = rho > 0 ? a_channel / rho : 0 at p_hit: the value sph_hip_sample_scalars_points
+ *              returns there.
+ *   COLUMN     A = 0.0f; for k = first_inside, first_inside + 1, ... while t_k <= tfar and
+ *              k < max_samples: (rho, a) = walk(eye + t_k * d); if rho > iso (strictly; NaN is outside)
+ *              A = A + (rho > 0 ? a_channel / rho : 0) * step.  v = A: the channel integrated along the
+ *              ray through the fluid; with a channel that is 1 everywhere, the fluid's thickness.
+ *              The marched box clips the column.  Solids do NOT: particles do not stand inside solids,
+ *              so a solid contributes nothing, but the fluid behind a solid that the ray passes through
+ *              after its fluid hit is added.  (A sample in a cell the renderer's occupancy map leaves
+ *              unmarked has rho exactly +0 and is outside: its walk is skipped, which changes no bit;
+ *              SPH_HIP_RENDER_NOSKIP=1 walks every sample.)
+ *   map        u = (v - lo) / (hi - lo); u = fminf(fmaxf(u, 0.0f), 1.0f) (a NaN value lands on row 0);
+ *              x = u * (float)(n_colors - 1); i = (int)x, lowered to n_colors - 2 where larger;
+ *              fr = x - (float)i; col_c = t[i][c] + fr * (t[i+1][c] - t[i][c]), t = table_rgb.
+ *   shade      w = 1.0f with SPH_HIP_TINT_FLAT, else the renderer's w = ambient + diffuse * fmaxf(ndl, 0.0f)
+ *              from normal_xyz as stored and rp->light; channel c = the renderer's byte of col_c * w,
+ *              alpha 255.  scalar = v.  FLAT exists for cut views: clipping `box` to half the tank makes
+ *              rays enter inside the fluid (first_inside == 0), where the density gradient is no surface
+ *              normal.
+ * The call synchronises and changes nothing: sph_hip_download, sph_hip_get_scalars, the motion clock, the
+ * bodies' state and every later step are bit-identical to a run without it.  With no particle resident
+ * the frame is the scene's and scalar is 0.
+ * SPH_HIP_ERR_INVALID, with a last_error text that names sph_hip_render_scalars, for everything
+ * sph_hip_render_scene refuses (but sp may be NULL), a non-null albedo array or n_albedo != 0 with a
+ * null sp, a context that carries no scalars, null tp or table_rgb, a channel outside 0 .. 3, an unknown
+ * mode, unknown tint flag bits, n_colors outside [2, 256], a lo, hi or table entry that is not finite,
+ * and lo >= hi.
+ * This entry point was added without a change of SPH_HIP_ABI_VERSION: no existing struct and no
+ * existing prototype changed. */
+#define SPH_HIP_TINT_SURFACE 0
+#define SPH_HIP_TINT_COLUMN  1
+#define SPH_HIP_TINT_FLAT    1          /* flag: no Lambert factor */
+#define SPH_HIP_TINT_MAX_COLORS 256
+typedef struct sph_hip_tint_params {    /* field order is ABI: 24 bytes */
+   int32_t channel;     /* 0 .. 3 */
+   int32_t mode;        /* SPH_HIP_TINT_SURFACE or SPH_HIP_TINT_COLUMN */
+   float lo, hi;        /* the values mapped onto the table's ends; lo < hi */
+   int32_t n_colors;    /* 2 .. 256 rows of table_rgb */
+   int32_t flags;       /* SPH_HIP_TINT_FLAT or 0 */
+} sph_hip_tint_params;
+
+int sph_hip_render_scalars(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                           const sph_hip_scene_params* sp /* NULL: fluid only */,
+                           const float* solid_albedo_rgb /* 3n or NULL */, int n_albedo,
+                           const sph_hip_tint_params* tp, const float* table_rgb /* 3 * n_colors */,
+                           int width, int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz,
+                           float* velocity_xyz, int32_t* first_inside, int32_t* solid_id,
+                           float* scalar /* one per pixel, may be NULL */);
+
 /* ---- static obstacles --------------------------------------------------------------------- *
  *
  * Analytic solids inside the domain: spheres, axis-aligned boxes, axis-aligned capped

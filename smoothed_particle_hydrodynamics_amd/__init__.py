@@ -5,11 +5,11 @@
 point raises."""
 from .build import build_library, library_path  # noqa: F401
 from .lib import SphParams, load_library, SphHipError, default_params  # noqa: F401
-from .sph import SPH, Particle, SurfaceMesh, write_ply, Camera, RenderResult, write_png, MODE_REF, MODE_FULL, MODE_FULL_FAST, ARITH_EXACT, ARITH_FAST  # noqa: F401
+from .sph import SPH, Particle, SurfaceMesh, write_ply, Camera, RenderResult, ScalarRenderResult, write_png, MODE_REF, MODE_FULL, MODE_FULL_FAST, ARITH_EXACT, ARITH_FAST  # noqa: F401
 from .lib import TIMING_OFF, TIMING_SUMS, TIMING_PHASES  # noqa: F401
 from .lib import Loads, LOAD_SOLIDS  # noqa: F401
 from .lib import Tracers, TracerPath  # noqa: F401
 from .gauges import PointGauge, ColumnGauge, SectionGauge, PressureGauge, PressurePatch, GaugeReadings, GaugeRecord  # noqa: F401
 from .ports import Emitter, Sink, PortTotals  # noqa: F401
 from .scalars import ScalarSource  # noqa: F401
-from . import gauges, obstacles, ports, scalars, scenes  # noqa: F401
+from . import colormaps, gauges, obstacles, ports, scalars, scenes  # noqa: F401

@@ -16,6 +16,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "context.h", "launch.h", "slab_comm.h", "sample_kernels.h", "sample_policy.h",
            "surface_kernels.h", "surface_policy.h", "render_kernels.h", "render_policy.h",
            "scene_kernels.h", "scene_policy.h", "obstacle_policy.h",
+           "tint_kernels.h", "tint_policy.h",
            "load_policy.h", "body_policy.h", "tracer_kernels.h", "tracer_policy.h",
            "gauge_kernels.h", "gauge_policy.h", "pressure_kernels.h",
            "scalar_kernels.h", "scalar_policy.h",

@@ -22,6 +22,7 @@
 #include "surface_kernels.h"
 #include "render_kernels.h"
 #include "scene_kernels.h"
+#include "tint_kernels.h"
 #include "tracer_kernels.h"
 #include "gauge_kernels.h"
 #include "pressure_kernels.h"
@@ -303,6 +304,10 @@ struct sph_hip_context {
    Scratch<int32_t> scene_id;
    Scratch<SceneSolid> scene_list;
    SceneSolid scene_list_host[SPH_HIP_MAX_OBSTACLES];
+   // scalar renderer (sph_hip_render_scalars): a chunk's scalar, and the colour table of the call
+   Scratch<float> tint_scalar;
+   Scratch<float> tint_table;
+   float tint_table_host[TINT_TABLE_FLOATS];
 
    // static obstacles (sph_hip_set_obstacles): the list the next enqueued steps use, its device copy,
    // and the pinned staging of that copy (reused only after the event behind the last copy)

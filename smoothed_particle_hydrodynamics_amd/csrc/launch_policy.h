@@ -359,6 +359,11 @@ inline bool step_reads_pressure(int row, int n_pressure) { return row >= 0 && ga
 // what it always launched.
 inline bool step_launches_scalars(int n_scalars, int n) { return n_scalars > 0 && n > 0; }
 
+// Whether a frame launches the tint pass (k_scalars_stage once, then k_tint_surface or k_tint_column per row
+// chunk: tint_kernels.h): the caller is sph_hip_render_scalars and a particle is resident.  Without a particle
+// there is no fluid pixel to tint; sph_hip_render and sph_hip_render_scene launch what they always launched.
+inline bool frame_launches_tint(bool have_tint, int n_particles) { return have_tint && n_particles > 0; }
+
 // How a workgroup of the scalar pass, and a lane of it, meets its neighbours.  LISTS: the lane walks the
 // neighbour list the density pass wrote for the acceleration pass; ROWS: it walks the nine cell rows as
 // k_particle_density does.  Same pairs, same order, same arithmetic: same bits.  wg_flag is

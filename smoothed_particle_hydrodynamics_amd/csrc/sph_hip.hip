@@ -2347,16 +2347,25 @@ struct SceneDraw {
    int32_t* solid_id;   // host output, may be null
 };
 
-// The frame of both entry points, arguments checked: the row chunks, their scratch, the launches and the
+// the tint of a scalar frame (null: no pixel is tinted)
+struct TintDraw {
+   sph_hip_tint_params tp;
+   const float* table;   // host, 3 * n_colors floats
+   float* scalar;        // host output, may be null
+};
+
+// The frame of the three entry points, arguments checked: the row chunks, their scratch, the launches and the
 // copies.  `who` names the caller in an error text.
 int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* cam, const sph_hip_render_params* rp,
                  int width, int height, int flags, uint8_t* rgba, float* depth, float* normal_xyz,
-                 float* velocity_xyz, int32_t* first_inside, const SceneDraw* scene)
+                 float* velocity_xyz, int32_t* first_inside, const SceneDraw* scene, const TintDraw* tint = nullptr)
 {
    int rc;
    const size_t pixels = (size_t)width * height;
    const bool vel = (flags & SPH_HIP_RENDER_VELOCITY) != 0;
    const bool solids = scene && scene->n > 0;
+   const bool tinted = frame_launches_tint(tint != nullptr, ctx->n);
+   if (tint && !tinted && tint->scalar) memset(tint->scalar, 0, sizeof(float) * pixels);
    if (velocity_xyz && !vel) memset(velocity_xyz, 0, sizeof(float) * 3 * pixels);
    if (scene && !solids && scene->solid_id) memset(scene->solid_id, 0xff, sizeof(int32_t) * pixels);
    if (ctx->n == 0 && !solids) {
@@ -2372,6 +2381,7 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
    }
    const bool fluid = ctx->n > 0;   // without a particle the solids are drawn over a background frame
    if (fluid && (rc = sample_prepare(ctx))) return rc;
+   if (tinted && (rc = launch_scalars_stage(ctx, false))) return rc;   // the channels by sorted slot, once
    hipStream_t st = ctx->stream;
    const CellGrid& g = ctx->grid;
    const bool skip = !ctx->render_noskip;
@@ -2403,6 +2413,19 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
       s_id = ctx->scene_id.get();
       SPH_TRY(hipMemcpyAsync(ctx->scene_list.get(), ctx->scene_list_host, sizeof(SceneSolid) * (size_t)scene->n,
                              hipMemcpyHostToDevice, st));
+   }
+   float* s_scalar = nullptr;
+   TintArgs T = {};
+   if (tinted) {
+      // the tint pass's own scratch (tint_policy.h) and the table, on the device before the first chunk
+      if ((rc = ctx->tint_scalar.reserve(ctx, (size_t)(tint_scalar_bytes(width, rows) / 4), no_scratch.c_str()))) return rc;
+      if ((rc = ctx->tint_table.reserve(ctx, TINT_TABLE_FLOATS))) return rc;
+      s_scalar = ctx->tint_scalar.get();
+      const size_t table_bytes = sizeof(float) * 3 * (size_t)tint->tp.n_colors;
+      memcpy(ctx->tint_table_host, tint->table, table_bytes);
+      SPH_TRY(hipMemcpyAsync(ctx->tint_table.get(), ctx->tint_table_host, table_bytes, hipMemcpyHostToDevice, st));
+      T.tp = tint->tp;
+      T.table = ctx->tint_table.get();
    }
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
@@ -2441,6 +2464,24 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
          }, !fluid);
          SPH_TRY(hipGetLastError());
       }
+      if (tinted) {
+         // untinted pixels keep this 0; the hit list and its count are the march's, still in the scratch
+         SPH_TRY(hipMemsetAsync(s_scalar, 0, sizeof(float) * (size_t)chunk, st));
+         const bool flat = (tint->tp.flags & SPH_HIP_TINT_FLAT) != 0;
+         if (tint->tp.mode == SPH_HIP_TINT_SURFACE)
+            bind_flags([&](auto U, auto FL) {
+               hipLaunchKernelGGL((k_tint_surface<U.value, FL.value>), dim3(div_up(chunk, RENDER_THREADS)),
+                                  dim3(RENDER_THREADS), 0, st, F, T, ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start,
+                                  g, k, s_hits, s_count, s_first, s_depth, s_nrm, s_rgba, s_scalar);
+            }, unit, flat);
+         else
+            bind_flags([&](auto U, auto S, auto FL) {
+               hipLaunchKernelGGL((k_tint_column<U.value, S.value, FL.value>), dim3(div_up(chunk, RENDER_THREADS)),
+                                  dim3(RENDER_THREADS), 0, st, F, T, ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start,
+                                  g, k, occ, s_hits, s_count, s_first, s_nrm, s_rgba, s_scalar);
+            }, unit, skip, flat);
+         SPH_TRY(hipGetLastError());
+      }
       const size_t o = (size_t)F.row0 * width;
       if (rgba) SPH_TRY(hipMemcpyAsync(rgba + 4 * o, s_rgba, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
       if (depth) SPH_TRY(hipMemcpyAsync(depth + o, s_depth, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
@@ -2450,8 +2491,35 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
       if (first_inside) SPH_TRY(hipMemcpyAsync(first_inside + o, s_first, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
       if (solids && scene->solid_id)
          SPH_TRY(hipMemcpyAsync(scene->solid_id + o, s_id, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
+      if (tinted && tint->scalar)
+         SPH_TRY(hipMemcpyAsync(tint->scalar + o, s_scalar, (size_t)chunk * 4, hipMemcpyDeviceToHost, st));
    }
    SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// the solids as they stand now (sph_hip_get_obstacles_now's list), their velocities and albedos, into
+// ctx->scene_list_host
+int scene_solids_now(sph_hip_context* ctx, const SceneDraw& scene, const sph_hip_scene_params* sp,
+                     const float* solid_albedo_rgb, int n_albedo)
+{
+   int rc;
+   sph_hip_obstacle now[SPH_HIP_MAX_OBSTACLES];
+   BodyState st[SPH_HIP_MAX_OBSTACLES];
+   if ((rc = obstacles_now(ctx, now, scene.n, st))) return rc;
+   for (int i = 0; i < scene.n; i++) {
+      SceneSolid& s = ctx->scene_list_host[i];
+      s.o = now[i];
+      if (ctx->n_bodies > 0 && body_is(ctx->bodies_host[i]))
+         for (int c = 0; c < 3; c++) s.vel[c] = st[i].V[c];
+      else if (i < ctx->n_path_entries && path_is(ctx->paths_host[i]))
+         path_velocity(ctx->paths_host[i], ctx->path_keys_host.data(), ctx->motion_tau, s.vel);
+      else if (i < ctx->n_motion)
+         scene_motion_velocity(ctx->motion_host[i], ctx->motion_tau, s.vel);
+      else
+         for (int c = 0; c < 3; c++) s.vel[c] = 0.0f;
+      for (int c = 0; c < 3; c++) s.alb[c] = n_albedo > 0 ? solid_albedo_rgb[3 * i + c] : sp->albedo[c];
+   }
    return SPH_HIP_OK;
 }
 
@@ -2481,26 +2549,38 @@ int sph_hip_render_scene(sph_hip_context* ctx, const sph_hip_camera* cam, const 
    if ((rc = sample_check(ctx, "sph_hip_render_scene"))) return rc;
    if (const char* why = scene_check(cam, rp, sp, solid_albedo_rgb, n_albedo, ctx->n_obst, width, height, flags))
       return refuse(ctx, "sph_hip_render_scene", why);
-   // the solids as they stand now (sph_hip_get_obstacles_now's list), their velocities and albedos
    SceneDraw scene = {*sp, ctx->n_obst, solid_id};
-   sph_hip_obstacle now[SPH_HIP_MAX_OBSTACLES];
-   BodyState st[SPH_HIP_MAX_OBSTACLES];
-   if ((rc = obstacles_now(ctx, now, scene.n, st))) return rc;
-   for (int i = 0; i < scene.n; i++) {
-      SceneSolid& s = ctx->scene_list_host[i];
-      s.o = now[i];
-      if (ctx->n_bodies > 0 && body_is(ctx->bodies_host[i]))
-         for (int c = 0; c < 3; c++) s.vel[c] = st[i].V[c];
-      else if (i < ctx->n_path_entries && path_is(ctx->paths_host[i]))
-         path_velocity(ctx->paths_host[i], ctx->path_keys_host.data(), ctx->motion_tau, s.vel);
-      else if (i < ctx->n_motion)
-         scene_motion_velocity(ctx->motion_host[i], ctx->motion_tau, s.vel);
-      else
-         for (int c = 0; c < 3; c++) s.vel[c] = 0.0f;
-      for (int c = 0; c < 3; c++) s.alb[c] = n_albedo > 0 ? solid_albedo_rgb[3 * i + c] : sp->albedo[c];
-   }
+   if ((rc = scene_solids_now(ctx, scene, sp, solid_albedo_rgb, n_albedo))) return rc;
    return render_frame(ctx, "sph_hip_render_scene", cam, rp, width, height, flags, rgba, depth, normal_xyz,
                        velocity_xyz, first_inside, &scene);
+}
+
+// ---- scalar renderer (tint_kernels.h; decisions: tint_policy.h) -----------------------------------------
+
+int sph_hip_render_scalars(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                           const sph_hip_scene_params* sp, const float* solid_albedo_rgb, int n_albedo,
+                           const sph_hip_tint_params* tp, const float* table_rgb, int width, int height, int flags,
+                           uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz, int32_t* first_inside,
+                           int32_t* solid_id, float* scalar)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_render_scalars";
+   if ((rc = sample_check(ctx, who))) return rc;
+   if (const char* why = tint_check(cam, rp, sp, solid_albedo_rgb, n_albedo, ctx->n_obst, ctx->n_scalars, tp, table_rgb,
+                                    width, height, flags))
+      return refuse(ctx, who, why);
+   const TintDraw tint = {*tp, table_rgb, scalar};
+   if (!sp) {
+      // fluid only: sph_hip_render's frame, solid_id -1 everywhere
+      if (solid_id) memset(solid_id, 0xff, sizeof(int32_t) * (size_t)width * height);
+      return render_frame(ctx, who, cam, rp, width, height, flags, rgba, depth, normal_xyz, velocity_xyz, first_inside,
+                          nullptr, &tint);
+   }
+   SceneDraw scene = {*sp, ctx->n_obst, solid_id};
+   if ((rc = scene_solids_now(ctx, scene, sp, solid_albedo_rgb, n_albedo))) return rc;
+   return render_frame(ctx, who, cam, rp, width, height, flags, rgba, depth, normal_xyz, velocity_xyz, first_inside,
+                       &scene, &tint);
 }
 
 void* sph_hip_stream(sph_hip_context* ctx) { return ctx ? (void*)ctx->stream : nullptr; }

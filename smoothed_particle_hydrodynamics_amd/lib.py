@@ -79,6 +79,13 @@ class SphSceneParams(C.Structure):
     _fields_ = [("albedo", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float)]
 
 
+class SphTintParams(C.Structure):
+    """Mirror of sph_hip_tint_params (include/sph_hip.h: scalar renderer): 24 bytes."""
+
+    _fields_ = [("channel", C.c_int32), ("mode", C.c_int32), ("lo", C.c_float), ("hi", C.c_float),
+                ("n_colors", C.c_int32), ("flags", C.c_int32)]
+
+
 from . import obstacles as _obstacles  # noqa: E402
 from .obstacles import (SphBody, SphBodyState, SphMotionKey, SphMotionPath, SphObstacle,  # noqa: E402
                         SphObstacleMotion)  # (mirrors of the C structs)
@@ -139,6 +146,10 @@ PROTOTYPES = {
     "sph_hip_render_scene": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), _P(SphSceneParams), C.c_void_p,
                                        C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_render_scalars": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), _P(SphSceneParams), C.c_void_p,
+                                         C.c_int, _P(SphTintParams), C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "sph_hip_set_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_get_obstacles": (C.c_int, [_ctx, _P(SphObstacle), C.c_int]),
     "sph_hip_set_obstacle_motion": (C.c_int, [_ctx, _P(SphObstacleMotion), C.c_int]),

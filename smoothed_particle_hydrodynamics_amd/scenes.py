@@ -550,3 +550,15 @@ def dam_break_dyed(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), nei
     values = np.zeros((n, 4), np.float32)
     values[:, 0] = (pos.reshape(-1, 3)[:, 0] < np.float32(0.5 * box[0] * fill[0])).astype(np.float32)
     return p, pos, vel, mass, values, np.zeros(4, np.float32)
+
+
+def dyed_cut_box(p):
+    """The marched box (lo, hi) that cuts the tank of dam_break_dyed and heated_floor at its mid-plane z = max_z / 2:
+    the renderer's default box - the domain grown by h - with its far side in z moved to the middle.  A camera
+    on the +z side then looks at a section through the fluid: renderScalars(..., box=dyed_cut_box(p), flat=True)."""
+    f = np.float32
+    h = f(p.h)
+    lo = np.full(3, f(0.0) - h, f)
+    hi = (np.array([p.max_x, p.max_y, p.max_z], f) + h).astype(f)
+    hi[2] = f(0.5) * f(p.max_z)
+    return lo, hi

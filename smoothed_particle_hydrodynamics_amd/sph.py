@@ -18,9 +18,10 @@ from . import gauges as _G
 from . import obstacles as _O
 from . import ports as _P
 from . import scalars as _S
-from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, TracerPath, Tracers, _ptr, default_params
+from . import colormaps as _CM
+from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, SphTintParams, TracerPath, Tracers, _ptr, default_params
 
-__all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
+__all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "ScalarRenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
 
 
 class Particle:
@@ -50,6 +51,15 @@ RENDER_VELOCITY = 1   # SPH_HIP_RENDER_VELOCITY (include/sph_hip.h)
 # the obstacle a pixel shows, -1 for none - from sph_hip_render_scene (render(..., solids=True)), else None
 RenderResult = collections.namedtuple("RenderResult", ["rgba", "depth", "normal", "velocity", "first_inside",
                                                        "solid_id"], defaults=[None])
+
+
+# sph_hip_render_scalars' frame: RenderResult's fields (solid_id None without solids) and scalar (H, W) float32,
+# the value a tinted pixel's colour stands for, 0 on every other pixel
+ScalarRenderResult = collections.namedtuple("ScalarRenderResult", RenderResult._fields + ("scalar",))
+
+TINT_SURFACE, TINT_COLUMN = 0, 1   # SPH_HIP_TINT_* (include/sph_hip.h)
+TINT_FLAT = 1
+TINT_MODES = {"surface": TINT_SURFACE, "column": TINT_COLUMN}
 
 
 class Camera:
@@ -647,32 +657,81 @@ class SPH(Context):
         (include/sph_hip.h: scene renderer) and fills RenderResult.solid_id: solid_albedo for every
         solid, or solid_colors, one RGB albedo per obstacle; solid_ambient / solid_diffuse default to the
         fluid's."""
-        rp = self.renderParams(iso, step, refine, grad_step, box, light, albedo, ambient, diffuse, background,
-                               max_samples)
-        W, H = int(width), int(height)
-        if W < 1 or H < 1:
-            raise ValueError("width and height must be positive")
-        rgba = np.zeros((H, W, 4), np.uint8)
-        depth = np.zeros((H, W), np.float32)
-        normal = np.zeros((H, W, 3), np.float32)
-        vel = np.zeros((H, W, 3), np.float32) if velocity else None
-        first = np.zeros((H, W), np.int32)
-        cam = camera.as_struct()
-        flags = RENDER_VELOCITY if velocity else 0
+        rp, W, H, out, cam, flags = self._frame_args(camera, width, height, iso, step, refine, grad_step, box, light,
+                                                     albedo, ambient, diffuse, background, velocity, max_samples)
+        rgba, depth, normal, vel, first = out
         if not solids:
             self.call("sph_hip_render", C.byref(cam), C.byref(rp), W, H, flags,
                       _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first))
             return RenderResult(rgba, depth, normal, vel, first)
-        sp = SphSceneParams()
-        sp.albedo[:] = [float(v) for v in solid_albedo]
-        sp.ambient = float(ambient if solid_ambient is None else solid_ambient)
-        sp.diffuse = float(diffuse if solid_diffuse is None else solid_diffuse)
-        colors = None if solid_colors is None else np.ascontiguousarray(solid_colors, np.float32).reshape(-1, 3)
+        sp, colors = self._scene_args(ambient, diffuse, solid_albedo, solid_colors, solid_ambient, solid_diffuse)
         solid_id = np.zeros((H, W), np.int32)
         self.call("sph_hip_render_scene", C.byref(cam), C.byref(rp), C.byref(sp), _ptr(colors),
                   0 if colors is None else colors.shape[0], W, H, flags,
                   _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first), _ptr(solid_id))
         return RenderResult(rgba, depth, normal, vel, first, solid_id)
+
+    def _frame_args(self, camera, width, height, iso, step, refine, grad_step, box, light, albedo, ambient, diffuse,
+                    background, velocity, max_samples):
+        """What every frame call is given: (params, W, H, (rgba, depth, normal, velocity or None, first_inside),
+        camera struct, flags)."""
+        rp = self.renderParams(iso, step, refine, grad_step, box, light, albedo, ambient, diffuse, background,
+                               max_samples)
+        W, H = int(width), int(height)
+        if W < 1 or H < 1:
+            raise ValueError("width and height must be positive")
+        out = (np.zeros((H, W, 4), np.uint8), np.zeros((H, W), np.float32), np.zeros((H, W, 3), np.float32),
+               np.zeros((H, W, 3), np.float32) if velocity else None, np.zeros((H, W), np.int32))
+        return rp, W, H, out, camera.as_struct(), RENDER_VELOCITY if velocity else 0
+
+    @staticmethod
+    def _scene_args(ambient, diffuse, solid_albedo, solid_colors, solid_ambient, solid_diffuse):
+        """(scene params, per-solid albedos (n, 3) or None) of a frame with the solids drawn"""
+        sp = SphSceneParams()
+        sp.albedo[:] = [float(v) for v in solid_albedo]
+        sp.ambient = float(ambient if solid_ambient is None else solid_ambient)
+        sp.diffuse = float(diffuse if solid_diffuse is None else solid_diffuse)
+        colors = None if solid_colors is None else np.ascontiguousarray(solid_colors, np.float32).reshape(-1, 3)
+        return sp, colors
+
+    # ---- scalar renderer (sph_hip_render_scalars) -----------------------------------------------------
+    def renderScalars(self, camera, width, height, iso, channel, value_range, colormap=None, mode="surface",
+                      flat=False, solids=False, step=None, refine=8, grad_step=None, box=None,
+                      light=(0.4, 0.8, 0.45), albedo=(0.25, 0.55, 0.9), ambient=0.2, diffuse=0.8,
+                      background=(0, 0, 0, 255), velocity=False, max_samples=1 << 16,
+                      solid_albedo=(0.72, 0.72, 0.72), solid_colors=None, solid_ambient=None, solid_diffuse=None):
+        """render(...)'s frame with every pixel that shows fluid coloured by carried channel `channel` on the
+        device (include/sph_hip.h: scalar renderer): a ScalarRenderResult, render's arrays plus .scalar.
+        value_range = (lo, hi) are the values mapped onto the first and last row of `colormap`, an (n, 3)
+        table of RGB in [0, 1] with 2 <= n <= 256 (colormaps.heat() by default).  mode "surface" colours a
+        pixel by the channel at its hit point - what sampleScalars returns there; "column" by the channel
+        integrated along the ray through the fluid from the surface to the end of `box` (with a channel
+        that is 1 everywhere: the fluid's thickness), which shows what lies under the surface.  Solids do
+        not clip a column.  flat=True leaves the Lambert factor out (for cut views, where rays enter inside
+        the fluid).  The other arguments are render's; the simulation is not changed by the call."""
+        if mode not in TINT_MODES:
+            raise ValueError("mode must be 'surface' or 'column'")
+        rp, W, H, out, cam, flags = self._frame_args(camera, width, height, iso, step, refine, grad_step, box, light,
+                                                     albedo, ambient, diffuse, background, velocity, max_samples)
+        rgba, depth, normal, vel, first = out
+        table = np.ascontiguousarray(_CM.heat() if colormap is None else colormap, np.float32)
+        if table.ndim != 2 or table.shape[1] != 3:
+            raise ValueError("colormap must be an (n, 3) table")
+        tp = SphTintParams()
+        tp.channel = int(channel)
+        tp.mode = TINT_MODES[mode]
+        tp.lo, tp.hi = float(value_range[0]), float(value_range[1])
+        tp.n_colors = table.shape[0]
+        tp.flags = TINT_FLAT if flat else 0
+        scalar = np.zeros((H, W), np.float32)
+        sp, colors, solid_id = None, None, None
+        if solids:
+            sp, colors = self._scene_args(ambient, diffuse, solid_albedo, solid_colors, solid_ambient, solid_diffuse)
+            solid_id = np.zeros((H, W), np.int32)
+        self.call("sph_hip_render_scalars", C.byref(cam), C.byref(rp), None if sp is None else C.byref(sp),
+                  _ptr(colors), 0 if colors is None else colors.shape[0], C.byref(tp), _ptr(table), W, H, flags,
+                  _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first), _ptr(solid_id), _ptr(scalar))
+        return ScalarRenderResult(rgba, depth, normal, vel, first, solid_id, scalar)
 
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
