@@ -1050,7 +1050,8 @@ int sph_hip_sample_pressure_lattice(sph_hip_context* ctx, const float origin[3],
  *   sources    at most SPH_HIP_MAX_SCALAR_SOURCES boxes.  After the update, in list order, a particle whose S_k
  *              position is STRICTLY inside [lo, hi] gets T_channel = value (HOLD: a heated plate, a dye
  *              injector) or T_channel = T_channel + value * dt (ADD: a heater of a given power).
- *   coupling   one way: no particle, density, acceleration, count or energy changes by a bit; no buoyancy.
+ *   coupling   one way: no particle, density, acceleration, count or energy changes by a bit - unless a
+ *              buoyancy is set (buoyancy, below), which is the coupling back and off by default.
  *              Queued steps stay queued.  A context without scalars launches what it launched before.
  *   not done   the stand-alone phase calls (sph_hip_compute_density .. sph_hip_integrate) do NOT advance the
  *              scalars.  REF and slab contexts are refused.  Ports are refused both ways - sph_hip_set_ports
@@ -1093,6 +1094,46 @@ int sph_hip_sample_scalars_points(sph_hip_context* ctx, int n, const float* xyz,
                                   int32_t* count);
 int sph_hip_sample_scalars_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
                                    const int32_t dims[3], float* channels4, float* density, int32_t* count);
+
+/* ---- buoyancy ----------------------------------------------------------------------------------- *
+ *
+ * The carried scalars change a particle's weight: warm water rises over a heated plate, a salinity front
+ * slumps.  No counterpart in the reference.  The operation-by-operation contract is in
+ * csrc/buoyancy_policy.h; all arithmetic is fp32, unfused, in the order written.
+ *   excess     for particle i of a step's state S_k, with T_i its channels as they stood BEFORE that step's
+ *              scalar update: s = 0; for c = 0 .. 3: s = s + beta[c] * (T_i,c - reference[c]).
+ *   force      b = (-s) * gravity per component: with gravity pointing down a positive beta lifts warm fluid,
+ *              a negative one (a salinity) sinks it.  `gravity` is the setting's own vector, not read from the
+ *              parameters: it says which way is down, whatever apply_gravity is.
+ *   guard      a particle with s == 0, or with s not finite (a diffusing channel can go NaN next to the spray,
+ *              see stability above), is left alone: not a bit of it changes, -0.0f included.
+ *   a step     behind the step's acceleration pass and before its integrate: a' = clamp(a + b), the
+ *              acceleration pass's own cfl_limit rule applied again, and v' = v + b * dt; the step's usual
+ *              integrate then runs from (x, v', a').  The acceleration read back after the step is a'.
+ *   two terms  the integrate gives a particle's acceleration half a time step of velocity (vh = v + a*dt/2) and
+ *              gravity a whole one more (nv = vh + g*dt).  b enters both ways, so that a particle's weight
+ *              changes by exactly the factor 1 - s in velocity: with s = 1 and a = gravity, a' = 0 exactly and
+ *              nv = (v - g*dt) + g*dt.  The position sees b*dt one step early, an offset of the size of one
+ *              step's velocity change, constant over a run.
+ *   route      a buoyant context gives up the fused integrate (it keeps the prehash) and launches one more
+ *              kernel per step.  Obstacles, motions, paths, bodies, load recordings, gauges and tracers work
+ *              beside it unchanged.  A context without buoyancy enqueues exactly what it always did.
+ *   not done   the stand-alone phase calls (sph_hip_compute_density .. sph_hip_integrate) do NOT apply
+ *              buoyancy, as they do not advance the scalars.
+ * sph_hip_set_buoyancy sets it for the steps enqueued from now on; it does not wait, and steps already queued
+ * keep the setting they were enqueued with.  b == NULL or a beta of four zeros switches buoyancy off.
+ * SPH_HIP_ERR_INVALID, the previous setting kept, for a context that carries no scalars, a beta, a reference
+ * or a gravity that is not finite.  Switching the scalars off, and a new sph_hip_upload, drop the setting.
+ * sph_hip_get_buoyancy returns 1 and copies the setting, or returns 0 when none is set.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no existing
+ * prototype changed. */
+typedef struct sph_hip_buoyancy {   /* field order is ABI: 44 bytes */
+   float beta[4];        /* per channel: weight change per unit of (T - reference) */
+   float reference[4];   /* per channel: the value at which a particle has its own weight */
+   float gravity[3];     /* the acceleration that -s scales */
+} sph_hip_buoyancy;
+int sph_hip_set_buoyancy(sph_hip_context* ctx, const sph_hip_buoyancy* b);
+int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out);
 
 /* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
  *

@@ -27,6 +27,7 @@
 #include "gauge_kernels.h"
 #include "pressure_kernels.h"
 #include "scalar_kernels.h"
+#include "buoyancy_kernels.h"
 #include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
@@ -421,6 +422,10 @@ struct sph_hip_context {
    int n_scalar_sources = 0;
    sph_hip_scalar_source scalar_sources[SPH_HIP_MAX_SCALAR_SOURCES];
    int scalar_force_rows = 0;      // SPH_HIP_SCALAR_ROWS=1, read at creation: every workgroup of the pass walks the rows
+
+   // buoyancy (sph_hip_set_buoyancy): the setting the next enqueued steps take by value; dropped with the scalars
+   int have_buoyancy = 0;
+   sph_hip_buoyancy buoyancy = {};
 
    // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
    // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the

@@ -903,6 +903,19 @@ int launch_scalars(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- buoyancy (buoyancy_kernels.h; contract: buoyancy_policy.h; decision: launch_policy.h) ------------------
+// Behind the step's acceleration pass, in front of its integrate: acc and velp of the sorted state S_k, with the
+// channels launch_scalars staged earlier in this step.  The setting travels by value: a later setter does not
+// reach the steps already queued.  Nothing synchronises.
+int launch_buoyancy(sph_hip_context* ctx)
+{
+   const sph_hip_params& p = ctx->prm;
+   hipLaunchKernelGGL(k_buoyancy_apply, dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream, ctx->scalar_Ts, ctx->meta,
+                      ctx->buoyancy, p.time_step, p.cfl_limit, p.cfl_limit2, ctx->acc, ctx->velp[ctx->cur]);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
 // buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
 // (prehashed: 1 whole grid, 2 a slab's owned entries).
@@ -1000,9 +1013,12 @@ int step_impl(sph_hip_context* ctx, bool timed)
    const bool hash_too = ctx->mode == SPH_HIP_MODE_FULL && !ctx->had_exchange && ctx->plane_lo == 0 &&
                          ctx->plane_hi == ctx->grid.nz_global &&
                          !ports_no_prehash(ctx->no_prehash != 0, ctx->n_emit, ctx->n_sink);
+   // buoyancy: one kernel between the acceleration pass and the integrate, so the step gives up the fused integrate
+   const bool buoyant = step_launches_buoyancy(ctx->have_buoyancy != 0, ctx->n_scalars, ctx->n);
    const bool fused = fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
-                                     loads_pending(ctx));
+                                     loads_pending(ctx), buoyant);
    if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;
+   if (buoyant && (rc = launch_buoyancy(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;
    if (fused) fused_step_done(ctx, 1);
    else if ((rc = launch_integrate(ctx, hash_too))) return rc;

@@ -258,11 +258,12 @@ inline PlaneRanges plane_ranges(int plane_lo, int plane_hi, int z0, int nz, int 
 // exchanged, prehash allowed), the tiled kernels, particles to move, no SPH_HIP_NO_FUSED_INTEGRATE,
 // and no static obstacles - their response runs in k_integrate_obst, the fused kernels stay as tuned.
 // record_loads: the step fills a row of a load recording (sph_hip_record_loads), which only
-// k_integrate_loads does.
+// k_integrate_loads does.  buoyancy: the step launches k_buoyancy_apply (step_launches_buoyancy), which stands
+// between the acceleration pass and the integrate; such a step keeps the prehash, in k_integrate<HASH>.
 inline bool fuse_integrate(bool hash_too, bool tiled, int n, bool no_fused_integrate, int n_obstacles,
-                           bool record_loads = false)
+                           bool record_loads = false, bool buoyancy = false)
 {
-   return hash_too && tiled && n > 0 && !no_fused_integrate && n_obstacles == 0 && !record_loads;
+   return hash_too && tiled && n > 0 && !no_fused_integrate && n_obstacles == 0 && !record_loads && !buoyancy;
 }
 
 // Whether a slab's early-exchange step (sph_hip_slab_step_begin / _end) integrates, hashes and packs
@@ -358,6 +359,14 @@ inline bool step_reads_pressure(int row, int n_pressure) { return row >= 0 && ga
 // acceleration pass: the context carries scalars and has particles.  A context without scalars launches
 // what it always launched.
 inline bool step_launches_scalars(int n_scalars, int n) { return n_scalars > 0 && n > 0; }
+
+// Whether a step launches k_buoyancy_apply (buoyancy_policy.h) between its acceleration pass and its integrate: a
+// buoyancy is set, and the step has staged the scalars it reads (step_launches_scalars).  Such a step gives up the
+// fused integrate (fuse_integrate).  A context without buoyancy launches what it always launched.
+inline bool step_launches_buoyancy(bool have_buoyancy, int n_scalars, int n)
+{
+   return have_buoyancy && step_launches_scalars(n_scalars, n);
+}
 
 // Whether a frame launches the tint pass (k_scalars_stage once, then k_tint_surface or k_tint_column per row
 // chunk: tint_kernels.h): the caller is sph_hip_render_scalars and a particle is resident.  Without a particle

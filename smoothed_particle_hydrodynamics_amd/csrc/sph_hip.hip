@@ -382,6 +382,7 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    // carried scalars belong to the rows of the upload they were set for: dropped with their sources
    ctx->n_scalars = 0;
    ctx->n_scalar_sources = 0;
+   ctx->have_buoyancy = 0;   // (buoyancy reads the scalars: it goes with them)
    ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
    ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
    ports_mass_rule(ctx, n == 0);
@@ -1994,6 +1995,7 @@ int sph_hip_set_scalars(sph_hip_context* ctx, int n, const float* values4, const
    if (!values4 || n == 0) {
       ctx->n_scalars = 0;
       ctx->n_scalar_sources = 0;
+      ctx->have_buoyancy = 0;
       return SPH_HIP_OK;
    }
    if (!ctx->scalar_T) {
@@ -2051,6 +2053,29 @@ int sph_hip_get_scalar_sources(sph_hip_context* ctx, sph_hip_scalar_source* out,
    const int m = ctx->n_scalar_sources < capacity ? ctx->n_scalar_sources : capacity;
    for (int q = 0; q < m; q++) out[q] = ctx->scalar_sources[q];
    return ctx->n_scalar_sources;
+}
+
+// ---- buoyancy (buoyancy_kernels.h; contract and check: buoyancy_policy.h) -------------------------------
+
+int sph_hip_set_buoyancy(sph_hip_context* ctx, const sph_hip_buoyancy* b)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = buoyancy_set_check(b, ctx->n_scalars)) return refuse(ctx, "sph_hip_set_buoyancy", why);
+   // (a step takes the setting by value: the steps already queued keep theirs)
+   ctx->have_buoyancy = buoyancy_is_off(b) ? 0 : 1;
+   if (ctx->have_buoyancy) ctx->buoyancy = *b;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!ctx->have_buoyancy) return 0;
+   if (!out) return refuse(ctx, "sph_hip_get_buoyancy", "null output");
+   *out = ctx->buoyancy;
+   return 1;
 }
 
 // The sampler's calls with the channel walk: behind the cell build the scalars are staged by sorted slot

@@ -91,7 +91,7 @@ from .obstacles import (SphBody, SphBodyState, SphMotionKey, SphMotionPath, SphO
                         SphObstacleMotion)  # (mirrors of the C structs)
 from .gauges import GaugeReadings, GaugeRecord, SphGauge  # noqa: E402,F401
 from .ports import PortTotals, SphEmitter, SphSink  # noqa: E402,F401
-from .scalars import SphScalarSource  # noqa: E402,F401
+from .scalars import SphBuoyancy, SphScalarSource  # noqa: E402,F401
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -184,6 +184,8 @@ PROTOTYPES = {
     "sph_hip_sample_scalars_points": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_sample_scalars_lattice": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3), _P(C.c_int32 * 3),
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "sph_hip_set_buoyancy": (C.c_int, [_ctx, _P(SphBuoyancy)]),
+    "sph_hip_get_buoyancy": (C.c_int, [_ctx, _P(SphBuoyancy)]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -3,7 +3,8 @@ concentration, a salinity - that move with the fluid and diffuse between neighbo
 
 SPH.setScalars gives every particle its values and every channel its diffusivity, SPH.getScalars reads them back
 in particle order, SPH.setScalarSources takes a list of ScalarSource, SPH.sampleScalars and
-SPH.sampleScalarLattice interpolate the channels at probes.  The arithmetic of a step is in csrc/scalar_policy.h."""
+SPH.sampleScalarLattice interpolate the channels at probes.  The arithmetic of a step is in csrc/scalar_policy.h.
+SPH.setBuoyancy takes a Buoyancy: the channels then change a particle's weight (csrc/buoyancy_policy.h)."""
 import ctypes as C
 
 import numpy as np
@@ -78,6 +79,67 @@ def as_array(sources):
     for i, q in enumerate(sources):
         arr[i] = q if isinstance(q, SphScalarSource) else q.to_struct()
     return arr, n
+
+
+class SphBuoyancy(C.Structure):
+    """Mirror of sph_hip_buoyancy (include/sph_hip.h): 44 bytes."""
+
+    _fields_ = [("beta", C.c_float * 4), ("reference", C.c_float * 4), ("gravity", C.c_float * 3)]
+
+
+def _pad4(v, what):
+    v = np.asarray(v, np.float32).reshape(-1)
+    if v.size > CHANNELS:
+        raise ValueError("at most %d %s" % (CHANNELS, what))
+    out = np.zeros(CHANNELS, np.float32)
+    out[:v.size] = v
+    return tuple(float(x) for x in out)
+
+
+class Buoyancy:
+    """The carried scalars change a particle's weight (include/sph_hip.h: buoyancy): with the excess
+    s = sum over the channels of beta[c] * (T_c - reference[c]) a particle takes the acceleration (-s) * gravity
+    on top of its own.  `beta` and `reference` are one value (channel 0) or up to four, padded with zeros;
+    gravity=None takes the context's params.gravity when the setting is handed to SPH.setBuoyancy.  A positive
+    beta lifts warm fluid, a negative one - a salinity - sinks it."""
+
+    __slots__ = ("beta", "reference", "gravity")
+
+    def __init__(self, beta, reference=(0.0, 0.0, 0.0, 0.0), gravity=None):
+        self.beta = _pad4(beta, "betas")
+        self.reference = _pad4(reference, "references")
+        self.gravity = None if gravity is None else _f3(gravity)
+
+    def _key(self):
+        return (self.beta, self.reference, self.gravity)
+
+    def __eq__(self, other):
+        return isinstance(other, Buoyancy) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return "Buoyancy(beta=%r, reference=%r, gravity=%r)" % self._key()
+
+    def with_gravity(self, gravity):
+        """This setting with `gravity` where it has none of its own."""
+        return self if self.gravity is not None else Buoyancy(self.beta, self.reference, gravity)
+
+    def to_struct(self):
+        if self.gravity is None:
+            raise ValueError("a Buoyancy without a gravity: give one, or hand it to SPH.setBuoyancy")
+        b = SphBuoyancy()
+        for c in range(CHANNELS):
+            b.beta[c] = self.beta[c]
+            b.reference[c] = self.reference[c]
+        for a in range(3):
+            b.gravity[a] = self.gravity[a]
+        return b
+
+
+def buoyancy_from_struct(b):
+    return Buoyancy(tuple(b.beta), tuple(b.reference), tuple(b.gravity))
 
 
 def pad_values(values, n=None):

@@ -552,6 +552,34 @@ def dam_break_dyed(n, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), nei
     return p, pos, vel, mass, values, np.zeros(4, np.float32)
 
 
+def thermal_plume(n, patch=0.3, beta=0.2, depth=0.3, hot=1.0, box=(1.0, 1.0, 1.0), neighbors=32.0, seed=42,
+                  gravity=-9.81):
+    """heated_floor's still tank with the HOLD slab shrunk to a square patch in the middle of the floor, `patch` of
+    the tank's width and length on a side, and a Buoyancy on channel 0: water at `hot` is lighter by the fraction
+    beta * hot and rises over the patch.  Returns heated_floor's tuple with the Buoyancy appended: setParticles,
+    setScalars, setScalarSources, then setBuoyancy."""
+    from .scalars import Buoyancy, ScalarSource
+    p, pos, vel, mass, values, kappa, _ = heated_floor(n, depth, hot, box, neighbors, seed, gravity)
+    h = float(p.h)
+    mx, mz = 0.5 * float(p.max_x), 0.5 * float(p.max_z)
+    rx, rz = 0.5 * patch * float(p.max_x), 0.5 * patch * float(p.max_z)
+    plate = ScalarSource.hold((mx - rx, -h, mz - rz), (mx + rx, h, mz + rz), 0, hot)
+    return p, pos, vel, mass, values, kappa, [plate], Buoyancy(beta, 0.0, tuple(p.gravity))
+
+
+def lock_exchange(n, beta=-0.2, depth=0.3, box=(1.0, 1.0, 1.0), neighbors=32.0, seed=42, gravity=-9.81):
+    """Still water `depth` of the box deep, gravity along -y and the walls on, with the lock just opened: channel 0
+    is a salinity of 1 in the half with x below the tank's middle and 0 in the other, carried without diffusion
+    (kappa = 0), and a Buoyancy with a negative beta - salt water is heavier by the fraction -beta and slumps under
+    the fresh.  Returns heated_floor's tuple (no sources) with the Buoyancy appended: setParticles, setScalars,
+    then setBuoyancy."""
+    from .scalars import Buoyancy
+    p, pos, vel, mass, values, kappa, _ = heated_floor(n, depth, 1.0, box, neighbors, seed, gravity)
+    kappa[:] = 0.0
+    values[:, 0] = (pos.reshape(-1, 3)[:, 0] < np.float32(0.5) * np.float32(p.max_x)).astype(np.float32)
+    return p, pos, vel, mass, values, kappa, [], Buoyancy(beta, 0.0, tuple(p.gravity))
+
+
 def dyed_cut_box(p):
     """The marched box (lo, hi) that cuts the tank of dam_break_dyed and heated_floor at its mid-plane z = max_z / 2:
     the renderer's default box - the domain grown by h - with its far side in z moved to the middle.  A camera

@@ -577,6 +577,24 @@ class SPH(Context):
         n = self.call("sph_hip_get_scalar_sources", arr, _S.MAX_SOURCES)
         return [_S.from_struct(arr[i]) for i in range(n)]
 
+    # ---- buoyancy (sph_hip_set_buoyancy) ----------------------------------------------------------
+    def setBuoyancy(self, buoyancy):
+        """Let the carried scalars change a particle's weight from the next enqueued step on
+        (scalars.Buoyancy; include/sph_hip.h: buoyancy): a particle with the excess s = sum of beta[c] *
+        (T_c - reference[c]) takes (-s) * gravity on top of its own acceleration.  A Buoyancy without a gravity
+        of its own takes the context's params.gravity as it stands now.  None, or a beta of zeros, switches it
+        off.  Needs setScalars first; a new setParticles, and setScalars(None), drop it."""
+        if buoyancy is None:
+            self.call("sph_hip_set_buoyancy", None)
+            return
+        b = buoyancy.with_gravity(self.getGravity()).to_struct()
+        self.call("sph_hip_set_buoyancy", C.byref(b))
+
+    def getBuoyancy(self):
+        """The Buoyancy in force, or None."""
+        b = _S.SphBuoyancy()
+        return _S.buoyancy_from_struct(b) if self.call("sph_hip_get_buoyancy", C.byref(b)) == 1 else None
+
     def sampleScalars(self, points):
         """The carried scalars of the current state at `points` ((n, 3) float32): (channels[n, 4], density[n],
         count[n]) - the Shepard-normalised sums over the sampler's members, 0 where there are none.  The
