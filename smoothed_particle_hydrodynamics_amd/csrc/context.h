@@ -283,6 +283,7 @@ struct sph_hip_context {
    Scratch<float> sample_buf;
    int sample_route = 0;           // SAMPLE_ROUTE_*: SPH_HIP_SAMPLE_UNTILED=1 / SPH_HIP_SAMPLE_TILED=1 (tests, A/B runs)
    int sample_lds_set = 0;         // the tiled lattice kernels may take their dynamic LDS on this device
+   int sample_chunk_forced = 0;    // SPH_HIP_SAMPLE_CHUNK=n (tests): probes per chunk, clamped (sample_chunk_forced)
 
    // iso-surface extractor (sph_hip_extract_surface): one slab's scratch, the running totals per
    // slab, and the kept mesh (grown on demand, kept until the next extraction or destroy)
@@ -534,6 +535,7 @@ int create_impl(sph_hip_context** out, const sph_hip_params* params, int capacit
    ctx->sample_route = getenv_flag("SPH_HIP_SAMPLE_UNTILED") ? SAMPLE_ROUTE_UNTILED
                        : getenv_flag("SPH_HIP_SAMPLE_TILED")  ? SAMPLE_ROUTE_TILED
                                                               : SAMPLE_ROUTE_DEFAULT;
+   if (const char* v = getenv("SPH_HIP_SAMPLE_CHUNK")) ctx->sample_chunk_forced = sample_chunk_forced(atoll(v));
    if (const char* v = getenv("SPH_HIP_SURFACE_PLANES")) ctx->surf_planes_forced = atoi(v) > 0 ? atoi(v) : 0;
    ctx->render_noskip = getenv_flag("SPH_HIP_RENDER_NOSKIP");
    ctx->tracer_sort_switch = tracer_sort_switch(getenv("SPH_HIP_TRACER_SORT"));

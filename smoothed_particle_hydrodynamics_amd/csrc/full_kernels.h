@@ -37,6 +37,22 @@ __device__ __forceinline__ void row_ranges(const CellGrid& g, const uint32_t* __
    }
 }
 
+// Begin and end of row `row` (0..8, the index of a loop that is not unrolled), by a chain of selects
+// over values: a dynamic index or a pointer into r would move RowRanges from registers to scratch
+// memory.  Every element is read into a local before the selects - reading them inside the arms, through
+// the reference, compiles to other (longer) code than the chains this replaced.
+__device__ __forceinline__ void row_range(const RowRanges& r, int row, uint32_t& b, uint32_t& e)
+{
+   const uint32_t s0 = r.s[0], s1 = r.s[1], s2 = r.s[2], s3 = r.s[3], s4 = r.s[4], s5 = r.s[5], s6 = r.s[6], s7 = r.s[7],
+                  s8 = r.s[8];
+   const uint32_t e0 = r.e[0], e1 = r.e[1], e2 = r.e[2], e3 = r.e[3], e4 = r.e[4], e5 = r.e[5], e6 = r.e[6], e7 = r.e[7],
+                  e8 = r.e[8];
+   b = row == 0 ? s0 : row == 1 ? s1 : row == 2 ? s2 : row == 3 ? s3 : row == 4 ? s4 : row == 5 ? s5 : row == 6 ? s6
+     : row == 7 ? s7 : s8;
+   e = row == 0 ? e0 : row == 1 ? e1 : row == 2 ? e2 : row == 3 ? e3 : row == 4 ? e4 : row == 5 ? e5 : row == 6 ? e6
+     : row == 7 ? e7 : e8;
+}
+
 // ---- density, untiled: one thread per particle, candidates read through L1/L2 -------------------
 // Used for workgroups whose LDS tile or neighbour lists would overflow (called inline from the
 // tiled kernels of full_tiled.h), for SPH_HIP_UNTILED=1, and as an independent cross-check.
@@ -58,10 +74,8 @@ __device__ __forceinline__ void density_untiled(int p, const float4* __restrict_
    int count = 0;
 #pragma unroll 1
    for (int row = 0; row < 9; row++) {
-      const uint32_t s = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
+      uint32_t s, e;
+      row_range(r, row, s, e);
       for (uint32_t q = s; q < e; q++) {
          if (q == (uint32_t)p) continue;
          const float4 pj = posm[q];
@@ -141,10 +155,8 @@ __device__ __forceinline__ void accel_untiled(int p, const float4* __restrict__ 
    if (FAST) first_v = visc_first(ncount[p], s.visc_scale);
 #pragma unroll 1
    for (int row = 0; row < 9; row++) {
-      const uint32_t b = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
+      uint32_t b, e;
+      row_range(r, row, b, e);
       for (uint32_t q = b; q < e; q++) {
          if (q == (uint32_t)p) continue;
          const float4 pj = posm[q];

@@ -46,7 +46,7 @@ k_gauges_read(const sph_hip_gauge* __restrict__ gauges, int n_gauges, const floa
       float px, py, pz;
       gauge_probe(G, q, px, py, pz);
       SampleSum<true> s;
-      if (has && have_particles) sample_walk<UNIT_SCALE, true>(px, py, pz, posm, velp, cell_start, g, k, s);
+      if (has && have_particles) sample_walk<UNIT_SCALE>(px, py, pz, posm, velp, cell_start, g, k, s);
       l_rho = s.rho;
       l_vx = s.vx;
       l_vy = s.vy;

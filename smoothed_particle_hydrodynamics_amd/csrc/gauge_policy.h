@@ -33,7 +33,7 @@
 //   P_j      = (rho_j - rho0) * stiffness: gauge_particle_pressure, the first line of neighbor_terms, with the
 //            context's constants at the time of the call or at the time the step is enqueued; not clamped
 //   pwalk(S, p): the sampler's members and terms t_j at p (a particle at p included) and, beside rho and count,
-//            pw = sum of t_j * P_j in canonical order (sample_walk_pressure: pressure_kernels.h)
+//            pw = sum of t_j * P_j in canonical order (sample_walk with PressureSum: pressure_kernels.h)
 //   pressure = rho > 0 ? pw / rho : 0: gauge_pressure_quotient, the Shepard normalisation of the velocity.  A
 //            probe at a wall has half its support empty; the quotient is what makes that reading a pressure.
 //   PRESSURE        one probe at the origin: v = {pressure, rho, pw, 0}, n = count, k = 0

@@ -1,12 +1,13 @@
 // Pressure readings (include/sph_hip.h: pressure readings; the contract and every decision: gauge_policy.h):
-// the particle densities of the current sorted state, the pressure form of the sampler's walk, the point and
-// lattice samplers of the pressure and the wave that reads the pressure gauges.
+// the particle densities of the current sorted state, the pressure sums of the sampler's walk (with them the
+// sampler's own kernels are the point and lattice samplers of the pressure: sample_kernels.h) and the wave
+// that reads the pressure gauges.
 //
 // k_particle_density is density_untiled's walk (full_kernels.h) writing the density alone, into a buffer of
-// the context's own: none of rho, velB, auxc, ncount, the lists or the tile statistics is touched.  The
-// pressure walk is sample_walk's (sample_kernels.h) with one more load per MEMBER, the member's density; it
-// forms P_j from it and adds t_j * P_j.  No kernel here uses LDS, and no local array goes to a function by
-// pointer (RowRanges is selected from, as in sample_walk).
+// the context's own: none of rho, velB, auxc, ncount, the lists or the tile statistics is touched.  A
+// pressure probe is sample_walk (sample_kernels.h) with PressureSum: one more load per MEMBER, the member's
+// density; it forms P_j from it and adds t_j * P_j.  No kernel here uses LDS, and no local array goes to a
+// function by pointer (RowRanges is selected from: row_range, full_kernels.h).
 #pragma once
 
 #include "cell_build.h"
@@ -29,10 +30,8 @@ k_particle_density(const float4* __restrict__ posm, const uint32_t* __restrict__
    float density = 0.0f;
 #pragma unroll 1
    for (int row = 0; row < 9; row++) {
-      const uint32_t s = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
+      uint32_t s, e;
+      row_range(r, row, s, e);
       for (uint32_t q = s; q < e; q++) {
          if (q == (uint32_t)p) continue;
          const float4 pj = posm[q];
@@ -48,16 +47,30 @@ k_particle_density(const float4* __restrict__ posm, const uint32_t* __restrict__
    rho_out[p] = density;
 }
 
-// ---- the pressure form of the sampler's walk ---------------------------------------------------------------
+// ---- the pressure sums of the sampler's walk ---------------------------------------------------------------
 // accumulator of one probe: the sampler's rho and count, and pw = sum of t_j * P_j
 struct PressureSum {
    float rho = 0.0f, pw = 0.0f;
    int count = 0;
 
+   using Payload = float;   // prho: the density of sorted particle q
+   struct Out {
+      float* prs;
+      float* rho;
+      int32_t* cnt;
+   };
+
+   template <bool UNIT_SCALE>
+   __device__ __forceinline__ void member(const PairConsts& k, float d2, float m, const float* __restrict__ prho,
+                                          uint32_t q)
+   {
+      add<UNIT_SCALE>(k, d2, m, prho[q]);
+   }
+
    template <bool UNIT_SCALE>
    __device__ __forceinline__ void add(const PairConsts& k, float d2, float m, float rho_j)
    {
-      float d = sqrt_rn(d2);   // (SampleSum::add)
+      float d = sqrt_rn(d2);   // (as SampleSum::add: sample_kernels.h)
       if (!UNIT_SCALE) d *= k.sim_scale;
       const float t = density_term<UNIT_SCALE>(k, m, d);
       rho += t;
@@ -65,78 +78,13 @@ struct PressureSum {
       count++;
    }
 
-   __device__ __forceinline__ void store(int o, float* __restrict__ prs_out, float* __restrict__ rho_out,
-                                         int32_t* __restrict__ cnt_out) const
+   __device__ __forceinline__ void store(int o, const Out& out) const
    {
-      prs_out[o] = gauge_pressure_quotient(pw, rho);
-      rho_out[o] = rho;
-      cnt_out[o] = count;
+      out.prs[o] = gauge_pressure_quotient(pw, rho);
+      out.rho[o] = rho;
+      out.cnt[o] = count;
    }
 };
-
-// one probe, candidates read from global memory; prho[q]: the density of sorted particle q, read for members
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void sample_walk_pressure(float px, float py, float pz, const float4* __restrict__ posm,
-                                                     const float* __restrict__ prho,
-                                                     const uint32_t* __restrict__ cell_start, const CellGrid& g,
-                                                     const PairConsts& k, PressureSum& s)
-{
-   int cx, cy, cz;
-   probe_cell(g, px, py, pz, cx, cy, cz);
-   RowRanges r;
-   row_ranges(g, cell_start, cx, cy, cz, r);
-#pragma unroll 1
-   for (int row = 0; row < 9; row++) {
-      const uint32_t b = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
-      for (uint32_t q = b; q < e; q++) {
-         const float4 pj = posm[q];
-         float dx, dy, dz;
-         const float d2 = dist2(px, py, pz, pj.x, pj.y, pj.z, dx, dy, dz);
-         if (d2 < k.h2) s.template add<UNIT_SCALE>(k, d2, pj.w, prho[q]);
-      }
-   }
-}
-
-// ---- point probes: one lane per probe ----------------------------------------------------------------------
-template <bool UNIT_SCALE>
-__global__ void __launch_bounds__(256)
-k_sample_pressure_points(const float* __restrict__ xyz, int n, const float4* __restrict__ posm,
-                         const float* __restrict__ prho, const uint32_t* __restrict__ cell_start, CellGrid g,
-                         PairConsts k, float* __restrict__ prs_out, float* __restrict__ rho_out,
-                         int32_t* __restrict__ cnt_out)
-{
-   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-   if (p >= n) return;
-   PressureSum s;
-   sample_walk_pressure<UNIT_SCALE>(xyz[3 * p + 0], xyz[3 * p + 1], xyz[3 * p + 2], posm, prho, cell_start, g, k, s);
-   s.store(p, prs_out, rho_out, cnt_out);
-}
-
-// ---- lattice probes: one workgroup per brick, every lane walks per probe (k_sample_lattice<.., false>) -----
-template <bool UNIT_SCALE>
-__global__ void __launch_bounds__(SAMPLE_THREADS)
-k_sample_pressure_lattice(SampleLattice L, const float4* __restrict__ posm, const float* __restrict__ prho,
-                          const uint32_t* __restrict__ cell_start, CellGrid g, PairConsts k,
-                          float* __restrict__ prs_out, float* __restrict__ rho_out, int32_t* __restrict__ cnt_out)
-{
-   const int t = threadIdx.x;
-   const int b = blockIdx.x;
-   const int bx = b % L.bricks_x, by = (b / L.bricks_x) % L.bricks_y, bz = b / (L.bricks_x * L.bricks_y);
-   const int il = bx * L.bx + t % L.bx;
-   const int jl = by * L.by + (t / L.bx) % L.by;
-   const int kl = bz * L.bz + t / (L.bx * L.by);
-   if (!(il < L.ex && jl < L.ey && kl < L.ez)) return;
-   const float px = L.ox + (float)(L.i0 + il) * L.sx;
-   const float py = L.oy + (float)(L.j0 + jl) * L.sy;
-   const float pz = L.oz + (float)(L.k0 + kl) * L.sz;
-   const int o = (kl * L.ey + jl) * L.ex + il;
-   PressureSum s;
-   sample_walk_pressure<UNIT_SCALE>(px, py, pz, posm, prho, cell_start, g, k, s);
-   s.store(o, prs_out, rho_out, cnt_out);
-}
 
 // ---- the pressure gauges: one wave per gauge, as k_gauges_read ---------------------------------------------
 // prho: the densities of the state in sorted order - the density pass's own inside a step, the context's
@@ -167,7 +115,7 @@ k_gauges_pressure(const sph_hip_gauge* __restrict__ gauges, int n_gauges, const 
       float px, py, pz;
       gauge_probe(G, q, px, py, pz);
       PressureSum s;
-      if (has && have_particles) sample_walk_pressure<UNIT_SCALE>(px, py, pz, posm, prho, cell_start, g, k, s);
+      if (has && have_particles) sample_walk<UNIT_SCALE>(px, py, pz, posm, prho, cell_start, g, k, s);
       l_rho = s.rho;
       l_pw = s.pw;
       l_count = s.count;

@@ -57,7 +57,7 @@ __device__ __forceinline__ float render_field(float x, float y, float z, const f
       if (!occ[(cz * g.ny + cy) * g.nx + cx]) return 0.0f;
    }
    SampleSum<false> s;
-   sample_walk<UNIT_SCALE, false>(x, y, z, posm, nullptr, cell_start, g, k, s);
+   sample_walk<UNIT_SCALE>(x, y, z, posm, nullptr, cell_start, g, k, s);
    return s.rho;
 }
 
@@ -218,7 +218,7 @@ k_render_shade(RenderFrame F, const float4* __restrict__ posm, const float4* __r
       probe_cell(g, p[0], p[1], p[2], cx, cy, cz);
       if (!SKIP || occ[(cz * g.ny + cy) * g.nx + cx]) {
          SampleSum<true> s;
-         sample_walk<UNIT_SCALE, true>(p[0], p[1], p[2], posm, velp, cell_start, g, k, s);
+         sample_walk<UNIT_SCALE>(p[0], p[1], p[2], posm, velp, cell_start, g, k, s);
          if (s.rho > 0.0f) {
             v[0] = s.vx / s.rho;
             v[1] = s.vy / s.rho;

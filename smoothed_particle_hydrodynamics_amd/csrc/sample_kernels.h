@@ -1,6 +1,8 @@
 // Field sampler: SPH interpolation of the current state at probe points (sph_hip_sample_points)
 // and on regular lattices (sph_hip_sample_lattice), over the cell-sorted FULL-mode state that a
-// cell build has just produced.
+// cell build has just produced.  The walk of a probe and the per-probe kernels take the accumulator
+// as a parameter: with PressureSum (pressure_kernels.h) and ScalarSum (scalar_kernels.h) they are the
+// samplers of the pressure and of the carried scalars.
 //
 // What a probe at x computes (include/sph_hip.h promises it, tests/test_gpu_sample.py pins it):
 //   members   every live particle j with d2 = (dx*dx + dy*dy) + dz*dz < h2 in fp32 (dist2), the
@@ -18,8 +20,8 @@
 // member, so such a probe gives density 0, count 0 and velocity 0.
 //
 // The walk of one probe is density_untiled's (full_kernels.h) without the self-skip: 9 cell rows
-// (cz-1..cz+1, cy-1..cy+1), each the contiguous sorted range of cells cx-1..cx+1.  The lattice
-// kernel's tiled route stages those rows once per brick of points (sample_policy.h) in LDS and
+// (cz-1..cz+1, cy-1..cy+1), each the contiguous sorted range of cells cx-1..cx+1.  The tiled lattice
+// kernel stages those rows once per brick of points (sample_policy.h) in LDS and
 // every lane walks its own 9 row segments from there, in the same order: the same bits.
 #pragma once
 
@@ -36,11 +38,30 @@ struct SampleLattice {
    int bricks_x, bricks_y;   // bricks per chunk along x and y
 };
 
-// accumulator of one probe
+// Accumulator of one probe.  What sample_walk and the per-probe kernels ask of an accumulator (this one,
+// PressureSum: pressure_kernels.h, ScalarSum: scalar_kernels.h): Payload, the per-particle array in sorted
+// order that a member contributes besides its position and mass; member(), which loads payload[q] - for
+// members only, behind the d2 < h2 test - and adds the term; Out, the output arrays, and store().
 template <bool VEL>
 struct SampleSum {
    float rho = 0.0f, vx = 0.0f, vy = 0.0f, vz = 0.0f;
    int count = 0;
+
+   using Payload = float4;   // velp: the velocities (not read, and may be null, unless VEL)
+   struct Out {
+      float* rho;
+      float* vel;
+      int32_t* cnt;
+   };
+
+   template <bool UNIT_SCALE>
+   __device__ __forceinline__ void member(const PairConsts& k, float d2, float m, const float4* __restrict__ velp,
+                                          uint32_t q)
+   {
+      float4 vj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      if (VEL) vj = velp[q];
+      add<UNIT_SCALE>(k, d2, m, vj.x, vj.y, vj.z);
+   }
 
    template <bool UNIT_SCALE>
    __device__ __forceinline__ void add(const PairConsts& k, float d2, float m, float ux, float uy, float uz)
@@ -57,6 +78,8 @@ struct SampleSum {
       }
       count++;
    }
+
+   __device__ __forceinline__ void store(int o, const Out& out) const { store(o, out.rho, out.vel, out.cnt); }
 
    __device__ __forceinline__ void store(int o, float* __restrict__ rho_out, float* __restrict__ vel_out,
                                          int32_t* __restrict__ cnt_out) const
@@ -80,12 +103,12 @@ __device__ __forceinline__ void probe_cell(const CellGrid& g, float x, float y, 
    cz = cell_coord(z, g.inv, g.nz);
 }
 
-// one probe, candidates read from global memory (through L1/L2)
-template <bool UNIT_SCALE, bool VEL>
+// one probe, candidates read from global memory (through L1/L2), for any accumulator
+template <bool UNIT_SCALE, class Sum>
 __device__ __forceinline__ void sample_walk(float px, float py, float pz, const float4* __restrict__ posm,
-                                            const float4* __restrict__ velp,
+                                            const typename Sum::Payload* __restrict__ payload,
                                             const uint32_t* __restrict__ cell_start, const CellGrid& g,
-                                            const PairConsts& k, SampleSum<VEL>& s)
+                                            const PairConsts& k, Sum& s)
 {
    int cx, cy, cz;
    probe_cell(g, px, py, pz, cx, cy, cz);
@@ -93,43 +116,59 @@ __device__ __forceinline__ void sample_walk(float px, float py, float pz, const 
    row_ranges(g, cell_start, cx, cy, cz, r);
 #pragma unroll 1
    for (int row = 0; row < 9; row++) {
-      const uint32_t b = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
+      uint32_t b, e;
+      row_range(r, row, b, e);
       for (uint32_t q = b; q < e; q++) {
          const float4 pj = posm[q];
          float dx, dy, dz;
          const float d2 = dist2(px, py, pz, pj.x, pj.y, pj.z, dx, dy, dz);
-         if (d2 < k.h2) {
-            float4 vj = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (VEL) vj = velp[q];
-            s.template add<UNIT_SCALE>(k, d2, pj.w, vj.x, vj.y, vj.z);
-         }
+         if (d2 < k.h2) s.template member<UNIT_SCALE>(k, d2, pj.w, payload, q);
       }
    }
 }
 
 // ---- point probes: one lane per probe ---------------------------------------------------------
-template <bool UNIT_SCALE, bool VEL>
+template <bool UNIT_SCALE, class Sum>
 __global__ void __launch_bounds__(256)
 k_sample_points(const float* __restrict__ xyz, int n, const float4* __restrict__ posm,
-                const float4* __restrict__ velp, const uint32_t* __restrict__ cell_start, CellGrid g,
-                PairConsts k, float* __restrict__ rho_out, float* __restrict__ vel_out,
-                int32_t* __restrict__ cnt_out)
+                const typename Sum::Payload* __restrict__ payload, const uint32_t* __restrict__ cell_start, CellGrid g,
+                PairConsts k, typename Sum::Out out)
 {
    const int p = blockIdx.x * blockDim.x + threadIdx.x;
    if (p >= n) return;
-   SampleSum<VEL> s;
-   sample_walk<UNIT_SCALE, VEL>(xyz[3 * p + 0], xyz[3 * p + 1], xyz[3 * p + 2], posm, velp, cell_start, g, k, s);
-   s.store(p, rho_out, vel_out, cnt_out);
+   Sum s;
+   sample_walk<UNIT_SCALE>(xyz[3 * p + 0], xyz[3 * p + 1], xyz[3 * p + 2], posm, payload, cell_start, g, k, s);
+   s.store(p, out);
 }
 
 // ---- lattice probes: one workgroup per brick --------------------------------------------------
-// TILED = false: every lane walks per probe (the default route: sample_policy.h); no LDS.  TILED = true: the tile of sample_policy.h, in dynamic LDS of
-// tile_cap * (16 or 28) bytes, SoA: x[cap], y[cap], z[cap], m[cap] (, vx[cap], vy[cap], vz[cap]).
 // Outputs are indexed by the point's place in the chunk: ((kl * ey) + jl) * ex + il.
-template <bool UNIT_SCALE, bool VEL, bool TILED>
+// Every lane walks per probe (the default route: sample_policy.h); no LDS.
+template <bool UNIT_SCALE, class Sum>
+__global__ void __launch_bounds__(SAMPLE_THREADS)
+k_sample_lattice_walk(SampleLattice L, const float4* __restrict__ posm, const typename Sum::Payload* __restrict__ payload,
+                      const uint32_t* __restrict__ cell_start, CellGrid g, PairConsts k, typename Sum::Out out)
+{
+   const int t = threadIdx.x;
+   const int b = blockIdx.x;
+   const int bx = b % L.bricks_x, by = (b / L.bricks_x) % L.bricks_y, bz = b / (L.bricks_x * L.bricks_y);
+   const int il = bx * L.bx + t % L.bx;
+   const int jl = by * L.by + (t / L.bx) % L.by;
+   const int kl = bz * L.bz + t / (L.bx * L.by);
+   if (!(il < L.ex && jl < L.ey && kl < L.ez)) return;
+   // the lattice point, origin + (float)i * spacing per axis (unfused: -ffp-contract=off)
+   const float px = L.ox + (float)(L.i0 + il) * L.sx;
+   const float py = L.oy + (float)(L.j0 + jl) * L.sy;
+   const float pz = L.oz + (float)(L.k0 + kl) * L.sz;
+   const int o = (kl * L.ey + jl) * L.ex + il;
+   Sum s;
+   sample_walk<UNIT_SCALE>(px, py, pz, posm, payload, cell_start, g, k, s);
+   s.store(o, out);
+}
+
+// The tiled route of the density and velocity sampler (SPH_HIP_SAMPLE_TILED=1): the tile of sample_policy.h,
+// in dynamic LDS of tile_cap * (16 or 28) bytes, SoA: x[cap], y[cap], z[cap], m[cap] (, vx[cap], vy[cap], vz[cap]).
+template <bool UNIT_SCALE, bool VEL>
 __global__ void __launch_bounds__(SAMPLE_THREADS)
 k_sample_lattice(SampleLattice L, const float4* __restrict__ posm, const float4* __restrict__ velp,
                  const uint32_t* __restrict__ cell_start, CellGrid g, PairConsts k, int tile_cap,
@@ -142,18 +181,12 @@ k_sample_lattice(SampleLattice L, const float4* __restrict__ posm, const float4*
    const int jl = by * L.by + (t / L.bx) % L.by;
    const int kl = bz * L.bz + t / (L.bx * L.by);
    const bool valid = il < L.ex && jl < L.ey && kl < L.ez;
-   // the lattice point, origin + (float)i * spacing per axis (unfused: -ffp-contract=off)
+   // (the lattice point and its place in the chunk: k_sample_lattice_walk's)
    const float px = L.ox + (float)(L.i0 + il) * L.sx;
    const float py = L.oy + (float)(L.j0 + jl) * L.sy;
    const float pz = L.oz + (float)(L.k0 + kl) * L.sz;
    const int o = (kl * L.ey + jl) * L.ex + il;
    SampleSum<VEL> s;
-   if (!TILED) {
-      if (!valid) return;
-      sample_walk<UNIT_SCALE, VEL>(px, py, pz, posm, velp, cell_start, g, k, s);
-      s.store(o, rho_out, vel_out, cnt_out);
-      return;
-   }
 
    __shared__ uint32_t row_s[SAMPLE_MAX_ROWS];       // global start of each tile row
    __shared__ uint32_t row_b[SAMPLE_MAX_ROWS + 1];   // its LDS base; [nrows] = entries
@@ -188,7 +221,7 @@ k_sample_lattice(SampleLattice L, const float4* __restrict__ posm, const float4*
    if (!box_ok || nrows > SAMPLE_MAX_ROWS) {
       // (uniform) more rows than the table holds, or a box that cannot be bounded: walk per probe
       if (!valid) return;
-      sample_walk<UNIT_SCALE, VEL>(px, py, pz, posm, velp, cell_start, g, k, s);
+      sample_walk<UNIT_SCALE>(px, py, pz, posm, velp, cell_start, g, k, s);
       s.store(o, rho_out, vel_out, cnt_out);
       return;
    }
@@ -222,7 +255,7 @@ k_sample_lattice(SampleLattice L, const float4* __restrict__ posm, const float4*
    if (total > (uint32_t)tile_cap) {
       // a denser region than the capacity is sized for: this brick walks per probe, with the same bits
       if (!valid) return;
-      sample_walk<UNIT_SCALE, VEL>(px, py, pz, posm, velp, cell_start, g, k, s);
+      sample_walk<UNIT_SCALE>(px, py, pz, posm, velp, cell_start, g, k, s);
       s.store(o, rho_out, vel_out, cnt_out);
       return;
    }

@@ -4,8 +4,8 @@
 // bounds the device scratch of large probe sets.
 // The lattice argument checks, the scratch budget and the 256-byte rounding are shared with the
 // iso-surface extractor (surface_policy.h) and the renderer (render_policy.h).
-// Pure C++17 without HIP (tests/test_sample_cpu.py compiles it with g++); the environment switch
-// (SPH_HIP_SAMPLE_UNTILED) is read by the caller and passed in.
+// Pure C++17 without HIP (tests/test_sample_cpu.py compiles it with g++); the environment switches
+// (SPH_HIP_SAMPLE_UNTILED, SPH_HIP_SAMPLE_TILED, SPH_HIP_SAMPLE_CHUNK) are read by the caller and passed in.
 #pragma once
 
 #include <math.h>
@@ -73,6 +73,19 @@ static const SampleBrick SAMPLE_BRICKS[SAMPLE_N_BRICKS] = {
 // budget the extractor's slabs and the renderer's row chunks are sized to as well.
 #define SAMPLE_CHUNK_POINTS (1 << 21)
 #define SAMPLE_SCRATCH_BUDGET (64ll << 20)
+
+// SPH_HIP_SAMPLE_CHUNK=n (tests; read at context creation): the chunk limit of every sampler call, so
+// that a small probe set takes several chunks.  0 or less: off, the compiled limits hold.  Otherwise
+// clamped to [SAMPLE_THREADS, SAMPLE_CHUNK_POINTS]: below one brick sample_lattice_chunk would return
+// an empty run of bricks, above the limit the scratch would exceed its budget.
+inline int sample_chunk_forced(long long value)
+{
+   if (value <= 0) return 0;
+   return (int)(value < SAMPLE_THREADS ? SAMPLE_THREADS : value > SAMPLE_CHUNK_POINTS ? SAMPLE_CHUNK_POINTS : value);
+}
+
+// the chunk limit of a call whose own limit is `limit`: the smaller of it and a forced one
+inline int sample_chunk_limit(int limit, int forced) { return forced > 0 && forced < limit ? forced : limit; }
 
 // scratch arrays start on 256-byte boundaries
 inline long long round256(long long b) { return (b + 255) / 256 * 256; }

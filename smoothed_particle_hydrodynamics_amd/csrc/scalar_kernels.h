@@ -1,6 +1,7 @@
 // Carried scalars (include/sph_hip.h: carried scalars; the contract and every check: scalar_policy.h; the
 // routes: launch_policy.h): the stage that brings the scalars to the sorted slots, the pass that advances
-// them, and the point and lattice samplers of the channels.
+// them, and the channel sums of the sampler's walk (with them the sampler's own kernels are the point and
+// lattice samplers of the channels: sample_kernels.h).
 //
 // The scalars live by particle ID (T[id], the id in velp.w) and never ride through the cell build.  A step
 // stages Ts[p] = T[id(p)] and Vs[p] = m / rho for the sorted slots of its state S_k (k_scalars_stage), then
@@ -95,10 +96,8 @@ __device__ __forceinline__ void scalars_from_rows(int p, const CellGrid& g, cons
    row_ranges(g, cell_start, cx, cy, cz, r);
 #pragma unroll 1
    for (int row = 0; row < 9; row++) {
-      const uint32_t b = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
+      uint32_t b, e;
+      row_range(r, row, b, e);
       for (uint32_t q = b; q < e; q++) {
          if (q == (uint32_t)p) continue;
          const float4 pj = posm[q];
@@ -151,16 +150,30 @@ k_scalars_step(const float4* __restrict__ posm, const float4* __restrict__ velp,
    if (id < (uint32_t)n_rows) T[id] = float4_of(out);
 }
 
-// ---- the samplers of the channels ------------------------------------------------------------------------------
+// ---- the channel sums of the sampler's walk (sample_kernels.h) -------------------------------------------------
 // accumulator of one probe: the sampler's rho and count, and a_c = sum of t_j * T_j,c
 struct ScalarSum {
    float rho = 0.0f, a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
    int count = 0;
 
+   using Payload = float4;   // Ts: the channels of sorted particle q (k_scalars_stage)
+   struct Out {
+      float4* chan;
+      float* rho;
+      int32_t* cnt;
+   };
+
+   template <bool UNIT_SCALE>
+   __device__ __forceinline__ void member(const PairConsts& k, float d2, float m, const float4* __restrict__ Ts,
+                                          uint32_t q)
+   {
+      add<UNIT_SCALE>(k, d2, m, Ts[q]);
+   }
+
    template <bool UNIT_SCALE>
    __device__ __forceinline__ void add(const PairConsts& k, float d2, float m, const float4& tj)
    {
-      float d = sqrt_rn(d2);   // (SampleSum::add)
+      float d = sqrt_rn(d2);   // (as SampleSum::add: sample_kernels.h)
       if (!UNIT_SCALE) d *= k.sim_scale;
       const float t = density_term<UNIT_SCALE>(k, m, d);
       rho += t;
@@ -171,76 +184,11 @@ struct ScalarSum {
       count++;
    }
 
-   __device__ __forceinline__ void store(int o, float4* __restrict__ chan_out, float* __restrict__ rho_out,
-                                         int32_t* __restrict__ cnt_out) const
+   __device__ __forceinline__ void store(int o, const Out& out) const
    {
-      chan_out[o] = make_float4(scalar_shepard(a0, rho), scalar_shepard(a1, rho), scalar_shepard(a2, rho),
+      out.chan[o] = make_float4(scalar_shepard(a0, rho), scalar_shepard(a1, rho), scalar_shepard(a2, rho),
                                 scalar_shepard(a3, rho));
-      rho_out[o] = rho;
-      cnt_out[o] = count;
+      out.rho[o] = rho;
+      out.cnt[o] = count;
    }
 };
-
-// one probe, candidates read from global memory (sample_walk with one more 16-byte load per member)
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void sample_walk_scalars(float px, float py, float pz, const float4* __restrict__ posm,
-                                                    const float4* __restrict__ Ts,
-                                                    const uint32_t* __restrict__ cell_start, const CellGrid& g,
-                                                    const PairConsts& k, ScalarSum& s)
-{
-   int cx, cy, cz;
-   probe_cell(g, px, py, pz, cx, cy, cz);
-   RowRanges r;
-   row_ranges(g, cell_start, cx, cy, cz, r);
-#pragma unroll 1
-   for (int row = 0; row < 9; row++) {
-      const uint32_t b = row == 0 ? r.s[0] : row == 1 ? r.s[1] : row == 2 ? r.s[2] : row == 3 ? r.s[3]
-                       : row == 4 ? r.s[4] : row == 5 ? r.s[5] : row == 6 ? r.s[6] : row == 7 ? r.s[7] : r.s[8];
-      const uint32_t e = row == 0 ? r.e[0] : row == 1 ? r.e[1] : row == 2 ? r.e[2] : row == 3 ? r.e[3]
-                       : row == 4 ? r.e[4] : row == 5 ? r.e[5] : row == 6 ? r.e[6] : row == 7 ? r.e[7] : r.e[8];
-      for (uint32_t q = b; q < e; q++) {
-         const float4 pj = posm[q];
-         float dx, dy, dz;
-         const float d2 = dist2(px, py, pz, pj.x, pj.y, pj.z, dx, dy, dz);
-         if (d2 < k.h2) s.template add<UNIT_SCALE>(k, d2, pj.w, Ts[q]);
-      }
-   }
-}
-
-// point probes: one lane per probe (k_sample_pressure_points' shape)
-template <bool UNIT_SCALE>
-__global__ void __launch_bounds__(256)
-k_sample_scalars_points(const float* __restrict__ xyz, int n, const float4* __restrict__ posm,
-                        const float4* __restrict__ Ts, const uint32_t* __restrict__ cell_start, CellGrid g,
-                        PairConsts k, float4* __restrict__ chan_out, float* __restrict__ rho_out,
-                        int32_t* __restrict__ cnt_out)
-{
-   const int p = blockIdx.x * blockDim.x + threadIdx.x;
-   if (p >= n) return;
-   ScalarSum s;
-   sample_walk_scalars<UNIT_SCALE>(xyz[3 * p + 0], xyz[3 * p + 1], xyz[3 * p + 2], posm, Ts, cell_start, g, k, s);
-   s.store(p, chan_out, rho_out, cnt_out);
-}
-
-// lattice probes: one workgroup per brick, every lane walks per probe (k_sample_pressure_lattice's shape)
-template <bool UNIT_SCALE>
-__global__ void __launch_bounds__(SAMPLE_THREADS)
-k_sample_scalars_lattice(SampleLattice L, const float4* __restrict__ posm, const float4* __restrict__ Ts,
-                         const uint32_t* __restrict__ cell_start, CellGrid g, PairConsts k,
-                         float4* __restrict__ chan_out, float* __restrict__ rho_out, int32_t* __restrict__ cnt_out)
-{
-   const int t = threadIdx.x;
-   const int b = blockIdx.x;
-   const int bx = b % L.bricks_x, by = (b / L.bricks_x) % L.bricks_y, bz = b / (L.bricks_x * L.bricks_y);
-   const int il = bx * L.bx + t % L.bx;
-   const int jl = by * L.by + (t / L.bx) % L.by;
-   const int kl = bz * L.bz + t / (L.bx * L.by);
-   if (!(il < L.ex && jl < L.ey && kl < L.ez)) return;
-   const float px = L.ox + (float)(L.i0 + il) * L.sx;
-   const float py = L.oy + (float)(L.j0 + jl) * L.sy;
-   const float pz = L.oz + (float)(L.k0 + kl) * L.sz;
-   const int o = (kl * L.ey + jl) * L.ex + il;
-   ScalarSum s;
-   sample_walk_scalars<UNIT_SCALE>(px, py, pz, posm, Ts, cell_start, g, k, s);
-   s.store(o, chan_out, rho_out, cnt_out);
-}

@@ -53,15 +53,6 @@ int sample_check(sph_hip_context* ctx, const char* who)
    return SPH_HIP_OK;
 }
 
-// nothing resident (the cell arrays may still describe an earlier upload): n samples of 0
-int sample_zero(size_t n, float* density, float* velocity_xyz, int32_t* count)
-{
-   if (density) memset(density, 0, sizeof(float) * n);
-   if (velocity_xyz) memset(velocity_xyz, 0, sizeof(float) * 3 * n);
-   if (count) memset(count, 0, sizeof(int32_t) * n);
-   return SPH_HIP_OK;
-}
-
 // Bring the cell structure up to date with the current positions: the build sph_hip_voxelize runs,
 // which consumes a pending prehash and moves the last sums with the particles, so that nothing a
 // caller can read or a later step computes changes.
@@ -94,6 +85,182 @@ struct Carver {
       return q;
    }
 };
+
+// ---- the samplers' host driver ---------------------------------------------------------------------
+// What the calls that sample a field at points or on a lattice share (density and velocity, the
+// pressure, the carried scalars): the checks in the order the header promises them, the cell build, the
+// chunks that bound the device scratch, the copies out.  A call says what it returns and what it needs;
+// its kernel launch for one chunk is a callable.
+
+// one output: the caller's array (null: not wanted) and its bytes per probe
+struct SampleOut {
+   void* host;
+   size_t bytes;
+};
+
+struct SampleCall {
+   const char* who;                                  // the entry point, for error text
+   SampleOut out[3];                                 // in the order of the entry point's arguments
+   const char* (*refusal)(const sph_hip_context*);   // a precondition of the call's own: why not, or nullptr
+   int (*stage)(sph_hip_context*);                   // what the kernel reads besides the sorted state: launched
+                                                     // behind the cell build
+};
+
+// The refusals every sampler shares, behind check_ctx and `args` (why the probes or the lattice are
+// refused, or nullptr), then the call's own.
+int sample_refusals(sph_hip_context* ctx, const SampleCall& c, const char* args)
+{
+   if (args) return refuse(ctx, c.who, args);
+   if (int rc = sample_check(ctx, c.who)) return rc;
+   if (c.refusal)
+      if (const char* why = c.refusal(ctx)) return refuse(ctx, c.who, why);
+   return SPH_HIP_OK;
+}
+
+// nothing resident (the cell arrays may still describe an earlier upload): n samples of 0
+int sample_zero(const SampleCall& c, size_t n)
+{
+   for (const SampleOut& o : c.out)
+      if (o.host) memset(o.host, 0, o.bytes * n);
+   return SPH_HIP_OK;
+}
+
+// the cell build, then the call's stage
+int sample_ready(sph_hip_context* ctx, const SampleCall& c)
+{
+   if (int rc = sample_prepare(ctx)) return rc;
+   return c.stage ? c.stage(ctx) : SPH_HIP_OK;
+}
+
+// A chunk's arrays in ctx->sample_buf: the outputs of 16-byte elements first (their stores are 16 bytes
+// wide), then the probes of a point set (3 floats each), then the other outputs in the call's order.
+struct SampleScratch {
+   float* xyz;
+   void* dev[3];
+};
+
+int sample_carve(sph_hip_context* ctx, const SampleCall& c, size_t chunk, bool probes, SampleScratch& s)
+{
+   size_t words = probes ? 3 : 0;
+   for (const SampleOut& o : c.out) words += o.bytes / sizeof(float);
+   if (int rc = ctx->sample_buf.reserve(ctx, chunk * words)) return rc;
+   float* p = ctx->sample_buf;
+   auto take = [&](size_t words_each) {
+      float* q = p;
+      p += chunk * words_each;
+      return q;
+   };
+   for (int i = 0; i < 3; i++)
+      if (c.out[i].bytes % 16 == 0) s.dev[i] = take(c.out[i].bytes / sizeof(float));
+   s.xyz = probes ? take(3) : nullptr;
+   for (int i = 0; i < 3; i++)
+      if (c.out[i].bytes % 16 != 0) s.dev[i] = take(c.out[i].bytes / sizeof(float));
+   return SPH_HIP_OK;
+}
+
+// n probes, at most chunk_limit per chunk; launch(probes on the device, their count, the outputs' arrays)
+template <class Launch>
+int sample_points_run(sph_hip_context* ctx, const SampleCall& c, int n, const float* xyz, int chunk_limit,
+                      Launch launch)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if ((rc = sample_refusals(ctx, c, n < 0 || (n > 0 && !xyz) ? "negative count or null probe array" : nullptr)))
+      return rc;
+   if (n == 0) return SPH_HIP_OK;
+   if (ctx->n == 0) return sample_zero(c, (size_t)n);
+   if ((rc = sample_ready(ctx, c))) return rc;
+   const int chunk = sample_points_chunk(n, sample_chunk_limit(chunk_limit, ctx->sample_chunk_forced));
+   SampleScratch s;
+   if ((rc = sample_carve(ctx, c, (size_t)chunk, true, s))) return rc;
+   hipStream_t st = ctx->stream;
+   for (int p0 = 0; p0 < n; p0 += chunk) {
+      const int m = n - p0 < chunk ? n - p0 : chunk;
+      SPH_TRY(hipMemcpyAsync(s.xyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+      launch(s.xyz, m, s.dev);
+      SPH_TRY(hipGetLastError());
+      for (int i = 0; i < 3; i++)
+         if (c.out[i].host)
+            SPH_TRY(hipMemcpyAsync((char*)c.out[i].host + c.out[i].bytes * (size_t)p0, s.dev[i], c.out[i].bytes * m,
+                                   hipMemcpyDeviceToHost, st));
+   }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// A chunk's outputs are a box of the caller's arrays (elem bytes a point): one copy per z-plane, or one
+// for the lot when the chunk spans whole planes.
+hipError_t sample_copy_box(void* dst, const void* src, size_t elem, const SampleLattice& L, const int32_t dims[3],
+                           hipStream_t st)
+{
+   char* d = (char*)dst;
+   const char* s = (const char*)src;
+   const size_t plane = (size_t)dims[0] * dims[1];
+   if (L.ex == dims[0] && L.ey == dims[1])
+      return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem, hipMemcpyDeviceToHost,
+                            st);
+   for (int z = 0; z < L.ez; z++) {
+      const hipError_t e = hipMemcpy2DAsync(
+          d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
+          s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
+          hipMemcpyDeviceToHost, st);
+      if (e != hipSuccess) return e;
+   }
+   return hipSuccess;
+}
+
+// a lattice, in chunks of whole bricks (sample_lattice_chunk); launch(the chunk, its bricks, the outputs' arrays)
+template <class Launch>
+int sample_lattice_run(sph_hip_context* ctx, const SampleCall& c, const float origin[3], const float spacing[3],
+                       const int32_t dims[3], Launch launch)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if ((rc = sample_refusals(ctx, c, lattice_check(origin, spacing, dims)))) return rc;
+   if (ctx->n == 0) return sample_zero(c, (size_t)dims[0] * dims[1] * dims[2]);
+   if ((rc = sample_ready(ctx, c))) return rc;
+   double cells[3];
+   sample_spacing_cells(spacing, ctx->grid.inv, cells);
+   const SampleBrick brick = sample_brick(dims, cells);
+   const SampleChunk ch =
+       sample_lattice_chunk(dims, brick, sample_chunk_limit(SAMPLE_CHUNK_POINTS, ctx->sample_chunk_forced));
+   SampleScratch s;
+   if ((rc = sample_carve(ctx, c, (size_t)ch.ex * ch.ey * ch.ez, false, s))) return rc;
+   hipStream_t st = ctx->stream;
+   SampleLattice L = lattice_of(origin, spacing, brick);
+   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += ch.ez)
+      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += ch.ey)
+         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += ch.ex) {
+            L.ex = dims[0] - L.i0 < ch.ex ? dims[0] - L.i0 : ch.ex;
+            L.ey = dims[1] - L.j0 < ch.ey ? dims[1] - L.j0 : ch.ey;
+            L.ez = dims[2] - L.k0 < ch.ez ? dims[2] - L.k0 : ch.ez;
+            L.bricks_x = div_up(L.ex, L.bx);
+            L.bricks_y = div_up(L.ey, L.by);
+            launch(L, L.bricks_x * L.bricks_y * div_up(L.ez, L.bz), s.dev);
+            SPH_TRY(hipGetLastError());
+            for (int i = 0; i < 3; i++)
+               if (c.out[i].host) SPH_TRY(sample_copy_box(c.out[i].host, s.dev[i], c.out[i].bytes, L, dims, st));
+         }
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// the launches of the per-probe kernels (sample_kernels.h), for any accumulator
+template <bool UNIT_SCALE, class Sum>
+void sample_points_launch(sph_hip_context* ctx, const float* xyz, int m, const typename Sum::Payload* payload,
+                          typename Sum::Out out)
+{
+   hipLaunchKernelGGL((k_sample_points<UNIT_SCALE, Sum>), dim3(div_up(m, 256)), dim3(256), 0, ctx->stream, xyz, m,
+                      ctx->posm[ctx->cur], payload, ctx->cell_start, ctx->grid, pair_consts(ctx->prm, ctx->fast != 0), out);
+}
+
+template <bool UNIT_SCALE, class Sum>
+void sample_lattice_launch(sph_hip_context* ctx, const SampleLattice& L, int bricks, const typename Sum::Payload* payload,
+                           typename Sum::Out out)
+{
+   hipLaunchKernelGGL((k_sample_lattice_walk<UNIT_SCALE, Sum>), dim3(bricks), dim3(SAMPLE_THREADS), 0, ctx->stream, L,
+                      ctx->posm[ctx->cur], payload, ctx->cell_start, ctx->grid, pair_consts(ctx->prm, ctx->fast != 0), out);
+}
 
 
 // ---- iso-surface extractor (surface_kernels.h; decisions: surface_policy.h) ------------------------
@@ -1536,18 +1703,28 @@ int sph_hip_get_loads(sph_hip_context* ctx, int first_row, int n_rows, int64_t* 
    SPH_TRY(hipStreamSynchronize(ctx->stream));
    if (rows_recorded) *rows_recorded = ctx->loads_next;
    if (n_rows == 0) return SPH_HIP_OK;
-   // a device row is impulse | count | skipped: one strided copy per output
+   // A device row is impulse | count | skipped.  The rows come over whole, in one contiguous copy, and are
+   // dealt out to the caller's arrays here.  (Three strided hipMemcpy2D calls into the caller's arrays stood
+   // here.  Three times a whole-suite run ended in one of them with "an illegal memory access", each time
+   // behind a stream synchronise that had succeeded, a different one of the three each time: DESIGN.md
+   // sections 20, 27 and 29.  A strided copy to pageable memory makes the runtime map the caller's pages for
+   // the device; a contiguous one goes through the runtime's own staging, as every other download here.)
    const size_t word = sizeof(int64_t), S = SPH_HIP_LOAD_SOLIDS;
    const unsigned long long* first = ctx->loads_dev.get() + (size_t)first_row * LOAD_ROW_WORDS;
-   if (impulse)
-      SPH_TRY(hipMemcpy2D(impulse, 3 * S * word, first, LOAD_ROW_WORDS * word, 3 * S * word, (size_t)n_rows,
-                          hipMemcpyDeviceToHost));
-   if (count)
-      SPH_TRY(hipMemcpy2D(count, S * word, first + LOAD_ROW_COUNT, LOAD_ROW_WORDS * word, S * word, (size_t)n_rows,
-                          hipMemcpyDeviceToHost));
-   if (skipped)
-      SPH_TRY(hipMemcpy2D(skipped, S * word, first + LOAD_ROW_SKIPPED, LOAD_ROW_WORDS * word, S * word,
-                          (size_t)n_rows, hipMemcpyDeviceToHost));
+   std::vector<unsigned long long> rows;
+   try {
+      rows.resize((size_t)n_rows * LOAD_ROW_WORDS);
+   } catch (const std::bad_alloc&) {
+      ctx->err = "sph_hip_get_loads: no host memory for " + std::to_string(n_rows) + " rows";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   SPH_TRY(hipMemcpy(rows.data(), first, rows.size() * word, hipMemcpyDeviceToHost));
+   for (size_t r = 0; r < (size_t)n_rows; r++) {
+      const unsigned long long* row = rows.data() + r * LOAD_ROW_WORDS;
+      if (impulse) memcpy(impulse + r * 3 * S, row, 3 * S * word);
+      if (count) memcpy(count + r * S, row + LOAD_ROW_COUNT, S * word);
+      if (skipped) memcpy(skipped + r * S, row + LOAD_ROW_SKIPPED, S * word);
+   }
    return SPH_HIP_OK;
 }
 
@@ -1753,230 +1930,81 @@ int sph_hip_download_neighbor_lists(sph_hip_context* ctx, uint32_t* neighbors, f
 int sph_hip_sample_points(sph_hip_context* ctx, int n, const float* xyz, float* density, float* velocity_xyz,
                           int32_t* count)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   if (n < 0 || (n > 0 && !xyz)) {
-      ctx->err = "sph_hip_sample_points: negative count or null probe array";
-      return SPH_HIP_ERR_INVALID;
-   }
-   if ((rc = sample_check(ctx, "sph_hip_sample_points"))) return rc;
-   if (n == 0) return SPH_HIP_OK;
-   if (ctx->n == 0) return sample_zero((size_t)n, density, velocity_xyz, count);
-   if ((rc = sample_prepare(ctx))) return rc;
-   const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS);
-   if ((rc = ctx->sample_buf.reserve(ctx, (size_t)chunk * 8))) return rc;
-   float* sxyz = ctx->sample_buf;
-   float* srho = sxyz + 3 * (size_t)chunk;
-   float* svel = srho + (size_t)chunk;
-   int32_t* scnt = reinterpret_cast<int32_t*>(svel + 3 * (size_t)chunk);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
-   hipStream_t st = ctx->stream;
-   for (int p0 = 0; p0 < n; p0 += chunk) {
-      const int m = n - p0 < chunk ? n - p0 : chunk;
-      SPH_TRY(hipMemcpyAsync(sxyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+   const SampleCall call = {"sph_hip_sample_points", {{density, 4}, {velocity_xyz, 12}, {count, 4}}, nullptr, nullptr};
+   return sample_points_run(ctx, call, n, xyz, SAMPLE_CHUNK_POINTS, [&](const float* sxyz, int m, void* const dev[3]) {
       bind_flags([&](auto U, auto V) {
-         hipLaunchKernelGGL((k_sample_points<U.value, V.value>), dim3(div_up(m, 256)), dim3(256), 0, st, sxyz, m,
-                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid, k, srho, svel,
-                            scnt);
+         sample_points_launch<U.value, SampleSum<V.value>>(ctx, sxyz, m, ctx->velp[ctx->cur],
+                                                           {(float*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
       }, unit_scale(ctx->prm), velocity_xyz != nullptr);
-      SPH_TRY(hipGetLastError());
-      if (density) SPH_TRY(hipMemcpyAsync(density + p0, srho, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-      if (velocity_xyz)
-         SPH_TRY(hipMemcpyAsync(velocity_xyz + 3 * (size_t)p0, svel, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, st));
-      if (count) SPH_TRY(hipMemcpyAsync(count + p0, scnt, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-   }
-   SPH_TRY(hipStreamSynchronize(st));
-   return SPH_HIP_OK;
+   });
 }
 
 int sph_hip_sample_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3], const int32_t dims[3],
                            float* density, float* velocity_xyz, int32_t* count)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, "sph_hip_sample_lattice", why);
-   if ((rc = sample_check(ctx, "sph_hip_sample_lattice"))) return rc;
-   if (ctx->n == 0) return sample_zero((size_t)dims[0] * dims[1] * dims[2], density, velocity_xyz, count);
-   if ((rc = sample_prepare(ctx))) return rc;
-   double cells[3];
-   sample_spacing_cells(spacing, ctx->grid.inv, cells);
-   const SampleBrick brick = sample_brick(dims, cells);
-   const bool tiled = sample_use_tiled(brick, dims, cells, SAMPLE_TILE_CAP, ctx->sample_route);
-   if (tiled && !ctx->sample_lds_set) {
-      // (the attribute belongs to the function on the current device: set once per context)
-      for (int m = 0; m < 4; m++)
-         bind_flags([&](auto U, auto V) {
-            (void)hipFuncSetAttribute((const void*)(k_sample_lattice<U.value, V.value, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      SAMPLE_TILE_CAP * SAMPLE_TILE_BYTES_VELOCITY);
-         }, (m & 1) != 0, (m & 2) != 0);
-      (void)hipGetLastError();
-      ctx->sample_lds_set = 1;
-   }
+   const SampleCall call = {"sph_hip_sample_lattice", {{density, 4}, {velocity_xyz, 12}, {count, 4}}, nullptr, nullptr};
    const bool vel = velocity_xyz != nullptr;
-   const size_t lds = tiled ? (size_t)SAMPLE_TILE_CAP *
-                                  (vel ? SAMPLE_TILE_BYTES_VELOCITY : SAMPLE_TILE_BYTES_DENSITY) : 0;
-   const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
-   const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
-   if ((rc = ctx->sample_buf.reserve(ctx, chunk_points * 5))) return rc;
-   float* srho = ctx->sample_buf;
-   float* svel = srho + chunk_points;
-   int32_t* scnt = reinterpret_cast<int32_t*>(svel + 3 * chunk_points);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
-   const bool unit = unit_scale(ctx->prm);
-   hipStream_t st = ctx->stream;
-   SampleLattice L = lattice_of(origin, spacing, brick);
-   // a chunk's outputs are a box of the caller's arrays: one copy per z-plane and array, or one for
-   // the lot when the chunk spans whole planes
-   auto copy_out = [&](void* dst, const void* src, size_t elem) -> hipError_t {
-      char* d = (char*)dst;
-      const char* s = (const char*)src;
-      const size_t plane = (size_t)dims[0] * dims[1];
-      if (L.ex == dims[0] && L.ey == dims[1])
-         return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem,
-                               hipMemcpyDeviceToHost, st);
-      for (int z = 0; z < L.ez; z++) {
-         const hipError_t e = hipMemcpy2DAsync(
-             d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
-             s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
-             hipMemcpyDeviceToHost, st);
-         if (e != hipSuccess) return e;
+   return sample_lattice_run(ctx, call, origin, spacing, dims, [&](const SampleLattice& L, int bricks, void* const dev[3]) {
+      float* srho = (float*)dev[0];
+      float* svel = (float*)dev[1];
+      int32_t* scnt = (int32_t*)dev[2];
+      // the tiled route (SPH_HIP_SAMPLE_TILED=1: sample_policy.h) is this call's alone
+      double cells[3];
+      sample_spacing_cells(spacing, ctx->grid.inv, cells);
+      if (!sample_use_tiled(SampleBrick{L.bx, L.by, L.bz}, dims, cells, SAMPLE_TILE_CAP, ctx->sample_route)) {
+         bind_flags([&](auto U, auto V) {
+            sample_lattice_launch<U.value, SampleSum<V.value>>(ctx, L, bricks, ctx->velp[ctx->cur], {srho, svel, scnt});
+         }, unit_scale(ctx->prm), vel);
+         return;
       }
-      return hipSuccess;
-   };
-   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += c.ez)
-      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += c.ey)
-         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += c.ex) {
-            L.ex = dims[0] - L.i0 < c.ex ? dims[0] - L.i0 : c.ex;
-            L.ey = dims[1] - L.j0 < c.ey ? dims[1] - L.j0 : c.ey;
-            L.ez = dims[2] - L.k0 < c.ez ? dims[2] - L.k0 : c.ez;
-            L.bricks_x = div_up(L.ex, L.bx);
-            L.bricks_y = div_up(L.ey, L.by);
-            const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
-            bind_flags([&](auto U, auto V, auto T) {
-               hipLaunchKernelGGL((k_sample_lattice<U.value, V.value, T.value>), dim3(bricks), dim3(SAMPLE_THREADS),
-                                  lds, st, L, ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid,
-                                  k, SAMPLE_TILE_CAP, srho, svel, scnt);
-            }, unit, vel, tiled);
-            SPH_TRY(hipGetLastError());
-            if (density) SPH_TRY(copy_out(density, srho, sizeof(float)));
-            if (velocity_xyz) SPH_TRY(copy_out(velocity_xyz, svel, 3 * sizeof(float)));
-            if (count) SPH_TRY(copy_out(count, scnt, sizeof(int32_t)));
-         }
-   SPH_TRY(hipStreamSynchronize(st));
-   return SPH_HIP_OK;
+      if (!ctx->sample_lds_set) {
+         // (the attribute belongs to the function on the current device: set once per context)
+         for (int m = 0; m < 4; m++)
+            bind_flags([&](auto U, auto V) {
+               (void)hipFuncSetAttribute((const void*)(k_sample_lattice<U.value, V.value>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         SAMPLE_TILE_CAP * SAMPLE_TILE_BYTES_VELOCITY);
+            }, (m & 1) != 0, (m & 2) != 0);
+         (void)hipGetLastError();
+         ctx->sample_lds_set = 1;
+      }
+      const size_t lds = (size_t)SAMPLE_TILE_CAP * (vel ? SAMPLE_TILE_BYTES_VELOCITY : SAMPLE_TILE_BYTES_DENSITY);
+      bind_flags([&](auto U, auto V) {
+         hipLaunchKernelGGL((k_sample_lattice<U.value, V.value>), dim3(bricks), dim3(SAMPLE_THREADS), lds, ctx->stream, L,
+                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid,
+                            pair_consts(ctx->prm, ctx->fast != 0), SAMPLE_TILE_CAP, srho, svel, scnt);
+      }, unit_scale(ctx->prm), vel);
+   });
 }
 
 // ---- pressure samplers (pressure_kernels.h; contract: gauge_policy.h) ------------------------------
-// The sampler's calls with the pressure walk: behind the cell build the densities of the current state
+// The sampler's calls with the pressure sums: behind the cell build the densities of the current state
 // are formed into the context's own buffer (launch_particle_density), then the probes are walked.
 
 int sph_hip_sample_pressure_points(sph_hip_context* ctx, int n, const float* xyz, float* pressure, float* density,
                                    int32_t* count)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   if (n < 0 || (n > 0 && !xyz)) {
-      ctx->err = "sph_hip_sample_pressure_points: negative count or null probe array";
-      return SPH_HIP_ERR_INVALID;
-   }
-   if ((rc = sample_check(ctx, "sph_hip_sample_pressure_points"))) return rc;
-   if (n == 0) return SPH_HIP_OK;
-   if (ctx->n == 0) {
-      if (pressure) memset(pressure, 0, sizeof(float) * (size_t)n);
-      return sample_zero((size_t)n, density, nullptr, count);
-   }
-   if ((rc = sample_prepare(ctx))) return rc;
-   if ((rc = launch_particle_density(ctx))) return rc;
-   const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS);
-   if ((rc = ctx->sample_buf.reserve(ctx, (size_t)chunk * 6))) return rc;
-   float* sxyz = ctx->sample_buf;
-   float* sprs = sxyz + 3 * (size_t)chunk;
-   float* srho = sprs + (size_t)chunk;
-   int32_t* scnt = reinterpret_cast<int32_t*>(srho + (size_t)chunk);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
-   hipStream_t st = ctx->stream;
-   for (int p0 = 0; p0 < n; p0 += chunk) {
-      const int m = n - p0 < chunk ? n - p0 : chunk;
-      SPH_TRY(hipMemcpyAsync(sxyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+   const SampleCall call = {"sph_hip_sample_pressure_points", {{pressure, 4}, {density, 4}, {count, 4}}, nullptr,
+                            launch_particle_density};
+   return sample_points_run(ctx, call, n, xyz, SAMPLE_CHUNK_POINTS, [&](const float* sxyz, int m, void* const dev[3]) {
       bind_flags([&](auto U) {
-         hipLaunchKernelGGL((k_sample_pressure_points<U.value>), dim3(div_up(m, 256)), dim3(256), 0, st, sxyz, m,
-                            ctx->posm[ctx->cur], ctx->rho_own, ctx->cell_start, ctx->grid, k, sprs, srho, scnt);
+         sample_points_launch<U.value, PressureSum>(ctx, sxyz, m, ctx->rho_own,
+                                                    {(float*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
       }, unit_scale(ctx->prm));
-      SPH_TRY(hipGetLastError());
-      if (pressure) SPH_TRY(hipMemcpyAsync(pressure + p0, sprs, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-      if (density) SPH_TRY(hipMemcpyAsync(density + p0, srho, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-      if (count) SPH_TRY(hipMemcpyAsync(count + p0, scnt, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-   }
-   SPH_TRY(hipStreamSynchronize(st));
-   return SPH_HIP_OK;
+   });
 }
 
 int sph_hip_sample_pressure_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
                                     const int32_t dims[3], float* pressure, float* density, int32_t* count)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, "sph_hip_sample_pressure_lattice", why);
-   if ((rc = sample_check(ctx, "sph_hip_sample_pressure_lattice"))) return rc;
-   if (ctx->n == 0) {
-      const size_t total = (size_t)dims[0] * dims[1] * dims[2];
-      if (pressure) memset(pressure, 0, sizeof(float) * total);
-      return sample_zero(total, density, nullptr, count);
-   }
-   if ((rc = sample_prepare(ctx))) return rc;
-   if ((rc = launch_particle_density(ctx))) return rc;
-   double cells[3];
-   sample_spacing_cells(spacing, ctx->grid.inv, cells);
-   const SampleBrick brick = sample_brick(dims, cells);
-   const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
-   const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
-   if ((rc = ctx->sample_buf.reserve(ctx, chunk_points * 3))) return rc;
-   float* sprs = ctx->sample_buf;
-   float* srho = sprs + chunk_points;
-   int32_t* scnt = reinterpret_cast<int32_t*>(srho + chunk_points);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
-   const bool unit = unit_scale(ctx->prm);
-   hipStream_t st = ctx->stream;
-   SampleLattice L = lattice_of(origin, spacing, brick);
-   // (sph_hip_sample_lattice's copy of a chunk's box into the caller's arrays; every array is 4 bytes a point)
-   auto copy_out = [&](void* dst, const void* src) -> hipError_t {
-      const size_t elem = sizeof(float);
-      char* d = (char*)dst;
-      const char* s = (const char*)src;
-      const size_t plane = (size_t)dims[0] * dims[1];
-      if (L.ex == dims[0] && L.ey == dims[1])
-         return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem,
-                               hipMemcpyDeviceToHost, st);
-      for (int z = 0; z < L.ez; z++) {
-         const hipError_t e = hipMemcpy2DAsync(
-             d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
-             s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
-             hipMemcpyDeviceToHost, st);
-         if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
-   };
-   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += c.ez)
-      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += c.ey)
-         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += c.ex) {
-            L.ex = dims[0] - L.i0 < c.ex ? dims[0] - L.i0 : c.ex;
-            L.ey = dims[1] - L.j0 < c.ey ? dims[1] - L.j0 : c.ey;
-            L.ez = dims[2] - L.k0 < c.ez ? dims[2] - L.k0 : c.ez;
-            L.bricks_x = div_up(L.ex, L.bx);
-            L.bricks_y = div_up(L.ey, L.by);
-            const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
-            bind_flags([&](auto U) {
-               hipLaunchKernelGGL((k_sample_pressure_lattice<U.value>), dim3(bricks), dim3(SAMPLE_THREADS), 0, st, L,
-                                  ctx->posm[ctx->cur], ctx->rho_own, ctx->cell_start, ctx->grid, k, sprs, srho, scnt);
-            }, unit);
-            SPH_TRY(hipGetLastError());
-            if (pressure) SPH_TRY(copy_out(pressure, sprs));
-            if (density) SPH_TRY(copy_out(density, srho));
-            if (count) SPH_TRY(copy_out(count, scnt));
-         }
-   SPH_TRY(hipStreamSynchronize(st));
-   return SPH_HIP_OK;
+   const SampleCall call = {"sph_hip_sample_pressure_lattice", {{pressure, 4}, {density, 4}, {count, 4}}, nullptr,
+                            launch_particle_density};
+   return sample_lattice_run(ctx, call, origin, spacing, dims, [&](const SampleLattice& L, int bricks, void* const dev[3]) {
+      bind_flags([&](auto U) {
+         sample_lattice_launch<U.value, PressureSum>(ctx, L, bricks, ctx->rho_own,
+                                                     {(float*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
+      }, unit_scale(ctx->prm));
+   });
 }
 
 // ---- carried scalars (scalar_kernels.h; contract and checks: scalar_policy.h) -----------------------
@@ -2078,118 +2106,37 @@ int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out)
    return 1;
 }
 
-// The sampler's calls with the channel walk: behind the cell build the scalars are staged by sorted slot
+// The sampler's calls with the channel sums: behind the cell build the scalars are staged by sorted slot
 // (launch_scalars_stage, channels only), then the probes are walked.
+
+static const char* scalars_refusal(const sph_hip_context* ctx) { return scalar_have_check(ctx->n_scalars); }
+static int scalars_stage_channels(sph_hip_context* ctx) { return launch_scalars_stage(ctx, false); }
 
 int sph_hip_sample_scalars_points(sph_hip_context* ctx, int n, const float* xyz, float* channels4, float* density,
                                   int32_t* count)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   const char* who = "sph_hip_sample_scalars_points";
-   if (n < 0 || (n > 0 && !xyz)) return refuse(ctx, who, "negative count or null probe array");
-   if ((rc = sample_check(ctx, who))) return rc;
-   if (const char* why = scalar_have_check(ctx->n_scalars)) return refuse(ctx, who, why);
-   if (n == 0) return SPH_HIP_OK;
-   if (ctx->n == 0) {
-      if (channels4) memset(channels4, 0, sizeof(float) * 4 * (size_t)n);
-      return sample_zero((size_t)n, density, nullptr, count);
-   }
-   if ((rc = sample_prepare(ctx))) return rc;
-   if ((rc = launch_scalars_stage(ctx, false))) return rc;
+   const SampleCall call = {"sph_hip_sample_scalars_points", {{channels4, 16}, {density, 4}, {count, 4}}, scalars_refusal,
+                            scalars_stage_channels};
    // (36 bytes a probe against the sampler's 32: half its chunk keeps the scratch inside the 64 MiB budget)
-   const int chunk = sample_points_chunk(n, SAMPLE_CHUNK_POINTS / 2);
-   if ((rc = ctx->sample_buf.reserve(ctx, (size_t)chunk * 9))) return rc;
-   // (the channels first: 16-byte stores)
-   float4* schan = reinterpret_cast<float4*>(ctx->sample_buf.get());
-   float* sxyz = ctx->sample_buf.get() + 4 * (size_t)chunk;
-   float* srho = sxyz + 3 * (size_t)chunk;
-   int32_t* scnt = reinterpret_cast<int32_t*>(srho + (size_t)chunk);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
-   hipStream_t st = ctx->stream;
-   for (int p0 = 0; p0 < n; p0 += chunk) {
-      const int m = n - p0 < chunk ? n - p0 : chunk;
-      SPH_TRY(hipMemcpyAsync(sxyz, xyz + 3 * (size_t)p0, sizeof(float) * 3 * m, hipMemcpyHostToDevice, st));
+   return sample_points_run(ctx, call, n, xyz, SAMPLE_CHUNK_POINTS / 2, [&](const float* sxyz, int m, void* const dev[3]) {
       bind_flags([&](auto U) {
-         hipLaunchKernelGGL((k_sample_scalars_points<U.value>), dim3(div_up(m, 256)), dim3(256), 0, st, sxyz, m,
-                            ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start, ctx->grid, k, schan, srho, scnt);
+         sample_points_launch<U.value, ScalarSum>(ctx, sxyz, m, ctx->scalar_Ts,
+                                                  {(float4*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
       }, unit_scale(ctx->prm));
-      SPH_TRY(hipGetLastError());
-      if (channels4)
-         SPH_TRY(hipMemcpyAsync(channels4 + 4 * (size_t)p0, schan, sizeof(float4) * m, hipMemcpyDeviceToHost, st));
-      if (density) SPH_TRY(hipMemcpyAsync(density + p0, srho, sizeof(float) * m, hipMemcpyDeviceToHost, st));
-      if (count) SPH_TRY(hipMemcpyAsync(count + p0, scnt, sizeof(int32_t) * m, hipMemcpyDeviceToHost, st));
-   }
-   SPH_TRY(hipStreamSynchronize(st));
-   return SPH_HIP_OK;
+   });
 }
 
 int sph_hip_sample_scalars_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
                                    const int32_t dims[3], float* channels4, float* density, int32_t* count)
 {
-   int rc = check_ctx(ctx);
-   if (rc) return rc;
-   const char* who = "sph_hip_sample_scalars_lattice";
-   if (const char* why = lattice_check(origin, spacing, dims)) return refuse(ctx, who, why);
-   if ((rc = sample_check(ctx, who))) return rc;
-   if (const char* why = scalar_have_check(ctx->n_scalars)) return refuse(ctx, who, why);
-   if (ctx->n == 0) {
-      const size_t total = (size_t)dims[0] * dims[1] * dims[2];
-      if (channels4) memset(channels4, 0, sizeof(float) * 4 * total);
-      return sample_zero(total, density, nullptr, count);
-   }
-   if ((rc = sample_prepare(ctx))) return rc;
-   if ((rc = launch_scalars_stage(ctx, false))) return rc;
-   double cells[3];
-   sample_spacing_cells(spacing, ctx->grid.inv, cells);
-   const SampleBrick brick = sample_brick(dims, cells);
-   const SampleChunk c = sample_lattice_chunk(dims, brick, SAMPLE_CHUNK_POINTS);
-   const size_t chunk_points = (size_t)c.ex * c.ey * c.ez;
-   if ((rc = ctx->sample_buf.reserve(ctx, chunk_points * 6))) return rc;
-   float4* schan = reinterpret_cast<float4*>(ctx->sample_buf.get());
-   float* srho = ctx->sample_buf.get() + 4 * chunk_points;
-   int32_t* scnt = reinterpret_cast<int32_t*>(srho + chunk_points);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
-   const bool unit = unit_scale(ctx->prm);
-   hipStream_t st = ctx->stream;
-   SampleLattice L = lattice_of(origin, spacing, brick);
-   // (sph_hip_sample_lattice's copy of a chunk's box into the caller's arrays; elem bytes a point)
-   auto copy_out = [&](void* dst, const void* src, size_t elem) -> hipError_t {
-      char* d = (char*)dst;
-      const char* s = (const char*)src;
-      const size_t plane = (size_t)dims[0] * dims[1];
-      if (L.ex == dims[0] && L.ey == dims[1])
-         return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem,
-                               hipMemcpyDeviceToHost, st);
-      for (int z = 0; z < L.ez; z++) {
-         const hipError_t e = hipMemcpy2DAsync(
-             d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
-             s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
-             hipMemcpyDeviceToHost, st);
-         if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
-   };
-   for (L.k0 = 0; L.k0 < dims[2]; L.k0 += c.ez)
-      for (L.j0 = 0; L.j0 < dims[1]; L.j0 += c.ey)
-         for (L.i0 = 0; L.i0 < dims[0]; L.i0 += c.ex) {
-            L.ex = dims[0] - L.i0 < c.ex ? dims[0] - L.i0 : c.ex;
-            L.ey = dims[1] - L.j0 < c.ey ? dims[1] - L.j0 : c.ey;
-            L.ez = dims[2] - L.k0 < c.ez ? dims[2] - L.k0 : c.ez;
-            L.bricks_x = div_up(L.ex, L.bx);
-            L.bricks_y = div_up(L.ey, L.by);
-            const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
-            bind_flags([&](auto U) {
-               hipLaunchKernelGGL((k_sample_scalars_lattice<U.value>), dim3(bricks), dim3(SAMPLE_THREADS), 0, st, L,
-                                  ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start, ctx->grid, k, schan, srho, scnt);
-            }, unit);
-            SPH_TRY(hipGetLastError());
-            if (channels4) SPH_TRY(copy_out(channels4, schan, sizeof(float4)));
-            if (density) SPH_TRY(copy_out(density, srho, sizeof(float)));
-            if (count) SPH_TRY(copy_out(count, scnt, sizeof(int32_t)));
-         }
-   SPH_TRY(hipStreamSynchronize(st));
-   return SPH_HIP_OK;
+   const SampleCall call = {"sph_hip_sample_scalars_lattice", {{channels4, 16}, {density, 4}, {count, 4}}, scalars_refusal,
+                            scalars_stage_channels};
+   return sample_lattice_run(ctx, call, origin, spacing, dims, [&](const SampleLattice& L, int bricks, void* const dev[3]) {
+      bind_flags([&](auto U) {
+         sample_lattice_launch<U.value, ScalarSum>(ctx, L, bricks, ctx->scalar_Ts,
+                                                   {(float4*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
+      }, unit_scale(ctx->prm));
+   });
 }
 
 // ---- iso-surface extractor ------------------------------------------------------------------------
@@ -2246,7 +2193,6 @@ int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const f
    double cells[3];
    sample_spacing_cells(spacing, ctx->grid.inv, cells);
    const SampleBrick brick = sample_brick(dims, cells);
-   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
    hipStream_t st = ctx->stream;
    SPH_TRY(hipMemsetAsync(totals, 0, 4 * sizeof(unsigned long long), st));
@@ -2280,9 +2226,7 @@ int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const f
       L.ez = ks1 - S.ks0;
       const int bricks = L.bricks_x * L.bricks_y * div_up(L.ez, L.bz);
       bind_flags([&](auto U, auto V) {
-         hipLaunchKernelGGL((k_sample_lattice<U.value, V.value, false>), dim3(bricks), dim3(SAMPLE_THREADS), 0, st, L,
-                            ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->grid, k, SAMPLE_TILE_CAP,
-                            srho, svel, scnt);
+         sample_lattice_launch<U.value, SampleSum<V.value>>(ctx, L, bricks, ctx->velp[ctx->cur], {srho, svel, scnt});
       }, unit, vel);
       SPH_TRY(hipGetLastError());
       // 2. classify, 3. scan

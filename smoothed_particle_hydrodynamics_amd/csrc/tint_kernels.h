@@ -8,7 +8,7 @@
 // so the list is per-wave runs of one 8 x 8 tile and most of a wave's lanes here are neighbouring pixels: they
 // walk the same cells through L1 and read the same or adjacent rows of the colour table (identical LDS
 // addresses broadcast).  A lane whose pixel a solid took (first_inside < 0) returns at once.
-//   k_tint_surface   one walk of the channels at the pixel's hit point (sample_walk_scalars: the scalar
+//   k_tint_surface   one walk of the channels at the pixel's hit point (sample_walk with ScalarSum: the scalar
 //                    sampler's bits)
 //   k_tint_column    the march from first_inside to the end of the box, a channel walk at every sample the
 //                    occupancy map does not rule out; rays of a wave differ in length, the loop runs as long
@@ -81,7 +81,7 @@ k_tint_surface(RenderFrame F, TintArgs T, const float4* __restrict__ posm, const
    const float t = depth_in[o];
    const float* eye = F.cam.eye;
    ScalarSum s;
-   sample_walk_scalars<UNIT_SCALE>(eye[0] + t * d[0], eye[1] + t * d[1], eye[2] + t * d[2], posm, Ts, cell_start, g, k,
+   sample_walk<UNIT_SCALE>(eye[0] + t * d[0], eye[1] + t * d[1], eye[2] + t * d[2], posm, Ts, cell_start, g, k,
                                    s);
    const float v = scalar_shepard(tint_channel(s, T.tp.channel), s.rho);
    tint_store<FLAT>(F, T, lds, o, v, normal_in, rgba_out, scalar_out);
@@ -126,7 +126,7 @@ k_tint_column(RenderFrame F, TintArgs T, const float4* __restrict__ posm, const 
          if (!occ[(cz * g.ny + cy) * g.nx + cx]) continue;
       }
       ScalarSum sum;
-      sample_walk_scalars<UNIT_SCALE>(x, y, z, posm, Ts, cell_start, g, k, sum);
+      sample_walk<UNIT_SCALE>(x, y, z, posm, Ts, cell_start, g, k, sum);
       A = tint_column_add(A, sum.rho, tint_channel(sum, channel), iso, step);
    }
    tint_store<FLAT>(F, T, lds, o, A, normal_in, rgba_out, scalar_out);

@@ -24,7 +24,7 @@ struct TracerSampler {
    __device__ __forceinline__ int operator()(float px, float py, float pz, float& ux, float& uy, float& uz) const
    {
       SampleSum<true> s;
-      if (have_particles) sample_walk<UNIT_SCALE, true>(px, py, pz, posm, velp, cell_start, g, k, s);
+      if (have_particles) sample_walk<UNIT_SCALE>(px, py, pz, posm, velp, cell_start, g, k, s);
       // SampleSum::store's normalisation
       const bool pos = s.rho > 0.0f;
       ux = pos ? s.vx / s.rho : 0.0f;

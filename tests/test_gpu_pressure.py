@@ -22,6 +22,7 @@ import gauge_emulation as G
 import pressure_emulation as P
 import sample_emulation as SE
 from helpers import to_oracle_params
+from test_sample_cpu import forced_chunks, policy  # noqa: F401  (policy: the g++ shim of sample_policy.h)
 
 pytestmark = pytest.mark.gpu
 
@@ -211,6 +212,31 @@ def test_lattice_sampler_equals_the_restatement_and_the_point_call(hiplib):
         # the densities and counts are the sampler's
         frho, _, fcnt = sph.sampleLattice(origin, (s, s, s), shape, velocity=False)
         assert same_bits(frho, rho) and same_bits(fcnt, cnt)
+
+
+def test_chunked_samplers_equal_the_unchunked_ones(hiplib, policy, monkeypatch):
+    """SPH_HIP_SAMPLE_CHUNK: the lattice in single bricks (cut along x, y and z: the strided copy-out), the
+    points in three chunks, the last one ragged - every bit as from the one chunk these calls take otherwise"""
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, iso, gauges, field = scene()
+    s = float(F32(0.5) * F32(p.h))
+    origin, shape = (0.1 - 16 * s, 0.75 - 8 * s, 0.4), (33, 17, 9)      # over the column's free corner
+    cut_x = forced_chunks(policy, shape, [s * float(F32(p.full_cell_inv))] * 3)[2]
+    probes = sample_probes()
+    assert 2 * 2000 < len(probes) < 3 * 2000
+    monkeypatch.delenv("SPH_HIP_SAMPLE_CHUNK", raising=False)
+    with fresh(S, "full", gauges=None) as sph:
+        sph.run(2)
+        whole_lattice = sph.samplePressureLattice(origin, (s, s, s), shape)
+        whole_points = sph.samplePressure(probes)
+    assert (whole_lattice[2] > 0).any() and (whole_lattice[2] == 0).any() and (whole_lattice[0] != 0).any()
+    for forced, call, args, whole in ((cut_x, "samplePressureLattice", (origin, (s, s, s), shape), whole_lattice),
+                                      (2000, "samplePressure", (probes,), whole_points)):
+        monkeypatch.setenv("SPH_HIP_SAMPLE_CHUNK", str(forced))
+        with fresh(S, "full", gauges=None) as sph:      # (the switch is read when the context is created)
+            sph.run(2)
+            for a, b in zip(getattr(sph, call)(*args), whole):
+                assert same_bits(a, b), "%s in chunks of %d" % (call, forced)
 
 
 @pytest.mark.parametrize("mode", ["full", "fast"])

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import sample_emulation as E
-from test_sample_cpu import DEFAULT, TILED, policy, tiled  # noqa: F401  (policy: the g++ shim of sample_policy.h)
+from test_sample_cpu import DEFAULT, TILED, forced_chunks, policy, tiled  # noqa: F401  (policy: the g++ shim of sample_policy.h)
 
 pytestmark = pytest.mark.gpu
 
@@ -155,6 +155,63 @@ def test_lattice_slices_and_thin_lattices(dam):
             got = sph.sampleLattice(origin, spacing, shape)
             want = g.sample(E.lattice_points(origin, spacing, shape).reshape(-1, 3))
             assert_fields((got[0].reshape(-1), got[1].reshape(-1, 3), got[2].reshape(-1)), want, str(shape))
+
+
+# ---- 2b. chunks: a forced chunk size changes no bit ------------------------------------------------
+def odd_lattice(p):
+    """surface_lattice with dims that are multiples of no brick"""
+    origin, spacing, _ = surface_lattice(p)
+    return origin, spacing, (37, 45, 19)
+
+
+def test_chunked_lattices_equal_the_unchunked_one(dam, policy, monkeypatch):
+    p = dam[0]
+    origin, spacing, shape = odd_lattice(p)
+    cells = [float(s) * float(F32(p.full_cell_inv)) for s in spacing]
+    cut_z, cut_y, cut_x = forced_chunks(policy, shape, cells)     # (asserts the three chunk shapes)
+    assert tiled(policy, shape, cells, TILED) == 1
+    for env in ("SPH_HIP_SAMPLE_TILED", "SPH_HIP_SAMPLE_UNTILED", "SPH_HIP_SAMPLE_CHUNK"):
+        monkeypatch.delenv(env, raising=False)
+    pts = E.lattice_points(origin, spacing, shape).reshape(-1, 3)
+    with make(dam) as sph:      # (the switches are read when the context is created)
+        whole = sph.sampleLattice(origin, spacing, shape)
+        whole_nv = sph.sampleLattice(origin, spacing, shape, velocity=False)
+        by_points = sph.sampleFields(pts)
+    # the unchunked call is the point sampler's, which test_points_match_the_emulation pins
+    assert_fields((whole[0].reshape(-1), whole[1].reshape(-1, 3), whole[2].reshape(-1)), by_points, "lattice vs points")
+    assert_fields(whole_nv, (whole[0], None, whole[2]), "unchunked without velocity")
+    assert (whole[2] == 0).sum() > 1000 and (whole[2] > 20).sum() > 1000
+    for forced, route in ((cut_z, None), (cut_y, None), (cut_x, None), (cut_x, "SPH_HIP_SAMPLE_TILED")):
+        monkeypatch.setenv("SPH_HIP_SAMPLE_CHUNK", str(forced))
+        monkeypatch.delenv("SPH_HIP_SAMPLE_TILED", raising=False)
+        if route:
+            monkeypatch.setenv(route, "1")
+        what = "chunks of %d, %s" % (forced, route or "default route")
+        with make(dam) as sph:
+            assert_fields(sph.sampleLattice(origin, spacing, shape), whole, what)
+            assert_fields(sph.sampleLattice(origin, spacing, shape, velocity=False), whole_nv, what + ", no velocity")
+
+
+def test_chunked_points_equal_the_unchunked_ones(dam, monkeypatch):
+    p = dam[0]
+    probes = probe_set(p, dam[1].reshape(-1, 3), np.random.default_rng(17), 2000, 426)
+    n = len(probes)
+    assert n == 2500                                   # chunks of 1000, 1000 and 500 probes
+    monkeypatch.delenv("SPH_HIP_SAMPLE_CHUNK", raising=False)
+    with make(dam) as sph:
+        whole = sph.sampleFields(probes)
+    assert (whole[2] == 0).any() and (whole[2][2000:] > 0).any()
+    monkeypatch.setenv("SPH_HIP_SAMPLE_CHUNK", "1000")
+    with make(dam) as sph:
+        assert_fields(sph.sampleFields(probes), whole, "chunks of 1000")
+        assert_fields(sph.sampleFields(probes, velocity=False), (whole[0], None, whole[2]), "chunks of 1000, no velocity")
+        # one output null at a time: the others are written as before, the null one is left alone
+        for skip in range(3):
+            out = [np.full(n, 7, F32), np.full((n, 3), 7, F32), np.full(n, 7, np.int32)]
+            ptrs = [None if i == skip else a.ctypes.data for i, a in enumerate(out)]
+            sph.call("sph_hip_sample_points", n, probes.ctypes.data, *ptrs)
+            for i, (a, w) in enumerate(zip(out, whole)):
+                assert same(a, np.full_like(a, 7) if i == skip else w), "null output %d: output %d" % (skip, i)
 
 
 # ---- 3. arithmetics and refusals ------------------------------------------------------------------

@@ -12,6 +12,7 @@ import pytest
 
 import sample_emulation as SE
 import scalar_emulation as SC
+from test_sample_cpu import forced_chunks, policy  # noqa: F401  (policy: the g++ shim of sample_policy.h)
 
 pytestmark = pytest.mark.gpu
 
@@ -314,6 +315,43 @@ def test_samplers_equal_the_restatement(hiplib, mode):
     assert same(lchan.reshape(-1, 4), lwant[0]) and same(lrho.reshape(-1), lwant[1])
     assert np.array_equal(lcnt.reshape(-1), lwant[2])
     assert (lcnt == 0).sum() > 50 and (lcnt > 0).sum() > 10 and not lchan[lcnt == 0].any()
+
+
+def test_chunked_samplers_equal_the_unchunked_ones(hiplib, policy, monkeypatch):
+    """SPH_HIP_SAMPLE_CHUNK: the lattice in single bricks (cut along x, y and z: the strided copy-out of 16-byte
+    elements), the points in three chunks, the last one ragged - every bit as from the one chunk these calls
+    take otherwise"""
+    import smoothed_particle_hydrodynamics_amd as S
+    p, pos, vel, mass, T, kappa = block_scene()
+    xyz = pos.reshape(-1, 3)
+    h = F32(p.h)
+    spacing = (float(h / F32(2)),) * 3
+    origin = tuple(float(c) for c in xyz.min(0) - h)          # from outside the column into it
+    shape = (19, 21, 11)
+    cut_x = forced_chunks(policy, shape, [spacing[0] * float(F32(p.full_cell_inv))] * 3)[2]
+    rng = np.random.default_rng(5)
+    probes = np.concatenate([xyz[rng.integers(0, N, 500)] + rng.uniform(-0.5, 0.5, (500, 3)).astype(F32) * h,
+                             rng.uniform(0.4, 0.9, (98, 3)).astype(F32),
+                             np.array([[np.nan, 0.1, 0.1], [-5.0, 0.2, 0.2]], F32)]).astype(F32)
+    assert len(probes) == 600                                 # chunks of 256, 256 and 88 probes
+
+    def sampled(forced):
+        monkeypatch.delenv("SPH_HIP_SAMPLE_CHUNK", raising=False)
+        if forced:
+            monkeypatch.setenv("SPH_HIP_SAMPLE_CHUNK", str(forced))
+        with S.SPH(N, p, mode=S.MODE_FULL) as sph:      # (the switch is read when the context is created)
+            sph.setParticles(pos, vel, mass)
+            sph.setScalars(T, kappa)
+            sph.run(3)
+            return sph.sampleScalarLattice(origin, spacing, shape), sph.sampleScalars(probes)
+
+    whole_lattice, whole_points = sampled(None)
+    assert (whole_lattice[2] > 0).sum() > 100 and (whole_lattice[2] == 0).sum() > 100 and whole_lattice[0].any()
+    assert (whole_points[2] > 0).sum() > 400 and (whole_points[2] == 0).sum() > 50
+    lattice, _ = sampled(cut_x)
+    _, points = sampled(256)
+    for got, whole, what in ((lattice, whole_lattice, "lattice in chunks of %d" % cut_x), (points, whole_points, "points in chunks of 256")):
+        assert same(got[0], whole[0]) and same(got[1], whole[1]) and np.array_equal(got[2], whole[2]), what
 
 
 # ---- refusals on the device ------------------------------------------------------------------------------------------

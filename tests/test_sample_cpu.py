@@ -46,6 +46,8 @@ void lattice_chunk(const int* dims, const int* brick, long long max_points, int*
    out[0] = c.ex; out[1] = c.ey; out[2] = c.ez;
 }
 int points_chunk(int n, int max_points) { return sample_points_chunk(n, max_points); }
+int chunk_forced(long long value) { return sample_chunk_forced(value); }
+int chunk_limit(int limit, int forced) { return sample_chunk_limit(limit, forced); }
 long long budget() { return SAMPLE_SCRATCH_BUDGET; }
 const char* check(const float* origin, const float* spacing, const int32_t* dims)
 {
@@ -64,6 +66,7 @@ def policy(tmp_path_factory):
     lib.brick_of.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.brick_of.restype = C.c_longlong
     lib.budget.restype = C.c_longlong
+    lib.chunk_forced.argtypes = [C.c_longlong]
     lib.check.argtypes = [C.c_void_p] * 3
     lib.check.restype = C.c_char_p
     return lib
@@ -90,6 +93,25 @@ def chunk(policy, dims, most, shape=(8, 8, 4)):
     out = (C.c_int * 3)()
     policy.lattice_chunk((C.c_int * 3)(*dims), (C.c_int * 3)(*shape), most, out)
     return tuple(out)
+
+
+def forced_chunks(policy, dims, cells):
+    """Three values of SPH_HIP_SAMPLE_CHUNK for the lattice `dims` (spacing `cells` cell edges): the chunks of
+    the first cut the lattice along z only (whole planes), those of the second along y as well (whole
+    x-rows), those of the third along x too - one layer, one row, one single brick at a time.  The shapes
+    are asserted here on sample_lattice_chunk, and that the clamp leaves the values alone."""
+    nx, ny, nz = dims
+    shape, _ = brick(policy, dims, cells)
+    bx, by, bz = shape
+    assert bx < nx and by < ny and bz < nz, "the lattice must exceed its brick %r along every axis" % (shape,)
+    values = (nx * ny * bz, nx * bz * by, bx * by * bz)
+    cut_z, cut_y, cut_x = (chunk(policy, dims, v, shape) for v in values)
+    assert cut_z == (nx, ny, bz)
+    assert cut_y == (nx, by, bz)
+    assert cut_x == (bx, by, bz)
+    for v in values:
+        assert policy.chunk_forced(v) == v
+    return values
 
 
 # ---- C ABI -------------------------------------------------------------------------------------
@@ -313,6 +335,33 @@ def test_lattice_chunks_cover_whole_bricks_within_the_bound(policy, dims, shape)
     # a chunk that does not span an axis is made of whole bricks along it
     for e, d, b in zip((ex, ey, ez), dims, shape):
         assert e == d or e % b == 0
+
+
+def test_forced_chunk_is_clamped(policy):
+    """SPH_HIP_SAMPLE_CHUNK: 0 (and anything below) is off; otherwise at least one brick, at most the limit"""
+    most = policy.chunk_points()
+    assert policy.threads() == 256 and most == 1 << 21
+    for off in (0, -1, -(1 << 40)):
+        assert policy.chunk_forced(off) == 0
+    for low in (1, 2, 255, 256):
+        assert policy.chunk_forced(low) == 256
+    for v in (257, 1000, most - 1, most):
+        assert policy.chunk_forced(v) == v
+    for high in (most + 1, 1 << 31, 1 << 40):
+        assert policy.chunk_forced(high) == most
+    # a call keeps a smaller limit of its own (the scalar point sampler: half the limit)
+    assert policy.chunk_limit(most, 0) == most and policy.chunk_limit(most // 2, 0) == most // 2
+    assert policy.chunk_limit(most, 1000) == 1000 and policy.chunk_limit(most // 2, 1000) == 1000
+    assert policy.chunk_limit(most // 2, most) == most // 2 and policy.chunk_limit(most, most) == most
+    # at the smallest forced value a lattice chunk is one whole brick of every shape, never empty
+    for i in range(policy.n_bricks()):
+        shape = (C.c_int * 3)()
+        policy.brick_table(i, shape)
+        assert chunk(policy, (100, 100, 100), 256, tuple(shape)) == tuple(shape)
+
+
+def test_forced_chunks_cut_along_z_then_y_then_x(policy):
+    assert forced_chunks(policy, (37, 45, 19), (0.25, 0.25, 0.25)) == (37 * 45 * 4, 37 * 4 * 8, 256)
 
 
 def test_point_chunks(policy):

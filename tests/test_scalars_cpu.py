@@ -270,7 +270,15 @@ def test_the_host_calls_refuse_in_the_headers_words():
     for check in ("scalar_context_check", "scalar_set_check", "scalar_source_check", "scalar_have_check",
                   "scalar_range_check"):
         assert check in body
-    assert body.count("sample_check(ctx, who)") == 3          # REF and slab contexts: the sampler's own refusals
+    # REF and slab contexts: the sampler's own refusals - in sph_hip_set_scalars itself, and for the two sampler
+    # calls in the samplers' shared driver, which asks sample_check first and the call's own refusal next
+    assert body.count("sample_check(ctx, who)") == 1
+    assert body.count("scalars_refusal,") == 2 and "return scalar_have_check(ctx->n_scalars);" in body
+    assert "sample_points_run(ctx, call," in body and "sample_lattice_run(ctx, call," in body
+    driver = text[text.index("int sample_refusals("):text.index("int sample_zero(")]
+    assert 0 < driver.index("sample_check(ctx, c.who)") < driver.index("c.refusal(ctx)")
+    for run in ("int sample_points_run(", "int sample_lattice_run("):
+        assert "sample_refusals(ctx, c," in text[text.index(run):text.index(run) + 600]
     ports = text[text.index("int sph_hip_set_ports("):text.index("int sph_hip_get_ports(")]
     assert "scalar_ports_check(ctx->n_scalars, ne, ns)" in ports
     upload = text[text.index("static int upload_impl("):text.index("static int all_same_mass(")]
