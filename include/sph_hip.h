@@ -837,14 +837,16 @@ int sph_hip_get_bodies(sph_hip_context* ctx, sph_hip_body* list, sph_hip_body_st
  *   contexts   FULL and FULL_FAST contexts that hold the whole grid: what the field sampler accepts, with
  *              the sampler's refusals for REF and slab contexts.
  *   advance    step k advances every tracer once, after that step's cell build and before anything moves
- *              the particles, in the state S_k the sampler would see at that moment, with dt = time_step as
+ *              the particles, in the state S_k the sampler would see at that moment, with the particles'
+ *              displacement step pos_dt = time_step * sim_scale_inv (the integrate moves a particle by
+ *              vh * pos_dt; at unit scale pos_dt is time_step itself) - one fp32 product of the parameters
  *              in force when the step is enqueued (by value: a later setter does not reach queued steps).
  *              sample(S, p) is sph_hip_sample_points at p: Shepard velocity u and member count c.
  *                1  (u1, c1) = sample(S_k, x)
  *                2  c1 == 0: the tracer is dry this step - x unchanged, dry_steps += 1, done
- *                3  half = 0.5f * dt; xm_c = x_c + u1_c * half; (u2, c2) = sample(S_k, xm);
+ *                3  half = 0.5f * pos_dt; xm_c = x_c + u1_c * half; (u2, c2) = sample(S_k, xm);
  *                   u = c2 > 0 ? u2 : u1
- *                4  y_c = x_c + u_c * dt; if any y_c is not finite the tracer is dry as in 2
+ *                4  y_c = x_c + u_c * pos_dt; if any y_c is not finite the tracer is dry as in 2
  *                5  apply_walls: y_c < 0 gives y_c = 0, y_c > max_c gives y_c = max_c - a clamp, not the
  *                   particles' reflection: a marker has no momentum
  *                6  x = y; wet_steps += 1

@@ -761,7 +761,8 @@ int launch_tracers(sph_hip_context* ctx)
       }
    }
    const sph_hip_params& p = ctx->prm;
-   const TracerStep ts = {p.time_step, p.apply_walls, {p.max_x, p.max_y, p.max_z}, ctx->n > 0 ? 1 : 0};
+   const float pos_dt = p.time_step * p.sim_scale_inv;   // the integrate's displacement step (common_kernels.h)
+   const TracerStep ts = {pos_dt, p.apply_walls, {p.max_x, p.max_y, p.max_z}, ctx->n > 0 ? 1 : 0};
    const PairConsts k = pair_consts(p, ctx->fast != 0);
    bind_flags([&](auto U) {
       hipLaunchKernelGGL((k_tracers_advance<U.value>), dim3(div_up(n, 256)), dim3(256), 0, ctx->stream,

@@ -188,25 +188,18 @@ int sample_points_run(sph_hip_context* ctx, const SampleCall& c, int n, const fl
    return SPH_HIP_OK;
 }
 
-// A chunk's outputs are a box of the caller's arrays (elem bytes a point): one copy per z-plane, or one
-// for the lot when the chunk spans whole planes.
-hipError_t sample_copy_box(void* dst, const void* src, size_t elem, const SampleLattice& L, const int32_t dims[3],
-                           hipStream_t st)
+// A chunk's outputs are a box of the caller's arrays (elem bytes a point); a chunk that spans whole planes is
+// one contiguous piece of them.  Any other chunk is brought over contiguous as well, into `src` on the host,
+// and its x-rows are dealt out to their places in the box here.
+void sample_deal_box(void* dst, const void* src, size_t elem, const SampleLattice& L, const int32_t dims[3])
 {
    char* d = (char*)dst;
    const char* s = (const char*)src;
-   const size_t plane = (size_t)dims[0] * dims[1];
-   if (L.ex == dims[0] && L.ey == dims[1])
-      return hipMemcpyAsync(d + (size_t)L.k0 * plane * elem, s, (size_t)L.ex * L.ey * L.ez * elem, hipMemcpyDeviceToHost,
-                            st);
-   for (int z = 0; z < L.ez; z++) {
-      const hipError_t e = hipMemcpy2DAsync(
-          d + (((size_t)(L.k0 + z) * dims[1] + L.j0) * dims[0] + L.i0) * elem, (size_t)dims[0] * elem,
-          s + (size_t)z * L.ey * L.ex * elem, (size_t)L.ex * elem, (size_t)L.ex * elem, (size_t)L.ey,
-          hipMemcpyDeviceToHost, st);
-      if (e != hipSuccess) return e;
-   }
-   return hipSuccess;
+   const size_t row = (size_t)L.ex * elem;
+   for (int z = 0; z < L.ez; z++)
+      for (int y = 0; y < L.ey; y++)
+         memcpy(d + (((size_t)(L.k0 + z) * dims[1] + L.j0 + y) * dims[0] + L.i0) * elem,
+                s + ((size_t)z * L.ey + y) * row, row);
 }
 
 // a lattice, in chunks of whole bricks (sample_lattice_chunk); launch(the chunk, its bricks, the outputs' arrays)
@@ -228,6 +221,23 @@ int sample_lattice_run(sph_hip_context* ctx, const SampleCall& c, const float or
    if ((rc = sample_carve(ctx, c, (size_t)ch.ex * ch.ey * ch.ez, false, s))) return rc;
    hipStream_t st = ctx->stream;
    SampleLattice L = lattice_of(origin, spacing, brick);
+   // Chunks of whole planes are copied straight into the caller's arrays, every copy behind its kernel on the
+   // stream.  A chunk cut along x or y comes over contiguous too, into a host buffer of this call, and its rows
+   // are dealt out here once the stream has drained.  (One strided hipMemcpy2DAsync per z-plane into the
+   // caller's arrays stood here; a whole-suite run ended in one of them with "an illegal memory access", as
+   // three had in sph_hip_get_loads' strided copies before: DESIGN.md sections 29 and 30.)
+   const bool whole_planes = ch.ex == dims[0] && ch.ey == dims[1];
+   std::vector<char> stage[3];
+   if (!whole_planes) {
+      try {
+         for (int i = 0; i < 3; i++)
+            if (c.out[i].host) stage[i].resize((size_t)ch.ex * ch.ey * ch.ez * c.out[i].bytes);
+      } catch (const std::bad_alloc&) {
+         ctx->err = std::string(c.who) + ": no host memory for a chunk of the lattice";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+   }
+   const size_t plane = (size_t)dims[0] * dims[1];
    for (L.k0 = 0; L.k0 < dims[2]; L.k0 += ch.ez)
       for (L.j0 = 0; L.j0 < dims[1]; L.j0 += ch.ey)
          for (L.i0 = 0; L.i0 < dims[0]; L.i0 += ch.ex) {
@@ -238,8 +248,16 @@ int sample_lattice_run(sph_hip_context* ctx, const SampleCall& c, const float or
             L.bricks_y = div_up(L.ey, L.by);
             launch(L, L.bricks_x * L.bricks_y * div_up(L.ez, L.bz), s.dev);
             SPH_TRY(hipGetLastError());
+            const size_t points = (size_t)L.ex * L.ey * L.ez;
+            for (int i = 0; i < 3; i++) {
+               if (!c.out[i].host) continue;
+               void* to = whole_planes ? (char*)c.out[i].host + (size_t)L.k0 * plane * c.out[i].bytes : stage[i].data();
+               SPH_TRY(hipMemcpyAsync(to, s.dev[i], points * c.out[i].bytes, hipMemcpyDeviceToHost, st));
+            }
+            if (whole_planes) continue;
+            SPH_TRY(hipStreamSynchronize(st));
             for (int i = 0; i < 3; i++)
-               if (c.out[i].host) SPH_TRY(sample_copy_box(c.out[i].host, s.dev[i], c.out[i].bytes, L, dims, st));
+               if (c.out[i].host) sample_deal_box(c.out[i].host, stage[i].data(), c.out[i].bytes, L, dims);
          }
    SPH_TRY(hipStreamSynchronize(st));
    return SPH_HIP_OK;

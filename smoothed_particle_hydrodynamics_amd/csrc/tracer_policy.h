@@ -6,12 +6,15 @@
 //
 // The contract.  All arithmetic is fp32, unfused, in the order written.  sample(S, p) is the field
 // sampler's walk at p over the state S with velocity (sample_kernels.h: sample_walk and SampleSum::store's
-// normalisation): the Shepard velocity u and the member count c.  One advance of a tracer at x with the
-// time step dt, in the state S_k the step's cell build has just sorted:
+// normalisation): the Shepard velocity u and the member count c.  A tracer moves as a particle does: the
+// integrate displaces a particle by vh * (dt * sim_scale_inv) (common_kernels.h: pos_dt), so the advance uses
+// that same displacement step pos_dt = dt * sim_scale_inv - one fp32 product, formed once on the host when
+// the step is enqueued (launch.h: launch_tracers); at unit scale it is dt itself.  One advance of a tracer at
+// x, in the state S_k the step's cell build has just sorted:
 //   1  (u1, c1) = sample(S_k, x)
 //   2  c1 == 0: the tracer is dry this step - x unchanged, dry_steps += 1, done
-//   3  half = 0.5f * dt; xm_c = x_c + u1_c * half; (u2, c2) = sample(S_k, xm); u = c2 > 0 ? u2 : u1
-//   4  y_c = x_c + u_c * dt; any y_c not finite: dry, as in 2
+//   3  half = 0.5f * pos_dt; xm_c = x_c + u1_c * half; (u2, c2) = sample(S_k, xm); u = c2 > 0 ? u2 : u1
+//   4  y_c = x_c + u_c * pos_dt; any y_c not finite: dry, as in 2
 //   5  apply_walls: y_c < 0 -> y_c = 0; y_c > max_c -> y_c = max_c (a clamp: a marker has no momentum)
 //   6  x = y; wet_steps += 1
 // The midpoint rule in the velocity field frozen at the start of the step.
@@ -35,7 +38,7 @@ TRACER_HD inline bool tracer_finite(float v) { return fabsf(v) <= 3.402823466e38
 
 // what one advance needs besides the state: by value in the kernel's arguments
 struct TracerStep {
-   float dt;
+   float pos_dt;         // dt * sim_scale_inv: the integrate's displacement step
    int apply_walls;
    float maxv[3];
    int have_particles;   // 0: nothing resident, every tracer is dry (the cell arrays may be stale)
@@ -54,7 +57,7 @@ TRACER_HD TRACER_INLINE inline bool tracer_move(float& x0, float& x1, float& x2,
       const int c = sample(p0, p1, p2, t0, t1, t2);
       if (trip == 0) {
          if (c == 0) return false;
-         const float half = 0.5f * st.dt;
+         const float half = 0.5f * st.pos_dt;
          u0 = t0;
          u1 = t1;
          u2 = t2;
@@ -67,7 +70,7 @@ TRACER_HD TRACER_INLINE inline bool tracer_move(float& x0, float& x1, float& x2,
          u2 = t2;
       }
    }
-   float y0 = x0 + u0 * st.dt, y1 = x1 + u1 * st.dt, y2 = x2 + u2 * st.dt;
+   float y0 = x0 + u0 * st.pos_dt, y1 = x1 + u1 * st.pos_dt, y2 = x2 + u2 * st.pos_dt;
    if (!(tracer_finite(y0) && tracer_finite(y1) && tracer_finite(y2))) return false;
    if (st.apply_walls) {
       if (y0 < 0.0f) y0 = 0.0f;

@@ -33,10 +33,10 @@ struct Canned {
 
 extern "C" {
 void advance(float* x, int32_t* wet, int32_t* dry, const float* u1, const int* c1, const float* u2, const int* c2,
-             const float* dt, const int* walls, const float* maxv, float* xm, int* probes, int m)
+             const float* pos_dt, const int* walls, const float* maxv, float* xm, int* probes, int m)
 {
    for (int k = 0; k < m; k++) {
-      const TracerStep st = {dt[k], walls[k], {maxv[0], maxv[1], maxv[2]}, 1};
+      const TracerStep st = {pos_dt[k], walls[k], {maxv[0], maxv[1], maxv[2]}, 1};
       const Canned s = {u1 + 3 * k, c1[k], u2 + 3 * k, c2[k], xm + 3 * k, 0};
       tracer_advance(x[3 * k], x[3 * k + 1], x[3 * k + 2], wet[k], dry[k], st, s);
       probes[k] = s.calls;
@@ -94,8 +94,17 @@ def ptr(a):
 MAXV = np.array([1.0, 2.0, 1.5], F32)
 
 
+class Scale:
+    """the one parameter displacement_step reads"""
+
+    def __init__(self, sim_scale_inv):
+        self.sim_scale_inv = sim_scale_inv
+
+
 def canned_cases(seed=5, m=4000):
-    """Random probe answers around the box [0, MAXV]: every branch of steps 2 to 5 among them."""
+    """Random probe answers around the box [0, MAXV]: every branch of steps 2 to 5 among them.  dt is the
+    displacement step the advance is handed (tracer_emulation.displacement_step): the time step at unit scale,
+    and from row 1400 on what sim_scale_inv = 2 and 0.5 make of it."""
     rng = np.random.default_rng(seed)
     x = (rng.random((m, 3)) * MAXV).astype(F32)
     u1 = rng.normal(0.0, 3.0, (m, 3)).astype(F32)
@@ -126,6 +135,8 @@ def canned_cases(seed=5, m=4000):
     dt[1200:1300] = F32(0.0)                       # dt == 0: wet, in place
     x[1300:1320] = 0.0                             # on the faces themselves
     x[1320:1340] = MAXV
+    dt[1400:2000] = T.displacement_step(Scale(2.0), F32(0.02))    # off unit scale: twice and half the time step
+    dt[2000:2600] = T.displacement_step(Scale(0.5), F32(0.02))
     wet0 = rng.integers(0, 100, m).astype(np.int32)
     dry0 = rng.integers(0, 100, m).astype(np.int32)
     return x, wet0, dry0, u1, c1, u2, c2, dt, walls
@@ -156,6 +167,10 @@ def test_advance_matches_the_restatement_bit_for_bit(policy):
                 taken[k] += int(np.asarray(getattr(info, k)).sum())
     # every branch was there to be compared
     assert all(v > 0 for v in taken.values()), taken
+    # the displacement steps off unit scale were among them, and they are one fp32 product
+    assert np.unique(dt).tolist() == [0.0, float(F32(0.01)), float(F32(0.02)), float(F32(0.04)), float(F32(3.0e38))]
+    assert T.displacement_step(Scale(1.0), F32(0.02)) == F32(0.02)
+    assert T.displacement_step(Scale(3.0), F32(0.1)).tobytes() == (F32(0.1) * F32(3.0)).tobytes()
     assert (gw + gd == wet0 + dry0 + 1).all()
     # walls off: some tracer is outside the box afterwards; dt == 0: wet and exactly in place
     off = walls == 0
@@ -264,6 +279,50 @@ def test_uniform_translation_carries_every_wet_tracer_at_v(hiplib):
     slack = bound(np.maximum(c1, c2)) * float(dt) + 2 * eps * (np.abs(want) + abs(float(dt)) * np.abs(v))
     assert not p.apply_walls
     assert (np.abs(st.x[both].astype(np.float64) - want[both]) <= slack[both]).all()
+
+
+def carried_check(p, x0, count, tracers_after, particles_after, particles_before):
+    """The property of scale_cases.carried_scene: (holds, worst excess over the bound) of tracers set on particles,
+    one step on, against those particles' new positions."""
+    import scale_cases
+    bound = scale_cases.carried_bound(p, count, np.concatenate([particles_before, particles_after]))
+    err = np.abs(np.asarray(tracers_after, np.float64) - np.asarray(particles_after, np.float64))
+    return bool((err <= bound).all()), float((err / bound).max())
+
+
+def test_tracers_are_carried_off_unit_scale(oracle, hiplib):
+    """sim_scale_inv = 2, a fluid in uniform translation without forces: after one step a tracer set on a particle
+    lies on that particle's new position - the oracle's -, within the rounding of the Shepard quotient and of the
+    move.  The arithmetic that advances a tracer by u * dt (sim_scale_inv left out) misses it by |v0_c| * dt."""
+    import scale_cases
+    from helpers import to_oracle_params
+    p, pos, vel, mass, rows = scale_cases.carried_scene()
+    x0 = pos.reshape(-1, 3)[rows].copy()
+    st, info = T.advance(p, pos, vel, mass, T.initial(x0), p.time_step, with_info=True)
+    count = SE.Grid(p, pos, vel, mass).sample(x0, velocity=False)[2]
+    assert info.wet.all() and (count > 8).all()
+    opos, ovel = pos.copy(), vel.copy()
+    out = oracle.step(to_oracle_params(p), opos, ovel, mass, mode="full")
+    assert not out["acc"].any()                    # every acceleration is exactly zero
+    after = opos.reshape(-1, 3)[rows]
+    # the oracle alone: a particle goes where x + v0 * pos_dt says, within the bound's last two roundings
+    pos_dt = float(T.displacement_step(p, p.time_step))
+    exact = x0.astype(np.float64) + np.array(scale_cases.V0, np.float64) * pos_dt
+    assert carried_check(p, x0, np.zeros(len(rows)), exact, after, x0)[0]
+    assert pos_dt == 2.0 * float(F32(p.time_step))
+    ok, worst = carried_check(p, x0, count, st.x, after, x0)
+    assert ok, worst
+    # the old contract - the time step where the displacement step belongs: sim_scale_inv = 1 in the move, the
+    # samples' arithmetic unchanged (sim_scale is still 0.5)
+    q = p.copy()
+    q.sim_scale_inv = 1.0
+    assert not SE.unit_scale(q)
+    old = T.advance(q, pos, vel, mass, T.initial(x0), p.time_step)
+    ok_old, worst_old = carried_check(p, x0, count, old.x, after, x0)
+    assert not ok_old and worst_old > 1000.0
+    # and at unit scale the displacement step is the time step, bit for bit
+    q.sim_scale = 1.0
+    assert T.displacement_step(q, p.time_step).tobytes() == F32(p.time_step).tobytes()
 
 
 def test_no_particles_every_tracer_is_dry(hiplib):
