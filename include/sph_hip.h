@@ -1137,6 +1137,41 @@ typedef struct sph_hip_buoyancy {   /* field order is ABI: 44 bytes */
 int sph_hip_set_buoyancy(sph_hip_context* ctx, const sph_hip_buoyancy* b);
 int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out);
 
+/* ---- cohesion ----------------------------------------------------------------------------------- *
+ *
+ * A pairwise surface tension that holds the fluid together (Becker and Teschner 2007): with rho0 below every
+ * density the pressure only ever pushes the fluid apart; cohesion pulls every particle towards its neighbours,
+ * which cancels inside the fluid and points inward at a free surface.  No counterpart in the reference.  The
+ * operation-by-operation contract is in csrc/cohesion_policy.h; all arithmetic is fp32, unfused, in the order
+ * written.
+ *   sum        for particle i of a step's state S_k, over its neighbours j (the acceleration pass's pairs, in
+ *              canonical order): s = s + t_j * (r_i - r_j) per component from 0, t_j the density pass's pair term
+ *              m_j * (kernel1 * (hscaled2 - d*d)^3), d = sqrtf(d2) * sim_scale (the field sampler's term, above),
+ *              the separation times sim_scale too.
+ *   force      c = (-gamma) * s per component.  The terms of (i, j) and (j, i) are each other's negation: with equal
+ *              masses momentum is conserved.  A negative gamma is a repulsion and is allowed.
+ *   guard      a particle whose c is zero in every component, or not finite in any, is left alone: not a bit of
+ *              it changes, -0.0f included.
+ *   a step     behind the step's acceleration pass, before buoyancy and the integrate: a' = clamp(a + c), the
+ *              acceleration pass's own cfl_limit rule applied again.  The velocity is not touched.  The
+ *              acceleration read back after the step is a' (with buoyancy: what buoyancy made of a').
+ *   modes      FULL and FULL_FAST give the same c bits.
+ *   route      a cohesive context gives up the fused integrate (it keeps the prehash) and launches one more
+ *              kernel per step.  Obstacles, motions, paths, bodies, load recordings, gauges, tracers, carried
+ *              scalars and buoyancy work beside it unchanged.  A context without cohesion enqueues exactly what
+ *              it always did.
+ *   not done   the stand-alone phase calls (sph_hip_compute_density .. sph_hip_integrate) and the slab steps do
+ *              NOT apply cohesion.
+ * sph_hip_set_cohesion sets gamma for the steps enqueued from now on; it does not wait, and steps already queued
+ * keep the gamma they were enqueued with.  gamma == 0 switches cohesion off and is never refused.
+ * SPH_HIP_ERR_INVALID, the previous setting kept, for a gamma that is not finite, a REF or a slab context, and a
+ * context with ports; sph_hip_set_ports refuses ports on a context with cohesion.  A new sph_hip_upload drops the
+ * setting.  sph_hip_get_cohesion stores the gamma in force, 0 when none is.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no existing
+ * prototype changed. */
+int sph_hip_set_cohesion(sph_hip_context* ctx, float gamma);
+int sph_hip_get_cohesion(sph_hip_context* ctx, float* gamma);
+
 /* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
  *
  * A particle count that changes while the steps stay queued: emitters append whole lattice layers

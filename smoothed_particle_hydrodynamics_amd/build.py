@@ -20,6 +20,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "load_policy.h", "body_policy.h", "tracer_kernels.h", "tracer_policy.h",
            "gauge_kernels.h", "gauge_policy.h", "pressure_kernels.h",
            "scalar_kernels.h", "scalar_policy.h", "buoyancy_kernels.h", "buoyancy_policy.h",
+           "cohesion_kernels.h", "cohesion_policy.h",
            os.path.join("..", "..", "include", "sph_hip.h")]
 
 # -ffp-contract=off: the reference's x86-64 IEEE build has no FMA contraction; neighbour

@@ -28,6 +28,7 @@
 #include "pressure_kernels.h"
 #include "scalar_kernels.h"
 #include "buoyancy_kernels.h"
+#include "cohesion_kernels.h"
 #include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
@@ -427,6 +428,10 @@ struct sph_hip_context {
    // buoyancy (sph_hip_set_buoyancy): the setting the next enqueued steps take by value; dropped with the scalars
    int have_buoyancy = 0;
    sph_hip_buoyancy buoyancy = {};
+
+   // cohesion (sph_hip_set_cohesion): the gamma the next enqueued steps take by value; dropped by an upload
+   int have_cohesion = 0;
+   float cohesion_gamma = 0.0f;
 
    // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
    // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the

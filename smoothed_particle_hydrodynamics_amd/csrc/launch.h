@@ -917,6 +917,24 @@ int launch_buoyancy(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- cohesion (cohesion_kernels.h; contract: cohesion_policy.h; decision: launch_policy.h) --------------------
+// Behind the step's acceleration pass, in front of buoyancy and the integrate: acc of the sorted state S_k, with the
+// lists and counts the step's density pass left.  gamma and the constants travel by value: a later setter does not
+// reach the steps already queued.  Nothing synchronises.
+int launch_cohesion(sph_hip_context* ctx)
+{
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   static_assert(TILE_THREADS == 256, "the cohesion kernel maps one workgroup to 256 sorted particles");
+   bind_flags([&](auto U, auto W) {
+      hipLaunchKernelGGL((k_cohesion_apply<U.value, W.value>), dim3(div_up(ctx->n, TILE_THREADS)), dim3(TILE_THREADS), 0,
+                         ctx->stream, ctx->posm[ctx->cur], ctx->ncount, ctx->cell_start, ctx->meta, ctx->grid, k,
+                         ctx->cohesion_gamma, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, ctx->list_cap,
+                         ctx->use_tiled ? 1 : 0, ctx->acc);
+   }, unit_scale(ctx->prm), ctx->caps.wide != 0);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
 // buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
 // (prehashed: 1 whole grid, 2 a slab's owned entries).
@@ -1016,9 +1034,13 @@ int step_impl(sph_hip_context* ctx, bool timed)
                          !ports_no_prehash(ctx->no_prehash != 0, ctx->n_emit, ctx->n_sink);
    // buoyancy: one kernel between the acceleration pass and the integrate, so the step gives up the fused integrate
    const bool buoyant = step_launches_buoyancy(ctx->have_buoyancy != 0, ctx->n_scalars, ctx->n);
-   const bool fused = fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
+   // cohesion: one more such kernel, in front of buoyancy's - either of them takes the step off the fused route
+   const bool cohesive = step_launches_cohesion(ctx->have_cohesion != 0, ctx->n);
+   const bool fused = !cohesive &&
+                      fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
                                      loads_pending(ctx), buoyant);
    if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;
+   if (cohesive && (rc = launch_cohesion(ctx))) return rc;
    if (buoyant && (rc = launch_buoyancy(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;
    if (fused) fused_step_done(ctx, 1);

@@ -258,8 +258,9 @@ inline PlaneRanges plane_ranges(int plane_lo, int plane_hi, int z0, int nz, int 
 // exchanged, prehash allowed), the tiled kernels, particles to move, no SPH_HIP_NO_FUSED_INTEGRATE,
 // and no static obstacles - their response runs in k_integrate_obst, the fused kernels stay as tuned.
 // record_loads: the step fills a row of a load recording (sph_hip_record_loads), which only
-// k_integrate_loads does.  buoyancy: the step launches k_buoyancy_apply (step_launches_buoyancy), which stands
-// between the acceleration pass and the integrate; such a step keeps the prehash, in k_integrate<HASH>.
+// k_integrate_loads does.  buoyancy: the step launches a kernel that stands between the acceleration pass and the
+// integrate - k_buoyancy_apply (step_launches_buoyancy), k_cohesion_apply (step_launches_cohesion) or both; such a
+// step keeps the prehash, in k_integrate<HASH>.
 inline bool fuse_integrate(bool hash_too, bool tiled, int n, bool no_fused_integrate, int n_obstacles,
                            bool record_loads = false, bool buoyancy = false)
 {
@@ -367,6 +368,11 @@ inline bool step_launches_buoyancy(bool have_buoyancy, int n_scalars, int n)
 {
    return have_buoyancy && step_launches_scalars(n_scalars, n);
 }
+
+// Whether a step launches k_cohesion_apply (cohesion_policy.h) between its acceleration pass and its integrate, in
+// front of buoyancy's kernel: a gamma is set and the step has particles.  Such a step gives up the fused integrate
+// (fuse_integrate's last argument).  A context without cohesion launches what it always launched.
+inline bool step_launches_cohesion(bool have_cohesion, int n) { return have_cohesion && n > 0; }
 
 // Whether a frame launches the tint pass (k_scalars_stage once, then k_tint_surface or k_tint_column per row
 // chunk: tint_kernels.h): the caller is sph_hip_render_scalars and a particle is resident.  Without a particle

@@ -568,6 +568,7 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    ctx->n_scalars = 0;
    ctx->n_scalar_sources = 0;
    ctx->have_buoyancy = 0;   // (buoyancy reads the scalars: it goes with them)
+   ctx->have_cohesion = 0;   // cohesion is a setting of the upload it was made for
    ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
    ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
    ports_mass_rule(ctx, n == 0);
@@ -1336,6 +1337,7 @@ int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int
       return refuse(ctx, who, "slab contexts (with neighbours, or that have exchanged) cannot have ports");
    if (const char* why = port_check(emitters, ne, sinks, ns, port_grid(ctx))) return refuse(ctx, who, why);
    if (const char* why = scalar_ports_check(ctx->n_scalars, ne, ns)) return refuse(ctx, who, why);
+   if (const char* why = cohesion_ports_check(ctx->have_cohesion != 0, ne, ns)) return refuse(ctx, who, why);
    // a pending prehash counted for a build whose entries the ports may change first
    if ((rc = drop_prehash(ctx))) return rc;
    // steps already queued keep the lists they were enqueued with: the copies go behind them
@@ -2122,6 +2124,34 @@ int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out)
    if (!out) return refuse(ctx, "sph_hip_get_buoyancy", "null output");
    *out = ctx->buoyancy;
    return 1;
+}
+
+// ---- cohesion (cohesion_kernels.h; contract and checks: cohesion_policy.h) -------------------------------
+
+int sph_hip_set_cohesion(sph_hip_context* ctx, float gamma)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_cohesion";
+   if (const char* why = cohesion_gamma_check(gamma)) return refuse(ctx, who, why);
+   if (!cohesion_is_off(gamma)) {   // (switching it off is never refused)
+      const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global && !ctx->had_exchange;
+      if (const char* why = cohesion_context_check(ctx->mode == SPH_HIP_MODE_FULL, whole)) return refuse(ctx, who, why);
+      if (const char* why = cohesion_ports_set_check(ports_active(ctx->n_emit, ctx->n_sink))) return refuse(ctx, who, why);
+   }
+   // (a step takes gamma by value: the steps already queued keep theirs)
+   ctx->have_cohesion = cohesion_is_off(gamma) ? 0 : 1;
+   ctx->cohesion_gamma = ctx->have_cohesion ? gamma : 0.0f;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_cohesion(sph_hip_context* ctx, float* gamma)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!gamma) return refuse(ctx, "sph_hip_get_cohesion", "null output");
+   *gamma = ctx->have_cohesion ? ctx->cohesion_gamma : 0.0f;
+   return SPH_HIP_OK;
 }
 
 // The sampler's calls with the channel sums: behind the cell build the scalars are staged by sorted slot

@@ -186,6 +186,8 @@ PROTOTYPES = {
                                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_set_buoyancy": (C.c_int, [_ctx, _P(SphBuoyancy)]),
     "sph_hip_get_buoyancy": (C.c_int, [_ctx, _P(SphBuoyancy)]),
+    "sph_hip_set_cohesion": (C.c_int, [_ctx, C.c_float]),
+    "sph_hip_get_cohesion": (C.c_int, [_ctx, _P(C.c_float)]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -580,6 +580,43 @@ def lock_exchange(n, beta=-0.2, depth=0.3, box=(1.0, 1.0, 1.0), neighbors=32.0, 
     return p, pos, vel, mass, values, kappa, [], Buoyancy(beta, 0.0, tuple(p.gravity))
 
 
+# the gamma at which the median cohesive acceleration of droplet(3000)'s shell particles is about the median
+# acceleration the pressure gives them (cohesion, "The droplet")
+DROPLET_GAMMA = 3.0e-6
+
+
+def droplet(n, gamma=DROPLET_GAMMA, neighbors=32.0, cells=None, seed=42):
+    """A blob of fluid held together by cohesion alone: n particles at rest, a cubic random fill in the middle of
+    the box at the density that gives ~`neighbors` particles inside radius h, gravity and the central mass off,
+    the walls on.  The box is `cells` voxels of edge 2h on a side; the smoothing length is the dam column's at
+    this n (dam_break_h), the cube's edge what the density asks for.  Without cohesion the pressure - repulsive at
+    every density with the reference's rho0 - blows the blob apart.  Returns (params, pos, vel, mass, gamma):
+    setParticles, then setCohesion."""
+    h = np.float32(dam_break_h(n, neighbors=neighbors))
+    number_density = 3.0 * neighbors / (4.0 * math.pi * float(h) ** 3)
+    edge = (n / number_density) ** (1.0 / 3.0)
+    if cells is None:   # the blob and its own width of room around it
+        cells = max(8, int(math.ceil(edge / float(h))))
+    p = default_params(float(h), [cells] * 3)
+    p.central_mass = 0.0
+    p.apply_gravity = 0
+    p.apply_walls = 1
+    mid = [0.5 * float(m) for m in (p.max_x, p.max_y, p.max_z)]
+    if not edge + 2.0 * float(h) < 2.0 * min(mid):
+        raise ValueError("the box is too small for this blob: more cells")
+    pos = box_fill(n, [m - 0.5 * edge for m in mid], [m + 0.5 * edge for m in mid], seed)
+    return p, pos, np.zeros(3 * n, np.float32), np.ones(n, np.float32), float(gamma)
+
+
+def dam_break_cohesive(n, gamma, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42,
+                       gravity=-9.81):
+    """The surging dam of dam_break_dye without the dye - gravity along -y, the walls on, the surge along +x - with
+    cohesion: the tongue that otherwise frays into single particles holds together.  Returns (params, pos, vel,
+    mass, gamma): setParticles, then setCohesion."""
+    p, pos, vel, mass, _ = dam_break_dye(n, 1.0, surge, box, fill, neighbors, seed, gravity)
+    return p, pos, vel, mass, float(gamma)
+
+
 def dyed_cut_box(p):
     """The marched box (lo, hi) that cuts the tank of dam_break_dyed and heated_floor at its mid-plane z = max_z / 2:
     the renderer's default box - the domain grown by h - with its far side in z moved to the middle.  A camera

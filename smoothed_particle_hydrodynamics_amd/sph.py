@@ -595,6 +595,20 @@ class SPH(Context):
         b = _S.SphBuoyancy()
         return _S.buoyancy_from_struct(b) if self.call("sph_hip_get_buoyancy", C.byref(b)) == 1 else None
 
+    # ---- cohesion (sph_hip_set_cohesion) ----------------------------------------------------------
+    def setCohesion(self, gamma):
+        """A pairwise surface tension from the next enqueued step on (include/sph_hip.h: cohesion): every particle
+        takes -gamma * sum_j t_j * (r_i - r_j) on top of its own acceleration, t_j the density sum's pair term - it
+        cancels inside the fluid and pulls a free surface inward.  None or 0 switches it off; a negative gamma
+        pushes apart.  FULL and FULL_FAST contexts without ports; a new setParticles drops it."""
+        self.call("sph_hip_set_cohesion", C.c_float(0.0 if gamma is None else float(gamma)))
+
+    def getCohesion(self):
+        """The gamma in force, 0.0 when cohesion is off."""
+        g = C.c_float(0.0)
+        self.call("sph_hip_get_cohesion", C.byref(g))
+        return float(g.value)
+
     def sampleScalars(self, points):
         """The carried scalars of the current state at `points` ((n, 3) float32): (channels[n, 4], density[n],
         count[n]) - the Shepard-normalised sums over the sampler's members, 0 where there are none.  The
