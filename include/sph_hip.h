@@ -1172,6 +1172,66 @@ int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out);
 int sph_hip_set_cohesion(sph_hip_context* ctx, float gamma);
 int sph_hip_get_cohesion(sph_hip_context* ctx, float* gamma);
 
+/* ---- step monitor ------------------------------------------------------------------------------- *
+ *
+ * Per-step stability and conservation rows, filled on the device while the steps stay queued: at which step a run
+ * left its limits, and what time step it should have had.  No counterpart in the reference.  The
+ * operation-by-operation contract is in csrc/monitor_policy.h; all arithmetic is fp32, unfused, in the order
+ * written, and everything a row holds is a maximum, a minimum, a count or an integer sum: its bits do not depend
+ * on the route a context takes (tiled or not, fused integrate or not, list capacities) nor on the run.
+ *   a row      describes one step: the step's densities, neighbour counts and final accelerations (behind cohesion
+ *              and buoyancy), and the positions, velocities and carried channels the step PRODUCED.
+ *   bad        a particle whose position, velocity, acceleration (x, y, z each) or density is not finite, or whose
+ *              density is negative: counted in `bad`, its id offered to bad_id_min (0xffffffff: none), and left
+ *              out of every other field but live, s_max and pair_bad.
+ *   ranges     v2 = (vx*vx + vy*vy) + vz*vz and a2 likewise; v2_max, a2_max, rho_max, rho_min, ncount_max, and
+ *              lone = the particles without a neighbour.  Floats are compared by the ordered integer key of their
+ *              bits: -0.0f < +0.0f, and the winner's bits do not depend on the order of comparison.  A range over
+ *              no value is 0.
+ *   sums       momentum[c] = sum llrint(m*v_c * 2^-q), kinetic = sum llrint(((0.5f*m)*v2) * 2^-q), mass =
+ *              sum llrint(m * 2^-q), q = quantum_log2, the rule of sph_hip_record_loads; a particle with a term
+ *              that is not finite or reaches 2^38 quanta adds to none of them and counts in `skipped`.
+ *   scalars    (flags bit 0) scalar_min / scalar_max over the finite values of each channel as the step left
+ *              them; scalar_bad = the particles with a channel that is not finite.
+ *   diffusion  (flags bit 1) s_max = the maximum over the particles of S_p = sum_j V_j * kernel3 * (hscaled -
+ *              d_ij), the scalar pass's own weights in its own order: dt * kappa[c] * s_max <= 1 is the condition
+ *              under which the pass is a convex combination.  pair_bad counts the S_p that are not finite.
+ * Fields that are not valid (a context without scalars) hold zeros.
+ * sph_hip_record_monitor keeps `rows` rows on the device: steps are numbered 1, 2, ... from the call, and step s
+ * fills row (s - 1) / every when every divides s - 1 and the row exists; only such steps launch anything new.
+ * rows = 0 stops and frees the recording.  The call does not wait unless it replaces a recording.
+ * SPH_HIP_ERR_INVALID, the previous recording kept, for rows < 0, every < 1, a quantum_log2 outside [-64, 32], a
+ * REF or a slab context, and a context with ports; sph_hip_set_ports and the slab exchange refuse a context with a
+ * recording.  The recording survives sph_hip_set_params, sph_hip_set_arithmetic and uploads.  The stand-alone phase
+ * calls do not record.
+ * sph_hip_get_monitor_record synchronises, copies rows [first_row, first_row + n_rows) of the rows filled so far
+ * into out (may be null with n_rows 0) and the number of the step each describes into steps (may be null);
+ * returns the number of filled rows, SPH_HIP_ERR_INVALID for a range that leaves them.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no existing
+ * prototype changed. */
+#define SPH_HIP_MONITOR_SCALARS_VALID 1u
+#define SPH_HIP_MONITOR_DIFFUSION_VALID 2u
+typedef struct sph_hip_monitor_row {   /* field order is ABI: 128 bytes */
+   int64_t momentum[3];    /* quanta of 2^quantum_log2 */
+   int64_t kinetic;
+   int64_t mass;
+   int32_t live;           /* slots visited */
+   int32_t bad;
+   int32_t skipped;
+   int32_t lone;
+   int32_t ncount_max;
+   int32_t scalar_bad;
+   int32_t pair_bad;
+   uint32_t bad_id_min;
+   float v2_max, a2_max, rho_max, rho_min, s_max;
+   float scalar_min[4];
+   float scalar_max[4];
+   uint32_t flags;
+} sph_hip_monitor_row;
+int sph_hip_record_monitor(sph_hip_context* ctx, int rows, int every, int quantum_log2);
+int sph_hip_get_monitor_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_monitor_row* out,
+                               int32_t* steps);
+
 /* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
  *
  * A particle count that changes while the steps stay queued: emitters append whole lattice layers

@@ -21,6 +21,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "gauge_kernels.h", "gauge_policy.h", "pressure_kernels.h",
            "scalar_kernels.h", "scalar_policy.h", "buoyancy_kernels.h", "buoyancy_policy.h",
            "cohesion_kernels.h", "cohesion_policy.h",
+           "monitor_kernels.h", "monitor_policy.h",
            os.path.join("..", "..", "include", "sph_hip.h")]
 
 # -ffp-contract=off: the reference's x86-64 IEEE build has no FMA contraction; neighbour

@@ -29,6 +29,7 @@
 #include "scalar_kernels.h"
 #include "buoyancy_kernels.h"
 #include "cohesion_kernels.h"
+#include "monitor_kernels.h"
 #include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
@@ -432,6 +433,17 @@ struct sph_hip_context {
    // cohesion (sph_hip_set_cohesion): the gamma the next enqueued steps take by value; dropped by an upload
    int have_cohesion = 0;
    float cohesion_gamma = 0.0f;
+
+   // step monitor (sph_hip_record_monitor): mon_rows rows; mon_step = steps enqueued since the call, mon_filled =
+   // rows those steps have filled, mon_row_now = the row the step being enqueued fills (-1: none).  The partial
+   // rows of the particle kernel's bounded grid and of the pair pass's workgroups (one per 256 particles of the
+   // capacity) are allocated with the recording; queued steps reuse them in stream order.
+   DevBuf<sph_hip_monitor_row> mon_dev;
+   DevBuf<MonitorAcc> mon_part;
+   DevBuf<MonitorPairAcc> mon_pair_part;
+   int mon_rows = 0, mon_every = 1, mon_filled = 0, mon_quantum = LOAD_QUANTUM_DEFAULT;
+   long long mon_step = 0;
+   int mon_row_now = -1;
 
    // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
    // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the

@@ -935,6 +935,47 @@ int launch_cohesion(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- step monitor (monitor_kernels.h; contract: monitor_policy.h; grid: launch_policy.h) ------------------------
+// Counts the step of a recording and picks the row it fills (mon_row_now, -1: none); on such a step of a context
+// whose scalar pass has just run, k_monitor_pairs directly behind that pass, with the volumes it staged.  The
+// constants travel by value.  Nothing synchronises.
+int launch_monitor_pairs(sph_hip_context* ctx)
+{
+   const int r = monitor_record_row(++ctx->mon_step, ctx->mon_every, ctx->mon_rows);
+   ctx->mon_row_now = r;
+   if (r < 0 || !monitor_launches_pairs(ctx->n_scalars, ctx->n)) return SPH_HIP_OK;
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   static_assert(TILE_THREADS == 256, "the monitor's pair kernel maps one workgroup to 256 sorted particles");
+   bind_flags([&](auto U, auto W) {
+      hipLaunchKernelGGL((k_monitor_pairs<U.value, W.value>), dim3(div_up(ctx->n, TILE_THREADS)), dim3(TILE_THREADS), 0,
+                         ctx->stream, ctx->posm[ctx->cur], ctx->scalar_Vs, ctx->ncount, ctx->cell_start, ctx->meta,
+                         ctx->grid, k, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, ctx->list_cap,
+                         ctx->use_tiled ? 1 : 0, ctx->scalar_force_rows, ctx->mon_pair_part);
+   }, unit_scale(ctx->prm), ctx->caps.wide != 0);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
+// The row mon_row_now of the step whose integrate has just been enqueued (on either route: posm / velp of ctx->cur
+// are what the step produced): k_monitor_particles over the live range the integrate took, then k_monitor_finish
+// into the row, whose address travels as a kernel argument.  Nothing synchronises.
+int launch_monitor(sph_hip_context* ctx)
+{
+   const int r = ctx->mon_row_now;
+   ctx->mon_row_now = -1;
+   const int blocks = monitor_grid(ctx->n);
+   const bool pairs = monitor_launches_pairs(ctx->n_scalars, ctx->n);
+   hipLaunchKernelGGL(k_monitor_particles, dim3(blocks), dim3(MONITOR_THREADS), 0, ctx->stream, ctx->posm[ctx->cur],
+                      ctx->velp[ctx->cur], ctx->acc, ctx->rho, ctx->ncount, ctx->meta,
+                      pairs ? ctx->scalar_T.get() : (const float4*)nullptr, ctx->n_scalars, ctx->mon_quantum, ctx->mon_part);
+   hipLaunchKernelGGL(k_monitor_finish, dim3(1), dim3(MONITOR_THREADS), 0, ctx->stream, ctx->mon_part, blocks,
+                      ctx->mon_pair_part, pairs ? div_up(ctx->n, TILE_THREADS) : 0, pairs ? 1 : 0,
+                      ctx->mon_dev.get() + (size_t)r);
+   SPH_TRY(hipGetLastError());
+   ctx->mon_filled = r + 1;
+   return SPH_HIP_OK;
+}
+
 // The fused acceleration pass did the rest of the step (FusedStep): the new state is in the other
 // buffers, its energy partials one pair per tiled workgroup, and the next build's hash done
 // (prehashed: 1 whole grid, 2 a slab's owned entries).
@@ -1026,6 +1067,7 @@ int step_impl(sph_hip_context* ctx, bool timed)
    // the pressure kinds of a row this step fills: with the densities of S_k the pass has just formed
    if (ctx->grec_row_now >= 0 && (rc = launch_gauges_pressure(ctx, gauge_density_source(true)))) return rc;
    if (ctx->n_scalars > 0 && (rc = launch_scalars(ctx))) return rc;   // carried scalars: in S_k, with its densities and lists
+   if (ctx->mon_rows > 0 && (rc = launch_monitor_pairs(ctx))) return rc;   // step monitor: the step is counted, its row picked
    if ((rc = mark_phase(ctx, se, 3, st))) return rc;
    // a context that holds the whole grid and has never exchanged anything: the integrate also
    // hashes and counts for the next cell build - and the tiled acceleration pass does both itself
@@ -1045,6 +1087,7 @@ int step_impl(sph_hip_context* ctx, bool timed)
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;
    if (fused) fused_step_done(ctx, 1);
    else if ((rc = launch_integrate(ctx, hash_too))) return rc;
+   if (ctx->mon_row_now >= 0 && (rc = launch_monitor(ctx))) return rc;   // step monitor: the row of the state just produced
    return mark_phase(ctx, se, 6, st);
 }
 

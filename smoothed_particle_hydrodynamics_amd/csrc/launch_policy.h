@@ -374,6 +374,22 @@ inline bool step_launches_buoyancy(bool have_buoyancy, int n_scalars, int n)
 // (fuse_integrate's last argument).  A context without cohesion launches what it always launched.
 inline bool step_launches_cohesion(bool have_cohesion, int n) { return have_cohesion && n > 0; }
 
+// ---- step monitor (monitor_policy.h) ---------------------------------------------------------------
+// The grid of k_monitor_particles: workgroups of MONITOR_THREADS lanes that stride over the live slots, one per 256
+// slots up to MONITOR_MAX_BLOCKS - a bounded number of partial rows, which one workgroup folds (k_monitor_finish).
+// At least one, so that a step without particles still writes its (empty) row.
+#define MONITOR_THREADS 256
+#define MONITOR_MAX_BLOCKS 1024
+inline int monitor_grid(int n)
+{
+   const long long want = ((long long)(n > 0 ? n : 0) + MONITOR_THREADS - 1) / MONITOR_THREADS;
+   return want < 1 ? 1 : want > MONITOR_MAX_BLOCKS ? MONITOR_MAX_BLOCKS : (int)want;
+}
+
+// Whether a step that fills a monitor row launches k_monitor_pairs behind its scalar pass: exactly when that pass
+// ran (step_launches_scalars), whose staged volumes it reads.
+inline bool monitor_launches_pairs(int n_scalars, int n) { return step_launches_scalars(n_scalars, n); }
+
 // Whether a frame launches the tint pass (k_scalars_stage once, then k_tint_surface or k_tint_column per row
 // chunk: tint_kernels.h): the caller is sph_hip_render_scalars and a particle is resident.  Without a particle
 // there is no fluid pixel to tint; sph_hip_render and sph_hip_render_scene launch what they always launched.

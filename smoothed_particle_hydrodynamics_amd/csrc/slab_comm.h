@@ -37,6 +37,13 @@ int refuse_paths(sph_hip_context* ctx)
    return SPH_HIP_ERR_INVALID;
 }
 
+// a step monitor (monitor_policy.h) reads the whole-grid arrays of one context: a context that records one cannot be a slab
+int refuse_monitor(sph_hip_context* ctx)
+{
+   ctx->err = monitor_exchange_check(ctx->mon_rows);
+   return SPH_HIP_ERR_INVALID;
+}
+
 int slab_pack(sph_hip_context* ctx, void* left_device, void* right_device,
                       int capacity_records)
 {
@@ -45,6 +52,7 @@ int slab_pack(sph_hip_context* ctx, void* left_device, void* right_device,
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
    if (ctx->n_paths > 0) return refuse_paths(ctx);
    if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
+   if (monitor_exchange_check(ctx->mon_rows)) return refuse_monitor(ctx);
    hipStream_t st = ctx->stream;
    ctx->had_exchange = 1;
    if ((rc = drop_prehash(ctx))) return rc;
@@ -68,6 +76,7 @@ int slab_unpack(sph_hip_context* ctx, const void* left_device, const void* right
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
    if (ctx->n_paths > 0) return refuse_paths(ctx);
    if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
+   if (monitor_exchange_check(ctx->mon_rows)) return refuse_monitor(ctx);
    ctx->had_exchange = 1;
    // (a slab's fused step has hashed its owned entries for the next build, which hashes what is
    // unpacked here: that stays; a whole-grid prehash knows nothing of new entries)
@@ -89,6 +98,7 @@ int slab_step_begin(sph_hip_context* ctx, void* left_device, void* right_device,
    if (ctx->n_bodies > 0) return refuse_bodies(ctx);
    if (ctx->n_paths > 0) return refuse_paths(ctx);
    if (ports_active(ctx->n_emit, ctx->n_sink)) return refuse_ports(ctx);
+   if (monitor_exchange_check(ctx->mon_rows)) return refuse_monitor(ctx);
    if (!ctx->use_tiled) {
       ctx->err = "sph_hip_slab_step_begin: needs the tiled kernels (SPH_HIP_UNTILED is set)";
       return SPH_HIP_ERR_INVALID;

@@ -1338,6 +1338,7 @@ int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int
    if (const char* why = port_check(emitters, ne, sinks, ns, port_grid(ctx))) return refuse(ctx, who, why);
    if (const char* why = scalar_ports_check(ctx->n_scalars, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = cohesion_ports_check(ctx->have_cohesion != 0, ne, ns)) return refuse(ctx, who, why);
+   if (const char* why = monitor_ports_check(ctx->mon_rows, ne, ns)) return refuse(ctx, who, why);
    // a pending prehash counted for a build whose entries the ports may change first
    if ((rc = drop_prehash(ctx))) return rc;
    // steps already queued keep the lists they were enqueued with: the copies go behind them
@@ -2152,6 +2153,72 @@ int sph_hip_get_cohesion(sph_hip_context* ctx, float* gamma)
    if (!gamma) return refuse(ctx, "sph_hip_get_cohesion", "null output");
    *gamma = ctx->have_cohesion ? ctx->cohesion_gamma : 0.0f;
    return SPH_HIP_OK;
+}
+
+// ---- step monitor (monitor_kernels.h; contract and checks: monitor_policy.h) ------------------------------
+
+static void stop_monitor_recording(sph_hip_context* ctx)
+{
+   ctx->mon_dev.reset();
+   ctx->mon_part.reset();
+   ctx->mon_pair_part.reset();
+   ctx->mon_rows = ctx->mon_filled = 0;
+   ctx->mon_every = 1;
+   ctx->mon_quantum = LOAD_QUANTUM_DEFAULT;
+   ctx->mon_step = 0;
+   ctx->mon_row_now = -1;
+}
+
+int sph_hip_record_monitor(sph_hip_context* ctx, int rows, int every, int quantum_log2)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_record_monitor";
+   if (const char* why = monitor_rows_check(rows)) return refuse(ctx, who, why);
+   if (const char* why = monitor_every_check(every)) return refuse(ctx, who, why);
+   if (const char* why = monitor_quantum_check(quantum_log2)) return refuse(ctx, who, why);
+   if (rows > 0) {   // (stopping a recording is never refused)
+      const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global && !ctx->had_exchange;
+      if (const char* why = monitor_mode_check(ctx->mode == SPH_HIP_MODE_FULL)) return refuse(ctx, who, why);
+      if (const char* why = monitor_slab_check(whole)) return refuse(ctx, who, why);
+      if (const char* why = monitor_ports_set_check(ports_active(ctx->n_emit, ctx->n_sink))) return refuse(ctx, who, why);
+   }
+   DevBuf<sph_hip_monitor_row> fresh;
+   DevBuf<MonitorAcc> part;
+   DevBuf<MonitorPairAcc> pair_part;
+   const size_t pair_blocks = (size_t)div_up(ctx->capacity > 0 ? ctx->capacity : 1, TILE_THREADS);
+   if (rows > 0 && (dev_alloc(fresh, (size_t)rows) != hipSuccess || dev_alloc(part, (size_t)MONITOR_MAX_BLOCKS) != hipSuccess ||
+                    dev_alloc(pair_part, pair_blocks) != hipSuccess)) {
+      (void)hipGetLastError();
+      ctx->err = "sph_hip_record_monitor: cannot allocate " + std::to_string(rows) + " rows";
+      return SPH_HIP_ERR_CAPACITY;
+   }
+   // steps already queued may still be writing the rows this call replaces
+   if (ctx->mon_dev) SPH_TRY(hipStreamSynchronize(ctx->stream));
+   stop_monitor_recording(ctx);
+   if (rows > 0) {
+      ctx->mon_dev = std::move(fresh);
+      ctx->mon_part = std::move(part);
+      ctx->mon_pair_part = std::move(pair_part);
+      ctx->mon_rows = rows;
+      ctx->mon_every = every;
+      ctx->mon_quantum = quantum_log2;
+   }
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_monitor_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_monitor_row* out, int32_t* steps)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = monitor_range_check(first_row, n_rows, ctx->mon_filled))
+      return refuse(ctx, "sph_hip_get_monitor_record", why);
+   SPH_TRY(hipStreamSynchronize(ctx->stream));
+   if (out && n_rows > 0)
+      SPH_TRY(hipMemcpy(out, ctx->mon_dev.get() + (size_t)first_row, sizeof(sph_hip_monitor_row) * (size_t)n_rows,
+                        hipMemcpyDeviceToHost));
+   for (int r = 0; steps && r < n_rows; r++) steps[r] = monitor_record_step(first_row + r, ctx->mon_every);
+   return ctx->mon_filled;
 }
 
 // The sampler's calls with the channel sums: behind the cell build the scalars are staged by sorted slot

@@ -19,6 +19,7 @@ from . import obstacles as _O
 from . import ports as _P
 from . import scalars as _S
 from . import colormaps as _CM
+from . import monitor as _M
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, SphTintParams, TracerPath, Tracers, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "ScalarRenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
@@ -608,6 +609,25 @@ class SPH(Context):
         g = C.c_float(0.0)
         self.call("sph_hip_get_cohesion", C.byref(g))
         return float(g.value)
+
+    # ---- step monitor (sph_hip_record_monitor) ------------------------------------------------------
+    def recordMonitor(self, rows, every=1, quantum_log2=_M.QUANTUM_DEFAULT):
+        """Keep a row of stability and conservation figures for the step after this call and every `every`-th
+        step from it, `rows` times, on the device (include/sph_hip.h: step monitor): peak speed and acceleration,
+        the density range, neighbour counts, particles that are not finite, the carried channels' range and
+        diffusion sum, and momentum, kinetic energy and mass as integer sums in quanta of 2^quantum_log2.  Queued
+        steps stay queued; rows = 0 stops and frees the recording.  FULL and FULL_FAST contexts without ports."""
+        self.call("sph_hip_record_monitor", int(rows), int(every), int(quantum_log2))
+        self._monitor_quantum = int(quantum_log2)
+
+    def getMonitorRecord(self):
+        """The rows filled so far, as a monitor.MonitorRecord (sph_hip_get_monitor_record; synchronises)."""
+        rows = self.call("sph_hip_get_monitor_record", 0, 0, None, None)
+        out = np.zeros(rows, _M.ROW)
+        steps = np.zeros(rows, np.int32)
+        if rows:
+            self.call("sph_hip_get_monitor_record", 0, rows, _ptr(out), _ptr(steps))
+        return _M.MonitorRecord(out, steps, getattr(self, "_monitor_quantum", _M.QUANTUM_DEFAULT))
 
     def sampleScalars(self, points):
         """The carried scalars of the current state at `points` ((n, 3) float32): (channels[n, 4], density[n],
