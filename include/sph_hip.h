@@ -1232,6 +1232,58 @@ int sph_hip_record_monitor(sph_hip_context* ctx, int rows, int every, int quantu
 int sph_hip_get_monitor_record(sph_hip_context* ctx, int first_row, int n_rows, sph_hip_monitor_row* out,
                                int32_t* steps);
 
+/* ---- velocity gradients --------------------------------------------------------------------------- *
+ *
+ * Where the flow rotates, compresses and shears: the vorticity, the divergence, the strain rate and the Q criterion
+ * of every particle, at particles, at probes, on lattices and in a frame.  No counterpart in the reference.  The
+ * gradient is a weighted least-squares fit over the particle's neighbours (the renormalised gradient of Randles and
+ * Libersky 1996), G = B * inverse(M) with B = sum_j w_j (v_i - v_j) (x) (r_i - r_j), M = sum_j w_j (r_i - r_j) (x)
+ * (r_i - r_j) and w_j the density pass's pair term: it reads no density and is exact on a linear velocity field for
+ * any neighbourhood whose M can be inverted, one-sided ones at a free surface or a wall included.  The
+ * operation-by-operation contract is in csrc/velgrad_policy.h; all arithmetic is fp32, unfused, in the order written.
+ *   members    the acceleration pass's pairs of the current state, in canonical order; at least 3 are needed
+ *   valid      det M > 2^-10 * (tr M / 3)^3: 1 for an isotropic neighbourhood, 0 for a coplanar one
+ *   rows       rotation   = (w_x, w_y, w_z, div), w = curl v, div = div v
+ *              invariants = (strain, Q, |w|, valid): strain = sqrt(2 S:S), Q = (|O|^2 - |S|^2) / 2 with S and O the
+ *              symmetric and antisymmetric parts of G, valid = 1.0f
+ *              A particle that is not valid, or with a value that is not finite, holds +0.0f in all eight.
+ *   units      the separations are taken times sim_scale, as the density pass takes its distances: G is the gradient
+ *              per unit of scaled length, and a field v = A x gives G = A / sim_scale.
+ *   modes      FULL and FULL_FAST give the same bits.
+ *   no cache  every call below runs a cell build of the current state and forms the rows anew; no particle,
+ *              density, neighbour list or clock changes by a bit, and a context that never calls them enqueues
+ *              exactly what it always did.
+ * sph_hip_get_velocity_gradients synchronises and copies rows [first, first + n) in particle-id order (either
+ * output may be null).  SPH_HIP_ERR_INVALID for a range that leaves the particles, a REF or a slab context, and a
+ * context whose ids ports have changed, until its next upload (sph_hip_download's rule).
+ * sph_hip_sample_velocity_gradients_points / _lattice are sph_hip_sample_scalars_points / _lattice with the rows in
+ * the place of the channels: group 0 samples `rotation`, group 1 `invariants`; a probe's value is the
+ * Shepard-normalised sum over its members, so a sampled `valid` is the weighted share of valid particles around
+ * it.  Allowed on a context with ports.
+ * sph_hip_render_velocity_gradients is sph_hip_render_scalars with tp->channel carrying a quantity
+ * SPH_HIP_VELGRAD_* in the place of a channel; the context needs no carried scalars.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no existing
+ * prototype changed. */
+#define SPH_HIP_VELGRAD_VORTICITY_X 0
+#define SPH_HIP_VELGRAD_VORTICITY_Y 1
+#define SPH_HIP_VELGRAD_VORTICITY_Z 2
+#define SPH_HIP_VELGRAD_DIVERGENCE 3
+#define SPH_HIP_VELGRAD_STRAIN_RATE 4
+#define SPH_HIP_VELGRAD_Q 5
+#define SPH_HIP_VELGRAD_VORTICITY_MAGNITUDE 6
+#define SPH_HIP_VELGRAD_VALID 7
+int sph_hip_get_velocity_gradients(sph_hip_context* ctx, int first, int n, float* rotation4, float* invariants4);
+int sph_hip_sample_velocity_gradients_points(sph_hip_context* ctx, int n, const float* xyz, int group, float* channels4,
+                                             float* density, int32_t* count);
+int sph_hip_sample_velocity_gradients_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                                              const int32_t dims[3], int group, float* channels4, float* density,
+                                              int32_t* count);
+int sph_hip_render_velocity_gradients(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                                      const sph_hip_scene_params* sp, const float* solid_albedo_rgb, int n_albedo,
+                                      const sph_hip_tint_params* tp, const float* table_rgb, int width, int height,
+                                      int flags, uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
+                                      int32_t* first_inside, int32_t* solid_id, float* scalar);
+
 /* ---- ports: inflow emitters and outflow sinks ------------------------------------------------- *
  *
  * A particle count that changes while the steps stay queued: emitters append whole lattice layers

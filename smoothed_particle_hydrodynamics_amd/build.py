@@ -22,6 +22,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "scalar_kernels.h", "scalar_policy.h", "buoyancy_kernels.h", "buoyancy_policy.h",
            "cohesion_kernels.h", "cohesion_policy.h",
            "monitor_kernels.h", "monitor_policy.h",
+           "velgrad_kernels.h", "velgrad_policy.h",
            os.path.join("..", "..", "include", "sph_hip.h")]
 
 # -ffp-contract=off: the reference's x86-64 IEEE build has no FMA contraction; neighbour

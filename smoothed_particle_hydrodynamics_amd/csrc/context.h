@@ -30,6 +30,7 @@
 #include "buoyancy_kernels.h"
 #include "cohesion_kernels.h"
 #include "monitor_kernels.h"
+#include "velgrad_kernels.h"
 #include "port_kernels.h"
 #include "slab_kernels.h"
 #include "slab_rccl.h"
@@ -444,6 +445,11 @@ struct sph_hip_context {
    int mon_rows = 0, mon_every = 1, mon_filled = 0, mon_quantum = LOAD_QUANTUM_DEFAULT;
    long long mon_step = 0;
    int mon_row_now = -1;
+
+   // velocity gradients (sph_hip_get_velocity_gradients and its samplers and renderer): the two rows of every sorted
+   // slot, (w_x, w_y, w_z, div) and (strain, Q, |w|, valid); both hold the capacity and are allocated at the first
+   // call.  Nothing is cached: every call forms them anew behind its cell build.
+   DevBuf<float4> velgrad_A, velgrad_B;
 
    // ports (sph_hip_set_ports): the lists the next enqueued steps use, staged and copied like the obstacle
    // list; the schedule (port steps taken, layers fired per emitter), the id the next new particle gets, the

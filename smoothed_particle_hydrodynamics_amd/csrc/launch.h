@@ -814,6 +814,35 @@ int launch_particle_density(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- velocity gradients (velgrad_kernels.h; contract: velgrad_policy.h) ----------------------------------------
+// The two rows of every sorted slot of the current sorted state into the context's own arrays (allocated here at
+// the first use): behind a cell build, outside a step.  The constants travel by value.  Writes nothing else, and
+// nothing synchronises.
+int launch_velgrad(sph_hip_context* ctx)
+{
+   const int n = ctx->n;
+   if (n == 0) return SPH_HIP_OK;
+   if (!ctx->velgrad_A || !ctx->velgrad_B) {
+      DevBuf<float4> a, b;
+      if (dev_alloc(a, (size_t)ctx->capacity) != hipSuccess || dev_alloc(b, (size_t)ctx->capacity) != hipSuccess) {
+         (void)hipGetLastError();
+         ctx->err = "velocity gradients: cannot allocate the rows of " + std::to_string(ctx->capacity) + " particles";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      ctx->velgrad_A = std::move(a);
+      ctx->velgrad_B = std::move(b);
+   }
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   static_assert(TILE_THREADS == 256, "the velocity-gradient kernel maps one workgroup to 256 sorted particles");
+   bind_flags([&](auto U) {
+      hipLaunchKernelGGL((k_velgrad_particles<U.value>), dim3(div_up(n, TILE_THREADS)), dim3(TILE_THREADS), 0, ctx->stream,
+                         ctx->posm[ctx->cur], ctx->velp[ctx->cur], ctx->cell_start, ctx->meta, ctx->grid, k,
+                         ctx->velgrad_A.get(), ctx->velgrad_B.get());
+   }, unit_scale(ctx->prm));
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // The pressure kinds: k_gauges_pressure into `row`, with the particle densities of `source`
 // (launch_policy.h: gauge_density_source).  A set without a pressure kind launches nothing.
 int launch_gauges_pressure_into(sph_hip_context* ctx, sph_hip_gauge_reading* row, int source)

@@ -2254,6 +2254,82 @@ int sph_hip_sample_scalars_lattice(sph_hip_context* ctx, const float origin[3], 
    });
 }
 
+// ---- velocity gradients (velgrad_kernels.h; contract and checks: velgrad_policy.h) -------------------------
+
+static const char* velgrad_refusal(const sph_hip_context* ctx)
+{
+   const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global && !ctx->had_exchange;
+   return velgrad_context_check(ctx->mode == SPH_HIP_MODE_FULL, whole);
+}
+
+int sph_hip_get_velocity_gradients(sph_hip_context* ctx, int first, int n, float* rotation4, float* invariants4)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_get_velocity_gradients";
+   if (const char* why = velgrad_refusal(ctx)) return refuse(ctx, who, why);
+   if (const char* why = velgrad_ids_check(ctx->ids_changed != 0)) return refuse(ctx, who, why);
+   if (const char* why = velgrad_range_check(first, n, ctx->n_owned)) return refuse(ctx, who, why);
+   if (n == 0 || ctx->n == 0) {
+      SPH_TRY(hipStreamSynchronize(ctx->stream));
+      return SPH_HIP_OK;
+   }
+   if ((rc = sample_prepare(ctx))) return rc;
+   if ((rc = launch_velgrad(ctx))) return rc;
+   // both rows into id order, in the staging buffer (idle outside a step: 12 floats a particle, 8 used here); an id
+   // no sorted slot holds keeps zeros
+   const int rows = ctx->n_owned;
+   float4* outA = reinterpret_cast<float4*>(ctx->stage.get());
+   float4* outB = outA + (size_t)rows;
+   hipStream_t st = ctx->stream;
+   SPH_TRY(hipMemsetAsync(outA, 0, sizeof(float4) * 2 * (size_t)rows, st));
+   hipLaunchKernelGGL(k_velgrad_unsort, dim3(div_up(ctx->n, 256)), dim3(256), 0, st, ctx->velp[ctx->cur], ctx->meta,
+                      ctx->velgrad_A.get(), ctx->velgrad_B.get(), rows, outA, outB);
+   SPH_TRY(hipGetLastError());
+   if (rotation4)
+      SPH_TRY(hipMemcpyAsync(rotation4, outA + first, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+   if (invariants4)
+      SPH_TRY(hipMemcpyAsync(invariants4, outB + first, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, st));
+   SPH_TRY(hipStreamSynchronize(st));
+   return SPH_HIP_OK;
+}
+
+// The sampler's calls with the rows as the payload of the channel sums: behind the cell build the rows are formed
+// (launch_velgrad), then the probes are walked.  (36 bytes a probe, as the scalars' calls.)
+
+int sph_hip_sample_velocity_gradients_points(sph_hip_context* ctx, int n, const float* xyz, int group, float* channels4,
+                                             float* density, int32_t* count)
+{
+   const char* who = "sph_hip_sample_velocity_gradients_points";
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = velgrad_group_check(group)) return refuse(ctx, who, why);
+   const SampleCall call = {who, {{channels4, 16}, {density, 4}, {count, 4}}, velgrad_refusal, launch_velgrad};
+   return sample_points_run(ctx, call, n, xyz, SAMPLE_CHUNK_POINTS / 2, [&](const float* sxyz, int m, void* const dev[3]) {
+      bind_flags([&](auto U) {
+         sample_points_launch<U.value, ScalarSum>(ctx, sxyz, m, group == 0 ? ctx->velgrad_A.get() : ctx->velgrad_B.get(),
+                                                  {(float4*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
+      }, unit_scale(ctx->prm));
+   });
+}
+
+int sph_hip_sample_velocity_gradients_lattice(sph_hip_context* ctx, const float origin[3], const float spacing[3],
+                                              const int32_t dims[3], int group, float* channels4, float* density,
+                                              int32_t* count)
+{
+   const char* who = "sph_hip_sample_velocity_gradients_lattice";
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (const char* why = velgrad_group_check(group)) return refuse(ctx, who, why);
+   const SampleCall call = {who, {{channels4, 16}, {density, 4}, {count, 4}}, velgrad_refusal, launch_velgrad};
+   return sample_lattice_run(ctx, call, origin, spacing, dims, [&](const SampleLattice& L, int bricks, void* const dev[3]) {
+      bind_flags([&](auto U) {
+         sample_lattice_launch<U.value, ScalarSum>(ctx, L, bricks, group == 0 ? ctx->velgrad_A.get() : ctx->velgrad_B.get(),
+                                                   {(float4*)dev[0], (float*)dev[1], (int32_t*)dev[2]});
+      }, unit_scale(ctx->prm));
+   });
+}
+
 // ---- iso-surface extractor ------------------------------------------------------------------------
 
 int sph_hip_extract_surface(sph_hip_context* ctx, const float origin[3], const float spacing[3], const int32_t dims[3],
@@ -2436,6 +2512,7 @@ struct TintDraw {
    sph_hip_tint_params tp;
    const float* table;   // host, 3 * n_colors floats
    float* scalar;        // host output, may be null
+   int velgrad = 0;      // tp.channel is a velocity-gradient quantity 0 .. 7 (sph_hip_render_velocity_gradients)
 };
 
 // The frame of the three entry points, arguments checked: the row chunks, their scratch, the launches and the
@@ -2465,7 +2542,8 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
    }
    const bool fluid = ctx->n > 0;   // without a particle the solids are drawn over a background frame
    if (fluid && (rc = sample_prepare(ctx))) return rc;
-   if (tinted && (rc = launch_scalars_stage(ctx, false))) return rc;   // the channels by sorted slot, once
+   // the channels by sorted slot, once: the carried scalars staged, or the velocity-gradient rows formed
+   if (tinted && (rc = tint->velgrad ? launch_velgrad(ctx) : launch_scalars_stage(ctx, false))) return rc;
    hipStream_t st = ctx->stream;
    const CellGrid& g = ctx->grid;
    const bool skip = !ctx->render_noskip;
@@ -2510,7 +2588,12 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
       SPH_TRY(hipMemcpyAsync(ctx->tint_table.get(), ctx->tint_table_host, table_bytes, hipMemcpyHostToDevice, st));
       T.tp = tint->tp;
       T.table = ctx->tint_table.get();
+      if (tint->velgrad) T.tp.channel = velgrad_quantity_component(tint->tp.channel);
    }
+   // what the tint kernels walk: the staged scalars, or the array that holds the quantity
+   const float4* tint_rows = !tinted          ? nullptr
+                             : !tint->velgrad ? ctx->scalar_Ts.get()
+                             : velgrad_quantity_group(tint->tp.channel) == 0 ? ctx->velgrad_A.get() : ctx->velgrad_B.get();
    const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
    const bool unit = unit_scale(ctx->prm);
    const unsigned char* occ = skip ? ctx->render_occ.get() : nullptr;
@@ -2555,13 +2638,13 @@ int render_frame(sph_hip_context* ctx, const char* who, const sph_hip_camera* ca
          if (tint->tp.mode == SPH_HIP_TINT_SURFACE)
             bind_flags([&](auto U, auto FL) {
                hipLaunchKernelGGL((k_tint_surface<U.value, FL.value>), dim3(div_up(chunk, RENDER_THREADS)),
-                                  dim3(RENDER_THREADS), 0, st, F, T, ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start,
+                                  dim3(RENDER_THREADS), 0, st, F, T, ctx->posm[ctx->cur], tint_rows, ctx->cell_start,
                                   g, k, s_hits, s_count, s_first, s_depth, s_nrm, s_rgba, s_scalar);
             }, unit, flat);
          else
             bind_flags([&](auto U, auto S, auto FL) {
                hipLaunchKernelGGL((k_tint_column<U.value, S.value, FL.value>), dim3(div_up(chunk, RENDER_THREADS)),
-                                  dim3(RENDER_THREADS), 0, st, F, T, ctx->posm[ctx->cur], ctx->scalar_Ts, ctx->cell_start,
+                                  dim3(RENDER_THREADS), 0, st, F, T, ctx->posm[ctx->cur], tint_rows, ctx->cell_start,
                                   g, k, occ, s_hits, s_count, s_first, s_nrm, s_rgba, s_scalar);
             }, unit, skip, flat);
          SPH_TRY(hipGetLastError());
@@ -2654,9 +2737,42 @@ int sph_hip_render_scalars(sph_hip_context* ctx, const sph_hip_camera* cam, cons
    if (const char* why = tint_check(cam, rp, sp, solid_albedo_rgb, n_albedo, ctx->n_obst, ctx->n_scalars, tp, table_rgb,
                                     width, height, flags))
       return refuse(ctx, who, why);
-   const TintDraw tint = {*tp, table_rgb, scalar};
+   const TintDraw tint = {*tp, table_rgb, scalar, 0};
    if (!sp) {
       // fluid only: sph_hip_render's frame, solid_id -1 everywhere
+      if (solid_id) memset(solid_id, 0xff, sizeof(int32_t) * (size_t)width * height);
+      return render_frame(ctx, who, cam, rp, width, height, flags, rgba, depth, normal_xyz, velocity_xyz, first_inside,
+                          nullptr, &tint);
+   }
+   SceneDraw scene = {*sp, ctx->n_obst, solid_id};
+   if ((rc = scene_solids_now(ctx, scene, sp, solid_albedo_rgb, n_albedo))) return rc;
+   return render_frame(ctx, who, cam, rp, width, height, flags, rgba, depth, normal_xyz, velocity_xyz, first_inside,
+                       &scene, &tint);
+}
+
+// ---- velocity-gradient renderer: the scalar renderer's frame tinted by one of the eight quantities -----------
+
+int sph_hip_render_velocity_gradients(sph_hip_context* ctx, const sph_hip_camera* cam, const sph_hip_render_params* rp,
+                                      const sph_hip_scene_params* sp, const float* solid_albedo_rgb, int n_albedo,
+                                      const sph_hip_tint_params* tp, const float* table_rgb, int width, int height,
+                                      int flags, uint8_t* rgba, float* depth, float* normal_xyz, float* velocity_xyz,
+                                      int32_t* first_inside, int32_t* solid_id, float* scalar)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_render_velocity_gradients";
+   if ((rc = sample_check(ctx, who))) return rc;
+   // tp->channel carries the quantity: checked here, and the scalar renderer's checks see a channel of their own
+   if (!tp) return refuse(ctx, who, "null tint params or colour table");
+   if (const char* why = velgrad_quantity_check(tp->channel)) return refuse(ctx, who, why);
+   sph_hip_tint_params as_channel = *tp;
+   as_channel.channel = velgrad_quantity_component(tp->channel);
+   if (const char* why = tint_check(cam, rp, sp, solid_albedo_rgb, n_albedo, ctx->n_obst, 1, &as_channel, table_rgb, width,
+                                    height, flags))
+      return refuse(ctx, who, why);
+   TintDraw tint = {*tp, table_rgb, scalar};
+   tint.velgrad = 1;
+   if (!sp) {
       if (solid_id) memset(solid_id, 0xff, sizeof(int32_t) * (size_t)width * height);
       return render_frame(ctx, who, cam, rp, width, height, flags, rgba, depth, normal_xyz, velocity_xyz, first_inside,
                           nullptr, &tint);

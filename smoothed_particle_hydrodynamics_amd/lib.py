@@ -190,6 +190,16 @@ PROTOTYPES = {
     "sph_hip_get_cohesion": (C.c_int, [_ctx, _P(C.c_float)]),
     "sph_hip_record_monitor": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
     "sph_hip_get_monitor_record": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sph_hip_get_velocity_gradients": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "sph_hip_sample_velocity_gradients_points": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]),
+    "sph_hip_sample_velocity_gradients_lattice": (C.c_int, [_ctx, _P(C.c_float * 3), _P(C.c_float * 3),
+                                                            _P(C.c_int32 * 3), C.c_int, C.c_void_p, C.c_void_p,
+                                                            C.c_void_p]),
+    "sph_hip_render_velocity_gradients": (C.c_int, [_ctx, _P(SphCamera), _P(SphRenderParams), _P(SphSceneParams),
+                                                    C.c_void_p, C.c_int, _P(SphTintParams), C.c_void_p, C.c_int,
+                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "sph_hip_stream": (C.c_void_p, [_ctx]),
     "sph_hip_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "sph_hip_create_slab": (C.c_int, [_P(_ctx), _P(SphParams), C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -617,6 +617,24 @@ def dam_break_cohesive(n, gamma, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75
     return p, pos, vel, mass, float(gamma)
 
 
+def rankine_vortex(n, omega, core, neighbors=32.0, cells=None, seed=42):
+    """A still block of fluid - droplet's fill, box and constants - swirling about the vertical (y) axis through its
+    middle as a Rankine vortex: solid-body rotation at the rate `omega` within the radius `core` of the axis,
+    v = omega x r with omega = (0, omega, 0), and the irrotational swirl of speed omega * core^2 / r outside it.
+    The vorticity is (0, 2 * omega, 0) inside the core and zero outside: what getVelocityGradients should show.
+    Returns (params, pos, vel, mass)."""
+    p, pos, _, mass, _ = droplet(n, 0.0, neighbors, cells, seed)
+    x = pos.reshape(-1, 3).astype(np.float64)
+    dx = x[:, 0] - 0.5 * float(p.max_x)
+    dz = x[:, 2] - 0.5 * float(p.max_z)
+    r2 = dx * dx + dz * dz
+    rate = np.where(r2 < float(core) ** 2, float(omega), float(omega) * float(core) ** 2 / np.maximum(r2, 1e-300))
+    vel = np.zeros((n, 3), np.float32)
+    vel[:, 0] = rate * dz
+    vel[:, 2] = -rate * dx
+    return p, pos, np.ascontiguousarray(vel.reshape(-1)), mass
+
+
 def dyed_cut_box(p):
     """The marched box (lo, hi) that cuts the tank of dam_break_dyed and heated_floor at its mid-plane z = max_z / 2:
     the renderer's default box - the domain grown by h - with its far side in z moved to the middle.  A camera

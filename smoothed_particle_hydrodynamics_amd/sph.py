@@ -20,6 +20,7 @@ from . import ports as _P
 from . import scalars as _S
 from . import colormaps as _CM
 from . import monitor as _M
+from . import velgrad as _V
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, SphTintParams, TracerPath, Tracers, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "ScalarRenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
@@ -761,6 +762,16 @@ class SPH(Context):
         that is 1 everywhere: the fluid's thickness), which shows what lies under the surface.  Solids do
         not clip a column.  flat=True leaves the Lambert factor out (for cut views, where rays enter inside
         the fluid).  The other arguments are render's; the simulation is not changed by the call."""
+        return self._render_tinted("sph_hip_render_scalars", int(channel), camera, width, height, iso, value_range,
+                                   colormap, mode, flat, solids, step, refine, grad_step, box, light, albedo, ambient,
+                                   diffuse, background, velocity, max_samples, solid_albedo, solid_colors,
+                                   solid_ambient, solid_diffuse)
+
+    def _render_tinted(self, entry, channel, camera, width, height, iso, value_range, colormap, mode, flat, solids,
+                       step, refine, grad_step, box, light, albedo, ambient, diffuse, background, velocity,
+                       max_samples, solid_albedo, solid_colors, solid_ambient, solid_diffuse):
+        """The tinted frame of renderScalars and renderVelocityGradients: `entry` is the C entry point, `channel`
+        what its tint params carry."""
         if mode not in TINT_MODES:
             raise ValueError("mode must be 'surface' or 'column'")
         rp, W, H, out, cam, flags = self._frame_args(camera, width, height, iso, step, refine, grad_step, box, light,
@@ -770,7 +781,7 @@ class SPH(Context):
         if table.ndim != 2 or table.shape[1] != 3:
             raise ValueError("colormap must be an (n, 3) table")
         tp = SphTintParams()
-        tp.channel = int(channel)
+        tp.channel = channel
         tp.mode = TINT_MODES[mode]
         tp.lo, tp.hi = float(value_range[0]), float(value_range[1])
         tp.n_colors = table.shape[0]
@@ -780,10 +791,66 @@ class SPH(Context):
         if solids:
             sp, colors = self._scene_args(ambient, diffuse, solid_albedo, solid_colors, solid_ambient, solid_diffuse)
             solid_id = np.zeros((H, W), np.int32)
-        self.call("sph_hip_render_scalars", C.byref(cam), C.byref(rp), None if sp is None else C.byref(sp),
+        self.call(entry, C.byref(cam), C.byref(rp), None if sp is None else C.byref(sp),
                   _ptr(colors), 0 if colors is None else colors.shape[0], C.byref(tp), _ptr(table), W, H, flags,
                   _ptr(rgba), _ptr(depth), _ptr(normal), _ptr(vel), _ptr(first), _ptr(solid_id), _ptr(scalar))
         return ScalarRenderResult(rgba, depth, normal, vel, first, solid_id, scalar)
+
+    # ---- velocity gradients (sph_hip_get_velocity_gradients) ---------------------------------------------
+    def getVelocityGradients(self):
+        """Vorticity, divergence, strain rate, Q and |vorticity| of every particle of the current state, in particle
+        order, as a velgrad.VelocityGradients (include/sph_hip.h: velocity gradients; synchronises): a weighted
+        least-squares fit of the velocity over each particle's neighbours, exact on a linear field.  A particle
+        with too few or nearly coplanar neighbours has .valid False and zeros.  The simulation is not changed by
+        the call.  FULL and FULL_FAST contexts whose ids ports have not changed."""
+        n = self.call("sph_hip_particle_count")      # (0 before the first setParticles)
+        rot = np.zeros((n, 4), np.float32)
+        inv = np.zeros((n, 4), np.float32)
+        self.call("sph_hip_get_velocity_gradients", 0, n, _ptr(rot), _ptr(inv))
+        return _V.VelocityGradients(rot, inv)
+
+    def sampleVelocityGradients(self, points):
+        """The same quantities at `points` ((n, 3) float32): a VelocityGradients with .density and .count, every
+        value the Shepard-normalised sum over the sampler's members, 0 where there are none; .valid is the
+        weighted share of valid particles around the probe.  Two calls, one per row."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        rows = [np.zeros((n, 4), np.float32) for _ in range(2)]
+        rho = np.zeros(n, np.float32)
+        cnt = np.zeros(n, np.int32)
+        for group in range(2):
+            self.call("sph_hip_sample_velocity_gradients_points", n, _ptr(pts), group, _ptr(rows[group]), _ptr(rho),
+                      _ptr(cnt))
+        return _V.VelocityGradients(rows[0], rows[1], rho, cnt)
+
+    def sampleVelocityGradientLattice(self, origin, spacing, shape):
+        """The same on sampleLattice's lattice, shape = (nx, ny, nz): every field with the leading shape
+        [nz, ny, nx]."""
+        o, s, d, dims = _lattice(origin, spacing, shape)
+        grid = (max(dims[2], 0), max(dims[1], 0), max(dims[0], 0))
+        if grid[0] * grid[1] * grid[2] >= 2 ** 31:
+            raise ValueError("a lattice of more than 2^31 - 1 points")
+        rows = [np.zeros(grid + (4,), np.float32) for _ in range(2)]
+        rho = np.zeros(grid, np.float32)
+        cnt = np.zeros(grid, np.int32)
+        for group in range(2):
+            self.call("sph_hip_sample_velocity_gradients_lattice", C.byref(o), C.byref(s), C.byref(d), group,
+                      _ptr(rows[group]), _ptr(rho), _ptr(cnt))
+        return _V.VelocityGradients(rows[0], rows[1], rho, cnt)
+
+    def renderVelocityGradients(self, camera, width, height, iso, quantity, value_range, colormap=None, mode="surface",
+                                flat=False, solids=False, step=None, refine=8, grad_step=None, box=None,
+                                light=(0.4, 0.8, 0.45), albedo=(0.25, 0.55, 0.9), ambient=0.2, diffuse=0.8,
+                                background=(0, 0, 0, 255), velocity=False, max_samples=1 << 16,
+                                solid_albedo=(0.72, 0.72, 0.72), solid_colors=None, solid_ambient=None,
+                                solid_diffuse=None):
+        """renderScalars' frame coloured by a velocity-gradient quantity in the place of a carried channel:
+        `quantity` is a name of velgrad.QUANTITIES ("vorticity_z", "divergence", "q", ...) or its number 0 .. 7.
+        The context needs no carried scalars.  Every other argument is renderScalars'."""
+        return self._render_tinted("sph_hip_render_velocity_gradients", _V.quantity_index(quantity), camera, width,
+                                   height, iso, value_range, colormap, mode, flat, solids, step, refine, grad_step,
+                                   box, light, albedo, ambient, diffuse, background, velocity, max_samples,
+                                   solid_albedo, solid_colors, solid_ambient, solid_diffuse)
 
     # ---- diagnostics -----------------------------------------------------------------------------
     def elapsed(self):
