@@ -1172,6 +1172,43 @@ int sph_hip_get_buoyancy(sph_hip_context* ctx, sph_hip_buoyancy* out);
 int sph_hip_set_cohesion(sph_hip_context* ctx, float gamma);
 int sph_hip_get_cohesion(sph_hip_context* ctx, float* gamma);
 
+/* ---- xsph --------------------------------------------------------------------------------------- *
+ *
+ * Velocity smoothing after Monaghan (1989): each step every particle's velocity is drawn towards a kernel-weighted
+ * mean of its neighbours' velocities.  Particle-scale velocity noise decays and the flow stays coherent; a uniform
+ * motion is not changed, and with equal masses neither is the total momentum.  No counterpart in the reference.
+ * The operation-by-operation contract is in csrc/xsph_policy.h; all arithmetic is fp32, unfused, in the order
+ * written.
+ *   stage      for every particle p of a step's state S_k: R_p = {v_p, 1.0f / rho_p}, rho_p the density the step's
+ *              density pass formed.
+ *   sum        for particle i over its neighbours j (the acceleration pass's pairs, in canonical order):
+ *              s = s + g_ij * (v_j - v_i) per component from 0, g_ij = t_j * (0.5f * (R_i.w + R_j.w)), t_j the
+ *              density pass's pair term m_j * (kernel1 * (hscaled2 - d*d)^3), d = sqrtf(d2) * sim_scale (the field
+ *              sampler's term, above): Monaghan's 2 m_j W / (rho_i + rho_j) with the mean of the inverse densities.
+ *   change     dv = eps * s per component; every sum reads S_k's velocities, never a smoothed one.
+ *   guard      a particle whose dv is zero in every component, or not finite in any, is left alone: not a bit of
+ *              it changes.  A particle without a neighbour and a uniform velocity field are left alone.
+ *   a step     behind the step's acceleration pass and cohesion, before buoyancy and the integrate: v' = v + dv.
+ *              There is no clamp, and the acceleration is not touched.  Buoyancy adds its b*dt to v'.
+ *   modes      FULL and FULL_FAST give the same dv bits from the same state.
+ *   range      the smoothing is a convex combination while eps * sum_j g_ij <= 1 - about eps at the fluid's own
+ *              density; nothing polices the sum.
+ *   route      a context with the smoothing gives up the fused integrate (it keeps the prehash) and launches two
+ *              more kernels per step.  Obstacles, motions, paths, bodies, load recordings, gauges, tracers, carried
+ *              scalars, buoyancy, cohesion and the step monitor work beside it unchanged.  A context without it
+ *              enqueues exactly what it always did, and allocates nothing for it.
+ *   not done   the stand-alone phase calls (sph_hip_compute_density .. sph_hip_integrate) and the slab steps do
+ *              NOT apply the smoothing.
+ * sph_hip_set_xsph sets eps for the steps enqueued from now on; it does not wait, and steps already queued keep the
+ * eps they were enqueued with.  eps == 0 switches the smoothing off and is never refused.  SPH_HIP_ERR_INVALID, the
+ * previous setting kept, for an eps that is not finite or lies outside [0, 1], a REF or a slab context, and a
+ * context with ports; sph_hip_set_ports refuses ports on a context with the smoothing.  A new sph_hip_upload drops
+ * the setting.  sph_hip_get_xsph stores the eps in force, 0 when none is.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no existing
+ * prototype changed. */
+int sph_hip_set_xsph(sph_hip_context* ctx, float eps);
+int sph_hip_get_xsph(sph_hip_context* ctx, float* eps);
+
 /* ---- step monitor ------------------------------------------------------------------------------- *
  *
  * Per-step stability and conservation rows, filled on the device while the steps stay queued: at which step a run

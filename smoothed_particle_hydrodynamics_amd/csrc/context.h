@@ -29,6 +29,7 @@
 #include "scalar_kernels.h"
 #include "buoyancy_kernels.h"
 #include "cohesion_kernels.h"
+#include "xsph_kernels.h"
 #include "monitor_kernels.h"
 #include "velgrad_kernels.h"
 #include "port_kernels.h"
@@ -434,6 +435,12 @@ struct sph_hip_context {
    // cohesion (sph_hip_set_cohesion): the gamma the next enqueued steps take by value; dropped by an upload
    int have_cohesion = 0;
    float cohesion_gamma = 0.0f;
+
+   // xsph (sph_hip_set_xsph): the eps the next enqueued steps take by value, dropped by an upload; the staged rows
+   // {v, 1 / rho} by sorted slot (xsph_R) hold the capacity and are allocated at the first non-zero setting
+   int have_xsph = 0;
+   float xsph_eps = 0.0f;
+   DevBuf<float4> xsph_R;
 
    // step monitor (sph_hip_record_monitor): mon_rows rows; mon_step = steps enqueued since the call, mon_filled =
    // rows those steps have filled, mon_row_now = the row the step being enqueued fills (-1: none).  The partial

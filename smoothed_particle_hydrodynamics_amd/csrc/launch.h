@@ -964,6 +964,27 @@ int launch_cohesion(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- xsph (xsph_kernels.h; contract: xsph_policy.h; decision: launch_policy.h) ----------------------------------
+// Behind the step's acceleration pass and cohesion, in front of buoyancy and the integrate: the stage of S_k's
+// velocities with the densities the step's density pass left, then the pass over the lists and counts it left,
+// which writes velp of the sorted state.  eps and the constants travel by value: a later setter does not reach the
+// steps already queued.  Nothing synchronises.
+int launch_xsph(sph_hip_context* ctx)
+{
+   hipLaunchKernelGGL(k_xsph_stage, dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream, ctx->velp[ctx->cur], ctx->rho,
+                      ctx->meta, ctx->xsph_R);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   static_assert(TILE_THREADS == 256, "the xsph kernel maps one workgroup to 256 sorted particles");
+   bind_flags([&](auto U, auto W) {
+      hipLaunchKernelGGL((k_xsph_apply<U.value, W.value>), dim3(div_up(ctx->n, TILE_THREADS)), dim3(TILE_THREADS), 0,
+                         ctx->stream, ctx->posm[ctx->cur], ctx->xsph_R, ctx->ncount, ctx->cell_start, ctx->meta, ctx->grid,
+                         k, ctx->xsph_eps, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, ctx->list_cap,
+                         ctx->use_tiled ? 1 : 0, ctx->velp[ctx->cur]);
+   }, unit_scale(ctx->prm), ctx->caps.wide != 0);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // ---- step monitor (monitor_kernels.h; contract: monitor_policy.h; grid: launch_policy.h) ------------------------
 // Counts the step of a recording and picks the row it fills (mon_row_now, -1: none); on such a step of a context
 // whose scalar pass has just run, k_monitor_pairs directly behind that pass, with the volumes it staged.  The
@@ -1110,11 +1131,15 @@ int step_impl(sph_hip_context* ctx, bool timed)
    const bool fused = !cohesive &&
                       fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
                                      loads_pending(ctx), buoyant);
-   if ((rc = launch_accel(ctx, 0, nullptr, fused))) return rc;
+   // xsph: two more such kernels, behind cohesion's and in front of buoyancy's; the step keeps the prehash
+   const bool smoothing = step_launches_xsph(ctx->have_xsph != 0, ctx->n);
+   const bool fuse_now = fused && !smoothing;
+   if ((rc = launch_accel(ctx, 0, nullptr, fuse_now))) return rc;
    if (cohesive && (rc = launch_cohesion(ctx))) return rc;
+   if (smoothing && (rc = launch_xsph(ctx))) return rc;
    if (buoyant && (rc = launch_buoyancy(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;
-   if (fused) fused_step_done(ctx, 1);
+   if (fuse_now) fused_step_done(ctx, 1);
    else if ((rc = launch_integrate(ctx, hash_too))) return rc;
    if (ctx->mon_row_now >= 0 && (rc = launch_monitor(ctx))) return rc;   // step monitor: the row of the state just produced
    return mark_phase(ctx, se, 6, st);

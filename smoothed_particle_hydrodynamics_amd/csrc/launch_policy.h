@@ -374,6 +374,12 @@ inline bool step_launches_buoyancy(bool have_buoyancy, int n_scalars, int n)
 // (fuse_integrate's last argument).  A context without cohesion launches what it always launched.
 inline bool step_launches_cohesion(bool have_cohesion, int n) { return have_cohesion && n > 0; }
 
+// Whether a step launches k_xsph_stage and k_xsph_apply (xsph_policy.h) between its acceleration pass and its
+// integrate, behind cohesion's kernel and in front of buoyancy's: an eps is set and the step has particles.  Such
+// a step gives up the fused integrate and keeps the prehash, as a cohesive step does.  A context without the
+// setting launches what it always launched.
+inline bool step_launches_xsph(bool have_xsph, int n) { return have_xsph && n > 0; }
+
 // ---- step monitor (monitor_policy.h) ---------------------------------------------------------------
 // The grid of k_monitor_particles: workgroups of MONITOR_THREADS lanes that stride over the live slots, one per 256
 // slots up to MONITOR_MAX_BLOCKS - a bounded number of partial rows, which one workgroup folds (k_monitor_finish).

@@ -569,6 +569,7 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    ctx->n_scalar_sources = 0;
    ctx->have_buoyancy = 0;   // (buoyancy reads the scalars: it goes with them)
    ctx->have_cohesion = 0;   // cohesion is a setting of the upload it was made for
+   ctx->have_xsph = 0;       // and so is the velocity smoothing
    ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
    ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
    ports_mass_rule(ctx, n == 0);
@@ -1338,6 +1339,7 @@ int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int
    if (const char* why = port_check(emitters, ne, sinks, ns, port_grid(ctx))) return refuse(ctx, who, why);
    if (const char* why = scalar_ports_check(ctx->n_scalars, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = cohesion_ports_check(ctx->have_cohesion != 0, ne, ns)) return refuse(ctx, who, why);
+   if (const char* why = xsph_ports_check(ctx->have_xsph != 0, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = monitor_ports_check(ctx->mon_rows, ne, ns)) return refuse(ctx, who, why);
    // a pending prehash counted for a build whose entries the ports may change first
    if ((rc = drop_prehash(ctx))) return rc;
@@ -2219,6 +2221,43 @@ int sph_hip_get_monitor_record(sph_hip_context* ctx, int first_row, int n_rows, 
                         hipMemcpyDeviceToHost));
    for (int r = 0; steps && r < n_rows; r++) steps[r] = monitor_record_step(first_row + r, ctx->mon_every);
    return ctx->mon_filled;
+}
+
+// ---- xsph (xsph_kernels.h; contract and checks: xsph_policy.h) -------------------------------------------
+
+int sph_hip_set_xsph(sph_hip_context* ctx, float eps)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_xsph";
+   if (const char* why = xsph_eps_check(eps)) return refuse(ctx, who, why);
+   if (!xsph_is_off(eps)) {   // (switching it off is never refused)
+      const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global && !ctx->had_exchange;
+      if (const char* why = xsph_context_check(ctx->mode == SPH_HIP_MODE_FULL, whole)) return refuse(ctx, who, why);
+      if (const char* why = xsph_ports_set_check(ports_active(ctx->n_emit, ctx->n_sink))) return refuse(ctx, who, why);
+      if (!ctx->xsph_R) {   // the staged rows: at the first setting, so a context that never asks keeps its footprint
+         DevBuf<float4> rows;
+         if (dev_alloc(rows, (size_t)ctx->capacity) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->err = "sph_hip_set_xsph: cannot allocate the staged rows of " + std::to_string(ctx->capacity) + " particles";
+            return SPH_HIP_ERR_CAPACITY;
+         }
+         ctx->xsph_R = std::move(rows);
+      }
+   }
+   // (a step takes eps by value: the steps already queued keep theirs)
+   ctx->have_xsph = xsph_is_off(eps) ? 0 : 1;
+   ctx->xsph_eps = ctx->have_xsph ? eps : 0.0f;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_xsph(sph_hip_context* ctx, float* eps)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!eps) return refuse(ctx, "sph_hip_get_xsph", "null output");
+   *eps = ctx->have_xsph ? ctx->xsph_eps : 0.0f;
+   return SPH_HIP_OK;
 }
 
 // The sampler's calls with the channel sums: behind the cell build the scalars are staged by sorted slot

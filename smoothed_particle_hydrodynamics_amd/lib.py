@@ -188,6 +188,8 @@ PROTOTYPES = {
     "sph_hip_get_buoyancy": (C.c_int, [_ctx, _P(SphBuoyancy)]),
     "sph_hip_set_cohesion": (C.c_int, [_ctx, C.c_float]),
     "sph_hip_get_cohesion": (C.c_int, [_ctx, _P(C.c_float)]),
+    "sph_hip_set_xsph": (C.c_int, [_ctx, C.c_float]),
+    "sph_hip_get_xsph": (C.c_int, [_ctx, _P(C.c_float)]),
     "sph_hip_record_monitor": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
     "sph_hip_get_monitor_record": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sph_hip_get_velocity_gradients": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -617,6 +617,30 @@ def dam_break_cohesive(n, gamma, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75
     return p, pos, vel, mass, float(gamma)
 
 
+# Monaghan's usual choice
+XSPH_EPS = 0.5
+
+
+def dam_break_smoothed(n, eps=XSPH_EPS, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42,
+                       gravity=-9.81):
+    """The surging dam of dam_break_dye without the dye - gravity along -y, the walls on, the surge along +x - with
+    XSPH velocity smoothing: the particle-scale velocity noise of the breaking column decays while the flow keeps
+    its course.  Returns (params, pos, vel, mass, eps): setParticles, then setVelocitySmoothing."""
+    p, pos, vel, mass, _ = dam_break_dye(n, 1.0, surge, box, fill, neighbors, seed, gravity)
+    return p, pos, vel, mass, float(eps)
+
+
+def noisy_block(n, amplitude, seed=42, neighbors=32.0, cells=None):
+    """A resting block with velocity noise: droplet's cubic random fill in the middle of the box (gravity and the
+    central mass off, the walls on, unit masses, ~`neighbors` particles inside radius h) and a seeded uniform
+    random velocity in [-amplitude, amplitude)^3 per particle - mean about zero, no structure above the particle
+    scale: what XSPH is there to remove.  Returns (params, pos, vel, mass)."""
+    p, pos, _, mass, _ = droplet(n, 0.0, neighbors, cells, seed)
+    a = float(amplitude)
+    vel = box_fill(n, (-a,) * 3, (a,) * 3, seed + 1) if a > 0.0 else np.zeros(3 * n, np.float32)
+    return p, pos, vel, mass
+
+
 def rankine_vortex(n, omega, core, neighbors=32.0, cells=None, seed=42):
     """A still block of fluid - droplet's fill, box and constants - swirling about the vertical (y) axis through its
     middle as a Rankine vortex: solid-body rotation at the rate `omega` within the radius `core` of the axis,

@@ -611,6 +611,20 @@ class SPH(Context):
         self.call("sph_hip_get_cohesion", C.byref(g))
         return float(g.value)
 
+    # ---- xsph (sph_hip_set_xsph) ------------------------------------------------------------------
+    def setVelocitySmoothing(self, eps):
+        """XSPH from the next enqueued step on (include/sph_hip.h: xsph): every particle's velocity moves by
+        eps * sum_j g_ij * (v_j - v_i) towards its neighbours' weighted mean, behind the acceleration pass and in
+        front of the integrate - velocity noise decays, a uniform motion and the momentum stay.  eps in [0, 1];
+        None or 0 switches it off.  FULL and FULL_FAST contexts without ports; a new setParticles drops it."""
+        self.call("sph_hip_set_xsph", C.c_float(0.0 if eps is None else float(eps)))
+
+    def getVelocitySmoothing(self):
+        """The eps in force, 0.0 when the smoothing is off."""
+        e = C.c_float(0.0)
+        self.call("sph_hip_get_xsph", C.byref(e))
+        return float(e.value)
+
     # ---- step monitor (sph_hip_record_monitor) ------------------------------------------------------
     def recordMonitor(self, rows, every=1, quantum_log2=_M.QUANTUM_DEFAULT):
         """Keep a row of stability and conservation figures for the step after this call and every `every`-th
