@@ -28,6 +28,7 @@
 
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/sph_hip.h"
 
@@ -132,6 +133,44 @@ inline bool port_in_real_cell(const PortGrid& g, float x, float y, float z)
    const int cz = port_cell_unclamped(z, g.inv, g.nz_global);
    return port_cell_unclamped(x, g.inv, g.nx) >= 0 && port_cell_unclamped(y, g.inv, g.ny) >= 0 && cz >= g.z0 &&
           cz < g.z0 + g.nz;
+}
+
+// ---- the uniform-mass rule --------------------------------------------------------------------------------
+// A context whose resident particles all have one mass skips the mass gather in its density and acceleration
+// passes (launch.h: uniform_mass).  With emitters that stays right only while every emitter's mass equals the
+// resident one IN BITS (memcmp, not ==: -0.0f and +0.0f differ, a NaN equals itself).
+struct PortMassRule {
+   int uniform;     // the flag after the rule
+   int known;       // whether `mass` is the mass of everything resident
+   float mass;      // the resident mass
+};
+
+inline bool port_same_bits(float a, float b) { return memcmp(&a, &b, sizeof(float)) == 0; }
+
+// uniform, known, mass: the flag the upload left, whether the uploaded mass is known, and that mass.
+// nothing_resident: an upload of no particles that nothing has been emitted into - the emitters' own agreement
+// decides, whatever the flag was, and the first emitter's mass becomes the resident one.  Otherwise the flag is
+// only ever cleared: by an unknown resident mass, or by an emitter whose mass differs from it.
+inline PortMassRule port_mass_rule(int uniform, int known, float mass, const sph_hip_emitter* emitters, int ne,
+                                   bool nothing_resident)
+{
+   PortMassRule r = {uniform, known, mass};
+   if (ne == 0) return r;
+   if (nothing_resident) {
+      r.uniform = 1;
+      for (int e = 1; e < ne; e++) r.uniform &= port_same_bits(emitters[e].mass, emitters[0].mass) ? 1 : 0;
+      r.known = 1;
+      r.mass = emitters[0].mass;
+      return r;
+   }
+   if (!uniform) return r;
+   if (!known) {
+      r.uniform = 0;
+      return r;
+   }
+   for (int e = 0; e < ne; e++)
+      if (!port_same_bits(emitters[e].mass, mass)) r.uniform = 0;
+   return r;
 }
 
 // ---- checks ---------------------------------------------------------------------------------------------

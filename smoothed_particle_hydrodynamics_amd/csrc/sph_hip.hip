@@ -500,29 +500,17 @@ int sph_hip_get_params(const sph_hip_context* ctx, sph_hip_params* out)
    return SPH_HIP_OK;
 }
 
-// The uniform-mass rule with emitters (port_policy.h): a context whose resident particles all have one mass
-// keeps skipping the mass gather only while every emitter's mass equals it in bits.  nothing_resident: an
-// upload of no particles that nothing has been emitted into - the emitters' own agreement decides, and their
-// mass becomes the resident one.  Results are bit-identical either way.
+// The uniform-mass rule with emitters (port_policy.h: port_mass_rule, which decides): a context whose resident
+// particles all have one mass keeps skipping the mass gather only while every emitter's mass equals it in bits.
+// nothing_resident: an upload of no particles that nothing has been emitted into - the emitters' own agreement
+// decides, and their mass becomes the resident one.  Results are bit-identical either way.
 static void ports_mass_rule(sph_hip_context* ctx, bool nothing_resident)
 {
-   if (ctx->n_emit == 0) return;
-   const float m0 = ctx->emit_host[0].mass;
-   if (nothing_resident) {
-      int same = 1;
-      for (int e = 1; e < ctx->n_emit; e++) same &= memcmp(&ctx->emit_host[e].mass, &m0, sizeof(float)) == 0;
-      ctx->uniform_mass = same;
-      ctx->upload_mass_known = 1;
-      ctx->upload_mass = m0;
-      return;
-   }
-   if (!ctx->uniform_mass) return;
-   if (!ctx->upload_mass_known) {
-      ctx->uniform_mass = 0;
-      return;
-   }
-   for (int e = 0; e < ctx->n_emit; e++)
-      if (memcmp(&ctx->emit_host[e].mass, &ctx->upload_mass, sizeof(float)) != 0) ctx->uniform_mass = 0;
+   const PortMassRule r = port_mass_rule(ctx->uniform_mass, ctx->upload_mass_known, ctx->upload_mass,
+                                         ctx->emit_host, ctx->n_emit, nothing_resident);
+   ctx->uniform_mass = r.uniform;
+   ctx->upload_mass_known = r.known;
+   ctx->upload_mass = r.mass;
 }
 
 // the port schedule, the totals and the id bookkeeping start over (sph_hip_set_ports, every upload)

@@ -111,7 +111,7 @@ def test_particles_equal_the_restatement(hiplib, mode):
             assert not rows_of(g)[~valid].any()
             assert (want[valid, 4] > 0).all() and (want[valid, 6] > 0).all()
             assert same(g.vorticity, want[:, 0:3]) and same(g.q, want[:, 5])
-            assert g.enstrophy(mass) == 0.5 * float(np.sum(want[:, 6].astype(np.float64) ** 2))
+            assert g.enstrophy(mass) == 0.5 * float(np.sum(mass.astype(np.float64) * want[:, 6].astype(np.float64) ** 2))
         # after three steps the sorted order is no longer the id order: the rows went through k_velgrad_unsort
         order = VE.PE.canonical_order(p, pos_k)
         assert (order != np.arange(N)).mean() > 0.5
