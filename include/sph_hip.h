@@ -1209,6 +1209,62 @@ int sph_hip_get_cohesion(sph_hip_context* ctx, float* gamma);
 int sph_hip_set_xsph(sph_hip_context* ctx, float eps);
 int sph_hip_get_xsph(sph_hip_context* ctx, float* eps);
 
+/* ---- viscous stress ----------------------------------------------------------------------------- *
+ *
+ * A pairwise, momentum-conserving viscous force of a stated dynamic viscosity mu: oil, honey, mud, a sloshing tank
+ * that comes to rest - and, with a law, a viscosity that follows a carried channel through a table: lava that
+ * stiffens as it cools.  params.viscosity is not this term: the reference rescales its viscous sum inside the
+ * neighbour loop by a factor derived from the pressure, and the bit-exact port keeps that.  The
+ * operation-by-operation contract is in csrc/viscous_policy.h; all arithmetic is fp32, unfused, in the order written.
+ *   law        factor(x) of a channel value x over K keys (value[k] strictly ascending, factor[k] >= 0): factor[0]
+ *              where !(x > value[0]) (NaN too), factor[K-1] where x >= value[K-1], else linear between the two keys
+ *              around x: f_k + u * (f_{k+1} - f_k), u = (x - x_k) / (x_{k+1} - x_k).
+ *   stage      for every particle p of a step's state S_k: R_p = {v_p, V_p}, V_p = m_p / rho_p (0 where rho_p is not
+ *              > 0), rho_p the density the step's density pass formed; with a law M_p = mu * factor(T_p,channel), T
+ *              the channels as they stood before this step (what buoyancy reads).
+ *   sum        for particle i over its neighbours j (the acceleration pass's pairs, in canonical order) with
+ *              V_j != 0: s = s + g_ij * (v_j - v_i) per component from 0, g_ij = (m_ij * (V_i * V_j)) * L,
+ *              L = kernel3 * (hscaled - d) the reference's viscosity Laplacian, d = sqrtf(d2) * sim_scale,
+ *              m_ij = 0.5f * (M_i + M_j) with a law, else mu.  g_ij == g_ji by bits: the force addends of a pair
+ *              negate each other for any masses.
+ *   accel      c = s / m_i per component.
+ *   guard      a particle with V_i == 0, a mass that is not > 0, a c that is zero in every component or not finite
+ *              in any, is left alone: not a bit of it changes.  A uniform velocity field stores nothing.
+ *   a step     behind the step's acceleration pass and cohesion, before XSPH, buoyancy and the integrate:
+ *              a' = clamp(a + c), the acceleration pass's clamp.  The velocity is not touched; every sum reads
+ *              S_k's velocities.
+ *   modes      FULL and FULL_FAST give the same c bits from the same state.
+ *   range      the scheme is explicit: a velocity stays a convex combination of itself and its neighbours' while
+ *              N_i = dt * (1 / m_i) * sum_j m_ij V_i V_j L <= 1.  NOTHING polices this, on the device or here.
+ *   route      a context with the term gives up the fused integrate (it keeps the prehash) and launches two more
+ *              kernels per step.  Obstacles, motions, paths, bodies, load recordings, gauges, tracers, carried
+ *              scalars, buoyancy, cohesion, XSPH and the step monitor work beside it unchanged.  A context without
+ *              it enqueues exactly what it always did, and allocates nothing for it: the first non-zero mu
+ *              allocates 16 bytes per particle of capacity, the first law 4 more.
+ *   not done   the stand-alone phase calls (sph_hip_compute_density .. sph_hip_integrate) and the slab steps do
+ *              NOT apply the viscous stress.
+ * sph_hip_set_viscous_stress sets mu and the law (null: a constant mu) for the steps enqueued from now on; it does
+ * not wait, and steps already queued keep what they were enqueued with.  mu == 0 switches the term off and is never
+ * refused.  SPH_HIP_ERR_INVALID, the previous setting kept, for a mu that is not finite or negative, a law whose
+ * channel, key count, key values or key factors break the rules above, a law on a context without scalars, a REF or
+ * a slab context, and a context with ports; sph_hip_set_ports refuses ports on a context with the term.
+ * sph_hip_set_scalars without rows drops the law and keeps mu.  A new sph_hip_upload drops the whole setting.
+ * sph_hip_get_viscous_stress stores the mu in force (0 when none is), the law (zeroed when none is) and whether there
+ * is one; each output may be null.
+ * These entry points were added without a change of SPH_HIP_ABI_VERSION: no existing struct and no existing
+ * prototype changed. */
+#define SPH_HIP_MAX_VISCOSITY_KEYS 16
+
+typedef struct sph_hip_viscosity_law {
+   int32_t channel;                            /* 0 .. SPH_HIP_SCALAR_CHANNELS - 1 */
+   int32_t n_keys;                             /* 2 .. SPH_HIP_MAX_VISCOSITY_KEYS */
+   float value[SPH_HIP_MAX_VISCOSITY_KEYS];    /* strictly ascending */
+   float factor[SPH_HIP_MAX_VISCOSITY_KEYS];   /* >= 0: mu is multiplied by it */
+} sph_hip_viscosity_law;
+
+int sph_hip_set_viscous_stress(sph_hip_context* ctx, float mu, const sph_hip_viscosity_law* law_or_null);
+int sph_hip_get_viscous_stress(sph_hip_context* ctx, float* mu, sph_hip_viscosity_law* law, int* have_law);
+
 /* ---- step monitor ------------------------------------------------------------------------------- *
  *
  * Per-step stability and conservation rows, filled on the device while the steps stay queued: at which step a run

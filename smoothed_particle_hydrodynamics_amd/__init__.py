@@ -12,4 +12,5 @@ from .lib import Tracers, TracerPath  # noqa: F401
 from .gauges import PointGauge, ColumnGauge, SectionGauge, PressureGauge, PressurePatch, GaugeReadings, GaugeRecord  # noqa: F401
 from .ports import Emitter, Sink, PortTotals  # noqa: F401
 from .scalars import Buoyancy, ScalarSource  # noqa: F401
-from . import colormaps, gauges, obstacles, ports, scalars, scenes  # noqa: F401
+from .viscosity import ViscosityLaw  # noqa: F401
+from . import colormaps, gauges, obstacles, ports, scalars, scenes, viscosity  # noqa: F401

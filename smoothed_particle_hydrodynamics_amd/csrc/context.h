@@ -30,6 +30,7 @@
 #include "buoyancy_kernels.h"
 #include "cohesion_kernels.h"
 #include "xsph_kernels.h"
+#include "viscous_kernels.h"
 #include "monitor_kernels.h"
 #include "velgrad_kernels.h"
 #include "port_kernels.h"
@@ -441,6 +442,15 @@ struct sph_hip_context {
    int have_xsph = 0;
    float xsph_eps = 0.0f;
    DevBuf<float4> xsph_R;
+
+   // viscous stress (sph_hip_set_viscous_stress): the mu and the law the next enqueued steps take by value, dropped
+   // by an upload (the law also with the scalars); the staged rows {v, m / rho} by sorted slot (viscous_R) and, with a
+   // law, the staged viscosities (viscous_M) hold the capacity: allocated at the first non-zero mu and the first law
+   int have_viscous = 0, have_viscous_law = 0;
+   float viscous_mu = 0.0f;
+   sph_hip_viscosity_law viscous_law = {};
+   DevBuf<float4> viscous_R;
+   DevBuf<float> viscous_M;
 
    // step monitor (sph_hip_record_monitor): mon_rows rows; mon_step = steps enqueued since the call, mon_filled =
    // rows those steps have filled, mon_row_now = the row the step being enqueued fills (-1: none).  The partial

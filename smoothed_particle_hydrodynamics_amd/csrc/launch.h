@@ -964,6 +964,34 @@ int launch_cohesion(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- viscous stress (viscous_kernels.h; contract: viscous_policy.h; decision: launch_policy.h) --------------------
+// Behind the step's acceleration pass and cohesion, in front of XSPH, buoyancy and the integrate: the stage of S_k's
+// velocities with the densities the step's density pass left (and, with a law, of the channels launch_scalars staged
+// earlier in this step), then the pass over the lists and counts the density pass left, which adds to acc of the
+// sorted state.  mu, the law and the constants travel by value: a later setter does not reach the steps already
+// queued.  Nothing synchronises.
+int launch_viscous(sph_hip_context* ctx)
+{
+   const bool law = ctx->have_viscous_law != 0;
+   bind_flags([&](auto L) {
+      hipLaunchKernelGGL((k_viscous_stage<L.value>), dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream,
+                         ctx->velp[ctx->cur], ctx->posm[ctx->cur], ctx->rho, ctx->meta,
+                         L.value ? ctx->scalar_Ts.get() : (const float4*)nullptr, ctx->viscous_mu, ctx->viscous_law,
+                         ctx->viscous_R, L.value ? ctx->viscous_M.get() : (float*)nullptr);
+   }, law);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   static_assert(TILE_THREADS == 256, "the viscous kernel maps one workgroup to 256 sorted particles");
+   bind_flags([&](auto U, auto W, auto L) {
+      hipLaunchKernelGGL((k_viscous_apply<U.value, W.value, L.value>), dim3(div_up(ctx->n, TILE_THREADS)),
+                         dim3(TILE_THREADS), 0, ctx->stream, ctx->posm[ctx->cur], ctx->viscous_R,
+                         L.value ? ctx->viscous_M.get() : (const float*)nullptr, ctx->ncount, ctx->cell_start, ctx->meta,
+                         ctx->grid, k, ctx->viscous_mu, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, ctx->list_cap,
+                         ctx->use_tiled ? 1 : 0, ctx->acc);
+   }, unit_scale(ctx->prm), ctx->caps.wide != 0, law);
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // ---- xsph (xsph_kernels.h; contract: xsph_policy.h; decision: launch_policy.h) ----------------------------------
 // Behind the step's acceleration pass and cohesion, in front of buoyancy and the integrate: the stage of S_k's
 // velocities with the densities the step's density pass left, then the pass over the lists and counts it left,
@@ -1128,14 +1156,17 @@ int step_impl(sph_hip_context* ctx, bool timed)
    const bool buoyant = step_launches_buoyancy(ctx->have_buoyancy != 0, ctx->n_scalars, ctx->n);
    // cohesion: one more such kernel, in front of buoyancy's - either of them takes the step off the fused route
    const bool cohesive = step_launches_cohesion(ctx->have_cohesion != 0, ctx->n);
+   // viscous stress: two more such kernels, behind cohesion's and in front of XSPH's; the step keeps the prehash
+   const bool viscous = step_launches_viscous(ctx->have_viscous != 0, ctx->n);
    const bool fused = !cohesive &&
-                      fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0, ctx->n_obst,
-                                     loads_pending(ctx), buoyant);
+                      fuse_integrate(hash_too, ctx->use_tiled != 0, ctx->n, ctx->no_fused_integrate != 0 || viscous,
+                                     ctx->n_obst, loads_pending(ctx), buoyant);
    // xsph: two more such kernels, behind cohesion's and in front of buoyancy's; the step keeps the prehash
    const bool smoothing = step_launches_xsph(ctx->have_xsph != 0, ctx->n);
    const bool fuse_now = fused && !smoothing;
    if ((rc = launch_accel(ctx, 0, nullptr, fuse_now))) return rc;
    if (cohesive && (rc = launch_cohesion(ctx))) return rc;
+   if (viscous && (rc = launch_viscous(ctx))) return rc;
    if (smoothing && (rc = launch_xsph(ctx))) return rc;
    if (buoyant && (rc = launch_buoyancy(ctx))) return rc;
    if ((rc = mark_phase(ctx, se, 5, st))) return rc;

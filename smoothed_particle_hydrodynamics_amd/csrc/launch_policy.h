@@ -380,6 +380,12 @@ inline bool step_launches_cohesion(bool have_cohesion, int n) { return have_cohe
 // setting launches what it always launched.
 inline bool step_launches_xsph(bool have_xsph, int n) { return have_xsph && n > 0; }
 
+// Whether a step launches k_viscous_stage and k_viscous_apply (viscous_policy.h) between its acceleration pass and
+// its integrate, behind cohesion's kernel and in front of XSPH's: a mu is set and the step has particles.  Such a
+// step gives up the fused integrate and keeps the prehash, as a smoothing step does.  A context without the setting
+// launches what it always launched.
+inline bool step_launches_viscous(bool have_viscous, int n) { return have_viscous && n > 0; }
+
 // ---- step monitor (monitor_policy.h) ---------------------------------------------------------------
 // The grid of k_monitor_particles: workgroups of MONITOR_THREADS lanes that stride over the live slots, one per 256
 // slots up to MONITOR_MAX_BLOCKS - a bounded number of partial rows, which one workgroup folds (k_monitor_finish).

@@ -558,6 +558,8 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    ctx->have_buoyancy = 0;   // (buoyancy reads the scalars: it goes with them)
    ctx->have_cohesion = 0;   // cohesion is a setting of the upload it was made for
    ctx->have_xsph = 0;       // and so is the velocity smoothing
+   ctx->have_viscous = 0;    // and the viscous stress, with its law
+   ctx->have_viscous_law = 0;
    ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
    ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
    ports_mass_rule(ctx, n == 0);
@@ -1328,6 +1330,7 @@ int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int
    if (const char* why = scalar_ports_check(ctx->n_scalars, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = cohesion_ports_check(ctx->have_cohesion != 0, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = xsph_ports_check(ctx->have_xsph != 0, ne, ns)) return refuse(ctx, who, why);
+   if (const char* why = viscous_ports_check(ctx->have_viscous != 0, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = monitor_ports_check(ctx->mon_rows, ne, ns)) return refuse(ctx, who, why);
    // a pending prehash counted for a build whose entries the ports may change first
    if ((rc = drop_prehash(ctx))) return rc;
@@ -2035,6 +2038,7 @@ int sph_hip_set_scalars(sph_hip_context* ctx, int n, const float* values4, const
       ctx->n_scalars = 0;
       ctx->n_scalar_sources = 0;
       ctx->have_buoyancy = 0;
+      ctx->have_viscous_law = 0;   // (a viscosity law reads the scalars: it goes with them, its mu stays)
       return SPH_HIP_OK;
    }
    if (!ctx->scalar_T) {
@@ -2245,6 +2249,62 @@ int sph_hip_get_xsph(sph_hip_context* ctx, float* eps)
    if (rc) return rc;
    if (!eps) return refuse(ctx, "sph_hip_get_xsph", "null output");
    *eps = ctx->have_xsph ? ctx->xsph_eps : 0.0f;
+   return SPH_HIP_OK;
+}
+
+// ---- viscous stress (viscous_kernels.h; contract and checks: viscous_policy.h) ---------------------------------
+
+int sph_hip_set_viscous_stress(sph_hip_context* ctx, float mu, const sph_hip_viscosity_law* law)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_viscous_stress";
+   if (const char* why = viscous_mu_finite_check(mu)) return refuse(ctx, who, why);
+   if (const char* why = viscous_mu_sign_check(mu)) return refuse(ctx, who, why);
+   const bool with_law = law && !viscous_is_off(mu);
+   if (!viscous_is_off(mu)) {   // (switching it off is never refused)
+      if (law) {
+         if (const char* why = viscous_law_channel_check(*law)) return refuse(ctx, who, why);
+         if (const char* why = viscous_law_keys_check(*law)) return refuse(ctx, who, why);
+         if (const char* why = viscous_law_values_finite_check(*law)) return refuse(ctx, who, why);
+         if (const char* why = viscous_law_ascending_check(*law)) return refuse(ctx, who, why);
+         if (const char* why = viscous_law_factors_finite_check(*law)) return refuse(ctx, who, why);
+         if (const char* why = viscous_law_factors_sign_check(*law)) return refuse(ctx, who, why);
+         if (const char* why = viscous_law_scalars_check(ctx->n_scalars)) return refuse(ctx, who, why);
+      }
+      const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global && !ctx->had_exchange;
+      if (const char* why = viscous_mode_check(ctx->mode == SPH_HIP_MODE_FULL)) return refuse(ctx, who, why);
+      if (const char* why = viscous_slab_check(whole)) return refuse(ctx, who, why);
+      if (const char* why = viscous_ports_set_check(ports_active(ctx->n_emit, ctx->n_sink))) return refuse(ctx, who, why);
+      // the staged rows: at the first setting that needs them, so a context that never asks keeps its footprint
+      DevBuf<float4> rows;
+      DevBuf<float> mus;
+      if ((!ctx->viscous_R && dev_alloc(rows, (size_t)ctx->capacity) != hipSuccess) ||
+          (with_law && !ctx->viscous_M && dev_alloc(mus, (size_t)ctx->capacity) != hipSuccess)) {
+         (void)hipGetLastError();
+         ctx->err = "sph_hip_set_viscous_stress: cannot allocate the staged rows of " + std::to_string(ctx->capacity) +
+                    " particles";
+         return SPH_HIP_ERR_CAPACITY;
+      }
+      if (!ctx->viscous_R) ctx->viscous_R = std::move(rows);
+      if (with_law && !ctx->viscous_M) ctx->viscous_M = std::move(mus);
+   }
+   // (a step takes mu and the law by value: the steps already queued keep theirs)
+   ctx->have_viscous = viscous_is_off(mu) ? 0 : 1;
+   ctx->viscous_mu = ctx->have_viscous ? mu : 0.0f;
+   ctx->have_viscous_law = with_law ? 1 : 0;
+   ctx->viscous_law = viscous_law_clean(with_law ? law : nullptr);
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_viscous_stress(sph_hip_context* ctx, float* mu, sph_hip_viscosity_law* law, int* have_law)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const bool with_law = ctx->have_viscous && ctx->have_viscous_law;
+   if (mu) *mu = ctx->have_viscous ? ctx->viscous_mu : 0.0f;
+   if (law) *law = viscous_law_clean(with_law ? &ctx->viscous_law : nullptr);
+   if (have_law) *have_law = with_law ? 1 : 0;
    return SPH_HIP_OK;
 }
 

@@ -92,6 +92,7 @@ from .obstacles import (SphBody, SphBodyState, SphMotionKey, SphMotionPath, SphO
 from .gauges import GaugeReadings, GaugeRecord, SphGauge  # noqa: E402,F401
 from .ports import PortTotals, SphEmitter, SphSink  # noqa: E402,F401
 from .scalars import SphBuoyancy, SphScalarSource  # noqa: E402,F401
+from .viscosity import SphViscosityLaw  # noqa: E402,F401
 
 # every symbol include/sph_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
@@ -190,6 +191,8 @@ PROTOTYPES = {
     "sph_hip_get_cohesion": (C.c_int, [_ctx, _P(C.c_float)]),
     "sph_hip_set_xsph": (C.c_int, [_ctx, C.c_float]),
     "sph_hip_get_xsph": (C.c_int, [_ctx, _P(C.c_float)]),
+    "sph_hip_set_viscous_stress": (C.c_int, [_ctx, C.c_float, _P(SphViscosityLaw)]),
+    "sph_hip_get_viscous_stress": (C.c_int, [_ctx, _P(C.c_float), _P(SphViscosityLaw), _P(C.c_int)]),
     "sph_hip_record_monitor": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
     "sph_hip_get_monitor_record": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sph_hip_get_velocity_gradients": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -641,6 +641,61 @@ def noisy_block(n, amplitude, seed=42, neighbors=32.0, cells=None):
     return p, pos, vel, mass
 
 
+def viscous_stable_mu(p, fraction=0.25, neighbors=32.0, mass=1.0):
+    """A dynamic viscosity for SPH.setViscousStress that keeps a step damping deep inside a fluid of ~`neighbors`
+    particles of `mass` inside radius h.  The explicit term is a convex combination while
+    dt * (1 / m_i) * sum_j mu * V_i * V_j * kernel3 * (h - d_ij) <= 1 (include/sph_hip.h: viscous stress); with
+    volumes that tile the fluid that is dt * (mu / rho) * kernel3 * pi * h^4 / 3 in scaled lengths
+    (scalar_stable_kappa's integral), rho the bulk density mass * 3 * neighbors / (4 pi h^3).  Returns the mu for
+    which the product is `fraction`.  Near a free surface densities are lower than the bulk's: keep a margin."""
+    hs = float(p.hscaled)
+    rho = float(mass) * 3.0 * float(neighbors) / (4.0 * math.pi * hs ** 3)
+    return scalar_stable_kappa(p, fraction) * rho
+
+
+def dam_break_viscous(n, mu, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0, seed=42,
+                      gravity=-9.81):
+    """The surging dam of dam_break_dye without the dye - gravity along -y, the walls on, the surge along +x - as a
+    thick fluid: a viscous stress of the dynamic viscosity `mu` (viscous_stable_mu gives the scale).  Returns
+    (params, pos, vel, mass, mu): setParticles, then setViscousStress."""
+    p, pos, vel, mass, _ = dam_break_dye(n, 1.0, surge, box, fill, neighbors, seed, gravity)
+    return p, pos, vel, mass, float(mu)
+
+
+def shear_layer(n, speed, seed=42, neighbors=32.0, cells=None):
+    """A resting block whose upper half moves: droplet's cubic random fill in the middle of the box (gravity and
+    the central mass off, the walls on, unit masses) with the velocity (speed, 0, 0) for every particle above the
+    block's mid-height and rest below it - a velocity jump one particle wide, which a viscous stress spreads into a
+    layer while the total momentum stays.  Returns (params, pos, vel, mass)."""
+    p, pos, _, mass, _ = droplet(n, 0.0, neighbors, cells, seed)
+    vel = np.zeros((n, 3), np.float32)
+    vel[pos.reshape(-1, 3)[:, 1] > np.float32(0.5) * np.float32(p.max_y), 0] = np.float32(speed)
+    return p, pos, np.ascontiguousarray(vel.reshape(-1)), mass
+
+
+def cooling_flow(n, hot=1.0, stiffening=50.0, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0,
+                 seed=42, gravity=-9.81):
+    """Lava over a cold floor: dam_break_dye's surging dam, warm through and through - channel 0 is a temperature
+    that starts at `hot` and diffuses (scalar_stable_kappa) - over heated_floor's slab, which holds the floor at 0,
+    with an exponential ViscosityLaw on the channel: the factor is 1 at `hot` and `stiffening` at 0, so the tongue's
+    underside thickens as it cools while its top keeps running.  mu is chosen so that the stiffest fluid stays inside
+    the explicit range (viscous_stable_mu over `stiffening`).  Returns (params, pos, vel, mass, values[n, 4],
+    kappa[4], [ScalarSource], mu, ViscosityLaw): setParticles, setScalars, setScalarSources, then
+    setViscousStress(mu, law)."""
+    from .scalars import ScalarSource
+    from .viscosity import ViscosityLaw
+    p, pos, vel, mass, _ = dam_break_dye(n, 1.0, surge, box, fill, neighbors, seed, gravity)
+    h = float(p.h)
+    values = np.zeros((n, 4), np.float32)
+    values[:, 0] = np.float32(hot)
+    kappa = np.zeros(4, np.float32)
+    kappa[0] = scalar_stable_kappa(p)
+    slab = ScalarSource.hold((-h, -h, -h), (float(p.max_x) + h, h, float(p.max_z) + h), 0, 0.0)
+    law = ViscosityLaw.exponential(0, hot, math.log(float(stiffening)) / float(hot), 0.0, hot)
+    mu = viscous_stable_mu(p, 0.25, neighbors) / float(stiffening)
+    return p, pos, vel, mass, values, kappa, [slab], float(mu), law
+
+
 def rankine_vortex(n, omega, core, neighbors=32.0, cells=None, seed=42):
     """A still block of fluid - droplet's fill, box and constants - swirling about the vertical (y) axis through its
     middle as a Rankine vortex: solid-body rotation at the rate `omega` within the radius `core` of the axis,

@@ -21,6 +21,7 @@ from . import scalars as _S
 from . import colormaps as _CM
 from . import monitor as _M
 from . import velgrad as _V
+from . import viscosity as _VS
 from .lib import ARITH_EXACT, ARITH_FAST, MODE_FULL, MODE_FULL_FAST, MODE_REF, Bodies, Context, SphCamera, SphRenderParams, SphSceneParams, SphTintParams, TracerPath, Tracers, _ptr, default_params
 
 __all__ = ["SPH", "Particle", "SurfaceMesh", "Tracers", "TracerPath", "Camera", "RenderResult", "ScalarRenderResult", "write_png", "MODE_REF", "MODE_FULL", "MODE_FULL_FAST", "ARITH_EXACT", "ARITH_FAST"]
@@ -624,6 +625,27 @@ class SPH(Context):
         e = C.c_float(0.0)
         self.call("sph_hip_get_xsph", C.byref(e))
         return float(e.value)
+
+    # ---- viscous stress (sph_hip_set_viscous_stress) ------------------------------------------------
+    def setViscousStress(self, mu, law=None):
+        """A pairwise viscous force of the dynamic viscosity `mu` from the next enqueued step on (include/sph_hip.h:
+        viscous stress): every particle takes (1 / m_i) * sum_j mu_ij * V_i * V_j * L(d_ij) * (v_j - v_i) on top of
+        its own acceleration, V = m / rho and L the viscosity Laplacian - velocity differences decay, a uniform
+        motion keeps its bits, and the force addends of a pair negate each other for any masses.  With a `law`
+        (viscosity.ViscosityLaw) mu is multiplied per particle by the law's factor of a carried channel and a pair
+        takes the mean of its two; a law needs setScalars first, and setScalars(None) drops it and keeps mu.  mu is
+        finite and >= 0; None or 0 switches the term off.  The scheme is explicit: a step damps while
+        dt * (1 / m_i) * sum_j mu_ij V_i V_j L <= 1 for every particle, and nothing polices that
+        (scenes.viscous_stable_mu gives a mu for the bulk).  FULL and FULL_FAST contexts without ports; a new
+        setParticles drops the setting."""
+        q = None if law is None else C.byref(law.to_struct())
+        self.call("sph_hip_set_viscous_stress", C.c_float(0.0 if mu is None else float(mu)), q)
+
+    def getViscousStress(self):
+        """(mu, law): the mu in force, 0.0 when the term is off, and its ViscosityLaw or None."""
+        mu, law, have = C.c_float(0.0), _VS.SphViscosityLaw(), C.c_int(0)
+        self.call("sph_hip_get_viscous_stress", C.byref(mu), C.byref(law), C.byref(have))
+        return float(mu.value), (_VS.from_struct(law) if have.value else None)
 
     # ---- step monitor (sph_hip_record_monitor) ------------------------------------------------------
     def recordMonitor(self, rows, every=1, quantum_log2=_M.QUANTUM_DEFAULT):
