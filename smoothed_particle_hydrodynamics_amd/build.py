@@ -23,7 +23,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "cohesion_kernels.h", "cohesion_policy.h", "xsph_kernels.h", "xsph_policy.h",
            "viscous_kernels.h", "viscous_policy.h",
            "monitor_kernels.h", "monitor_policy.h",
-           "velgrad_kernels.h", "velgrad_policy.h",
+           "velgrad_kernels.h", "velgrad_policy.h", "pair_walk.h",
            os.path.join("..", "..", "include", "sph_hip.h")]
 
 # -ffp-contract=off: the reference's x86-64 IEEE build has no FMA contraction; neighbour

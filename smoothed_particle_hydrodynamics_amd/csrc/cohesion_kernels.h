@@ -3,83 +3,37 @@
 // front of buoyancy's.  No existing kernel changes: the integrate of the context, whichever form launch_integrate
 // picks, runs behind it from the rows it leaves.
 //
-// k_cohesion_apply is k_scalars_step's skeleton (scalar_kernels.h) - a fourth consumer of the neighbour lists the
-// density pass left for the acceleration pass.  A lane takes its list a block of eight entries per trip, the next
-// block requested before this one's gathers; a workgroup or a lane without a list walks the nine cell rows as
-// k_particle_density does, by the scalar pass's route decisions (launch_policy.h: scalar_workgroup_route,
-// scalar_lane_route).  Same pairs, same order, same arithmetic: same bits.  It gathers posm[q] only - 16 bytes per
-// neighbour, the mass in .w - and reads and writes its own acc[p] only, so nothing races.  The only LDS is its copy
-// of its TileDesc, and every local array is indexed by unrolled constants (none lives in scratch memory).
+// k_cohesion_apply is one of the consumers of the neighbour lists the density pass left for the acceleration pass:
+// the walk, on either route, is pair_walk.h's.  It gathers posm[q] only - 16 bytes per neighbour, the mass in .w, no
+// payload - and reads and writes its own acc[p] only, so nothing races.
 //
 // One kernel is enough because nothing between the density pass and the integrate of an unfused step writes what
 // it reads: posm[cur], ncount, nlist, nlist_overflow and tile_desc are written by the cell build and the density
 // kernels only (cohesion, "The premise"), and k_full_accel_lists / k_full_accel take them all const.
 #pragma once
 
-#include "cell_build.h"
 #include "cohesion_policy.h"
-#include "full_tiled.h"
-#include "neighbor_lists.h"
-#include "pair_math.h"
+#include "pair_walk.h"
 
-// one neighbour into the sum: the weight is the density pass's own pair term
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void cohesion_add(const PairConsts& k, const float4& pi, const float4& pj, CohesionSum& s)
-{
-   float dx, dy, dz;
-   float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
-   if (!UNIT_SCALE) d *= k.sim_scale;
-   const float w = density_term<UNIT_SCALE>(k, pj.w, d);
-   cohesion_pair(s, w, dx, dy, dz, k.sim_scale, UNIT_SCALE);
-}
+// the pass's accumulator (pair_walk.h): the weight of a pair is the density pass's own pair term
+struct CohesionPairs {
+   const PairConsts& k;
+   CohesionSum s;
 
-// the list walk of one lane (scalars_from_lists' loop: one 16-byte load per eight entries)
-template <bool UNIT_SCALE, bool WIDE>
-__device__ __forceinline__ void cohesion_from_lists(int cnt, const ListReader& lr, const TileDesc& d, const PairConsts& k,
-                                                    const float4& pi, const float4* __restrict__ posm, CohesionSum& s)
-{
-   const int lastb = cnt > 0 ? (cnt - 1) >> 3 : 0;
-   uint4 blk = lr.block(0);
-   for (int j0 = 0; j0 < cnt; j0 += 8) {
-      uint32_t entry[8];
-      list_block_entries(blk, entry);
-      blk = lr.block(min((j0 >> 3) + 1, lastb));
-      float4 pj[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const uint32_t e = j0 + u < cnt ? entry[u] : entry[0];      // (entry 0 of a block in use is a neighbour)
-         const int q = ListEntry<WIDE>::tile(e) - ListEntry<WIDE>::shift(d, e);
-         pj[u] = posm[q];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-         if (j0 + u < cnt) cohesion_add<UNIT_SCALE>(k, pi, pj[u], s);
+   struct Payload {};
+   template <class Index>
+   __device__ __forceinline__ Payload gather(Index) const { return Payload{}; }
+
+   template <bool UNIT_SCALE>
+   __device__ __forceinline__ void add(const float4& pi, const float4& pj, const Payload&)
+   {
+      float dx, dy, dz;
+      float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
+      if (!UNIT_SCALE) d *= k.sim_scale;
+      const float w = density_term<UNIT_SCALE>(k, pj.w, d);
+      cohesion_pair(s, w, dx, dy, dz, k.sim_scale, UNIT_SCALE);
    }
-}
-
-// the row walk of one lane (k_particle_density's: pressure_kernels.h)
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void cohesion_from_rows(int p, const CellGrid& g, const uint32_t* __restrict__ cell_start,
-                                                   const PairConsts& k, const float4& pi, const float4* __restrict__ posm,
-                                                   CohesionSum& s)
-{
-   int cx, cy, cz;
-   cell_of(g, pi.x, pi.y, pi.z, cx, cy, cz);
-   RowRanges r;
-   row_ranges(g, cell_start, cx, cy, cz, r);
-#pragma unroll 1
-   for (int row = 0; row < 9; row++) {
-      uint32_t b, e;
-      row_range(r, row, b, e);
-      for (uint32_t q = b; q < e; q++) {
-         if (q == (uint32_t)p) continue;
-         const float4 pj = posm[q];
-         float dx, dy, dz;
-         const float d2 = dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz);
-         if (d2 < k.h2) cohesion_add<UNIT_SCALE>(k, pi, pj, s);
-      }
-   }
-}
+};
 
 // One workgroup per 256 sorted particles of the live range.  tiled: the context's density pass wrote lists and
 // flags (else nlist, nlist_overflow, desc are not read).  gamma and the constants arrive by value: a later setter
@@ -92,32 +46,15 @@ k_cohesion_apply(const float4* __restrict__ posm, const int32_t* __restrict__ nc
                  float4* __restrict__ acc)
 {
    __shared__ TileDesc sd;
-   const int begin = meta[META_SUM_BEGIN], end = meta[META_SUM_END];
-   const int tid = threadIdx.x;
-   const int wg = xcd_workgroup(blockIdx.x, gridDim.x);
-   const int p0 = begin + wg * TILE_THREADS;
-   if (p0 >= end) return;   // (the whole workgroup)
-   const int p = p0 + tid;
-   const bool live = p < end;
-   // (workgroup-uniform: the barrier inside tile_desc_load is reached by every lane or by none)
-   const uint32_t flag = tiled ? nlist_overflow[wg] : LISTS_NONE;
-   const int wg_route = scalar_workgroup_route(tiled != 0, false, flag);
-   if (wg_route == SCALAR_ROUTE_LISTS) tile_desc_load(desc, wg, sd);
-   if (!live) return;
+   const PairLane w = pair_workgroup(meta, tiled, 0, nlist_overflow, desc, sd);
+   if (!w.live) return;
+   const int p = w.p;
 
    const float4 pi = posm[p];
-   CohesionSum s = {0.0f, 0.0f, 0.0f};
-   int lane_route = SCALAR_ROUTE_ROWS;
-   if (wg_route == SCALAR_ROUTE_LISTS) {
-      const int cnt = ncount[p];
-      const ListReader lr(nlist, wg, list_cap, tid);
-      const uint32_t first_word = (flag == LISTS_SOME && cnt > 0) ? (lr.no_list() ? NLIST_NO_LIST : 0u) : 0u;
-      lane_route = scalar_lane_route(wg_route, flag, cnt, first_word);
-      if (lane_route == SCALAR_ROUTE_LISTS) cohesion_from_lists<UNIT_SCALE, WIDE>(cnt, lr, sd, k, pi, posm, s);
-   }
-   if (lane_route == SCALAR_ROUTE_ROWS) cohesion_from_rows<UNIT_SCALE>(p, g, cell_start, k, pi, posm, s);
+   CohesionPairs pairs = {k, {0.0f, 0.0f, 0.0f}};
+   pair_walk<UNIT_SCALE, WIDE>(w, sd, ncount, nlist, list_cap, g, cell_start, k.h2, pi, posm, pairs);
 
-   const CohesionSum c = cohesion_accel(gamma, s);
+   const CohesionSum c = cohesion_accel(gamma, pairs.s);
    if (!cohesion_acts(c)) return;
    float4 a = acc[p];
    cohesion_apply(c, k.cfl_limit, k.cfl_limit2, a.x, a.y, a.z);

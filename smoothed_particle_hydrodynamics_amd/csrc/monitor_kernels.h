@@ -9,9 +9,10 @@
 // shuffles (an int64 as two halves), a workgroup through LDS, and every workgroup stores ONE partial row.  The row
 // takes no atomics: six contended atomics per workgroup are what full_tiled.h measured away.
 //
-// k_monitor_pairs is k_cohesion_apply's skeleton (cohesion_kernels.h) - a fifth consumer of the neighbour lists the
-// density pass left - directly behind the scalar pass, on contexts that carry scalars: S_p, the factor of
-// dt * kappa in the pass's convexity condition.  It gathers posm[q] and Vs[q] and writes one partial per workgroup.
+// k_monitor_pairs is one of the consumers of the neighbour lists the density pass left - the walk, on either route,
+// is pair_walk.h's - directly behind the scalar pass, on contexts that carry scalars: S_p, the factor of
+// dt * kappa in the pass's convexity condition.  It gathers posm[q] and Vs[q], 20 bytes per neighbour in two
+// streams, and writes one partial per workgroup.
 // Nothing between the density pass and this launch writes its inputs: posm[cur], ncount, nlist, nlist_overflow and
 // tile_desc are written by the cell build and the density kernels only (cohesion, "The premise"), Vs by
 // k_scalars_stage only, and k_scalars_step - the one launch between the stage and this one - takes them all const
@@ -22,12 +23,8 @@
 // memory).
 #pragma once
 
-#include "cell_build.h"
-#include "full_tiled.h"
-#include "launch_policy.h"
 #include "monitor_policy.h"
-#include "neighbor_lists.h"
-#include "pair_math.h"
+#include "pair_walk.h"
 #include "scalar_kernels.h"
 
 static_assert(MONITOR_THREADS % SPH_WAVE == 0, "a monitor workgroup is whole waves");
@@ -111,66 +108,25 @@ k_monitor_particles(const float4* __restrict__ posm, const float4* __restrict__ 
 }
 
 // ---- the pairs: one workgroup per 256 sorted particles --------------------------------------------------------------
-// one neighbour's operands into S_p (scalars_add's distance)
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void monitor_add(const PairConsts& k, const float4& pi, const float4& pj, float vj, float& S)
-{
-   float dx, dy, dz;
-   float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
-   if (!UNIT_SCALE) d *= k.sim_scale;
-   monitor_pair(S, vj, d, k.hscaled, k.kernel3);
-}
+// the pass's accumulator (pair_walk.h): S_p, by the scalar pass's distance
+struct MonitorPairs {
+   const PairConsts& k;
+   const float* __restrict__ Vs;
+   float S;
 
-// the list walk of one lane (scalars_from_lists' loop: one 16-byte load per eight entries)
-template <bool UNIT_SCALE, bool WIDE>
-__device__ __forceinline__ void monitor_from_lists(int cnt, const ListReader& lr, const TileDesc& d, const PairConsts& k,
-                                                   const float4& pi, const float4* __restrict__ posm,
-                                                   const float* __restrict__ Vs, float& S)
-{
-   const int lastb = cnt > 0 ? (cnt - 1) >> 3 : 0;
-   uint4 blk = lr.block(0);
-   for (int j0 = 0; j0 < cnt; j0 += 8) {
-      uint32_t entry[8];
-      list_block_entries(blk, entry);
-      blk = lr.block(min((j0 >> 3) + 1, lastb));
-      float4 pj[8];
-      float vj[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const uint32_t e = j0 + u < cnt ? entry[u] : entry[0];      // (entry 0 of a block in use is a neighbour)
-         const int q = ListEntry<WIDE>::tile(e) - ListEntry<WIDE>::shift(d, e);
-         pj[u] = posm[q];
-         vj[u] = Vs[q];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-         if (j0 + u < cnt) monitor_add<UNIT_SCALE>(k, pi, pj[u], vj[u], S);
-   }
-}
+   using Payload = float;   // Vs: the volume of sorted particle q (k_scalars_stage)
+   template <class Index>
+   __device__ __forceinline__ Payload gather(Index q) const { return Vs[q]; }
 
-// the row walk of one lane (k_particle_density's: pressure_kernels.h)
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void monitor_from_rows(int p, const CellGrid& g, const uint32_t* __restrict__ cell_start,
-                                                  const PairConsts& k, const float4& pi, const float4* __restrict__ posm,
-                                                  const float* __restrict__ Vs, float& S)
-{
-   int cx, cy, cz;
-   cell_of(g, pi.x, pi.y, pi.z, cx, cy, cz);
-   RowRanges r;
-   row_ranges(g, cell_start, cx, cy, cz, r);
-#pragma unroll 1
-   for (int row = 0; row < 9; row++) {
-      uint32_t b, e;
-      row_range(r, row, b, e);
-      for (uint32_t q = b; q < e; q++) {
-         if (q == (uint32_t)p) continue;
-         const float4 pj = posm[q];
-         float dx, dy, dz;
-         const float d2 = dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz);
-         if (d2 < k.h2) monitor_add<UNIT_SCALE>(k, pi, pj, Vs[q], S);
-      }
+   template <bool UNIT_SCALE>
+   __device__ __forceinline__ void add(const float4& pi, const float4& pj, float vj)
+   {
+      float dx, dy, dz;
+      float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
+      if (!UNIT_SCALE) d *= k.sim_scale;
+      monitor_pair(S, vj, d, k.hscaled, k.kernel3);
    }
-}
+};
 
 // tiled, force_rows: the scalar pass's own route switches (k_scalars_step).  Every workgroup of the grid stores its
 // partial part[blockIdx.x] - one past the live range an empty one - so nothing returns before the fold.
@@ -184,36 +140,18 @@ k_monitor_pairs(const float4* __restrict__ posm, const float* __restrict__ Vs, c
 {
    static_assert(TILE_THREADS == MONITOR_THREADS, "the pair pass folds with the monitor's workgroup size");
    __shared__ TileDesc sd;
-   const int begin = meta[META_SUM_BEGIN], end = meta[META_SUM_END];
-   const int tid = threadIdx.x;
-   const int wg = xcd_workgroup(blockIdx.x, gridDim.x);
-   const int p0 = begin + wg * TILE_THREADS;
-   const bool any = p0 < end;   // (the whole workgroup)
-   const int p = p0 + tid;
-   const bool live = p < end;
-   // (workgroup-uniform: the barrier inside tile_desc_load is reached by every lane or by none)
-   const uint32_t flag = (tiled && any) ? nlist_overflow[wg] : LISTS_NONE;
-   const int wg_route = scalar_workgroup_route(tiled != 0, force_rows != 0, flag);
-   if (any && wg_route == SCALAR_ROUTE_LISTS) tile_desc_load(desc, wg, sd);
+   const PairLane w = pair_workgroup(meta, tiled, force_rows, nlist_overflow, desc, sd);
 
    MonitorPairAcc a;
    monitor_pair_clear(a);
-   if (live) {
-      const float4 pi = posm[p];
-      float S = 0.0f;
-      int lane_route = SCALAR_ROUTE_ROWS;
-      if (wg_route == SCALAR_ROUTE_LISTS) {
-         const int cnt = ncount[p];
-         const ListReader lr(nlist, wg, list_cap, tid);
-         const uint32_t first_word = (flag == LISTS_SOME && cnt > 0) ? (lr.no_list() ? NLIST_NO_LIST : 0u) : 0u;
-         lane_route = scalar_lane_route(wg_route, flag, cnt, first_word);
-         if (lane_route == SCALAR_ROUTE_LISTS) monitor_from_lists<UNIT_SCALE, WIDE>(cnt, lr, sd, k, pi, posm, Vs, S);
-      }
-      if (lane_route == SCALAR_ROUTE_ROWS) monitor_from_rows<UNIT_SCALE>(p, g, cell_start, k, pi, posm, Vs, S);
-      monitor_pair_offer(a, S);
+   if (w.live) {
+      const float4 pi = posm[w.p];
+      MonitorPairs pairs = {k, Vs, 0.0f};
+      pair_walk<UNIT_SCALE, WIDE>(w, sd, ncount, nlist, list_cap, g, cell_start, k.h2, pi, posm, pairs);
+      monitor_pair_offer(a, pairs.S);
    }
    monitor_pair_block_fold(a);
-   if (tid == 0) part[blockIdx.x] = a;
+   if (w.tid == 0) part[blockIdx.x] = a;
 }
 
 // ---- the fold: one workgroup ------------------------------------------------------------------------------------

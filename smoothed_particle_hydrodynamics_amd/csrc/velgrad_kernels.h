@@ -2,9 +2,10 @@
 // per-particle pair kernel outside the step, behind a cell build of the current state, and the copy of its rows into
 // particle-id order for the getter.  No existing kernel changes, and a context that never asks launches neither.
 //
-// k_velgrad_particles is cohesion_from_rows' walk (cohesion_kernels.h), which is k_particle_density's
-// (pressure_kernels.h): the nine cell rows of the particle's cell, itself skipped, the d2 < h2 test in front of the
-// second gather.  It gathers posm[q] - 16 bytes, the mass in .w - for every candidate and velp[q] for members only.
+// k_velgrad_particles is pair_walk_rows' walk (pair_walk.h), which is k_particle_density's (pressure_kernels.h), in a
+// copy of its own - on the shared walk the compiler vectorised its fifteen sums differently, with two more vector
+// registers (the pair walk): the nine cell rows of the particle's cell, itself skipped, the d2 < h2 test in
+// front of the second gather.  It gathers posm[q] - 16 bytes, the mass in .w - for every candidate and velp[q] for members only.
 // There is no neighbour-list route: by the time a caller can ask, the lists are those of the state before the last
 // integrate, and the cell build in front of this pass has moved the particles they index.  The kernel uses no LDS,
 // its fifteen accumulators are named scalars (VelgradSums), and no local is indexed by anything but unrolled

@@ -4,14 +4,14 @@
 // whichever form launch_integrate picks, runs behind them from the rows they leave.
 //
 // k_viscous_stage is k_xsph_stage's shape (xsph_kernels.h): one lane per live sorted slot writes R[p] = {v, m / rho}
-// and, with a law, M[p] = mu * factor(Ts[p].c).  k_viscous_apply is k_xsph_apply's skeleton - a sixth consumer of the
-// neighbour lists the density pass left for the acceleration pass.  A lane takes its list a block of eight entries per
-// trip, the next block requested before this one's gathers; a workgroup or a lane without a list walks the nine cell
-// rows as k_particle_density does, by the scalar pass's route decisions (launch_policy.h: scalar_workgroup_route,
-// scalar_lane_route).  Same pairs, same order, same arithmetic: same bits.  It gathers posm[q] and R[q] - 32 bytes
-// per neighbour in two streams - and with a law M[q], 36 bytes in three; it reads and writes its own acc[p] only.  So
-// nothing races, and every sum reads S_k's velocities.  The only LDS is its copy of its TileDesc, and every local
-// array is indexed by unrolled constants (none lives in scratch memory).
+// and, with a law, M[p] = mu * factor(Ts[p].c).  k_viscous_apply is a consumer of the neighbour lists the density pass
+// left for the acceleration pass, and its walk is pair_walk.h's - in a copy of its own: on the shared walk the compiler
+// allotted its instantiations 100 and 114 vector registers for 102 and 112 and packed the pair arithmetic of two of
+// them differently (the pair walk), and a pass moves there only with the registers and the arithmetic it
+// has.  A fix to pair_walk.h's workgroup step, list walk or row walk is to be made here too.  It gathers posm[q] and
+// R[q] - 32 bytes per neighbour in two streams - and with a law M[q], 36 bytes in three; it reads and writes its own
+// acc[p] only.  So nothing races, and every sum reads S_k's velocities.  The only LDS is its copy of its TileDesc,
+// and every local array is indexed by unrolled constants (none lives in scratch memory).
 //
 // Nothing between the density pass and these kernels writes what they read: posm[cur], ncount, nlist,
 // nlist_overflow and tile_desc are written by the cell build and the density kernels only, rho by the density
@@ -60,7 +60,7 @@ __device__ __forceinline__ void viscous_add(const PairConsts& k, float mu, const
    viscous_pair(s, viscous_pair_mu(LAW, mu, Mi, mj), d, k.hscaled, k.kernel3, Ri, viscous_row_of(rj));
 }
 
-// the list walk of one lane (xsph_from_lists' loop: one 16-byte load per eight entries)
+// the list walk of one lane (pair_walk_lists' loop, pair_walk.h: one 16-byte load per eight entries)
 template <bool UNIT_SCALE, bool WIDE, bool LAW>
 __device__ __forceinline__ void viscous_from_lists(int cnt, const ListReader& lr, const TileDesc& d, const PairConsts& k,
                                                    float mu, const float4& pi, const ViscousRow& Ri, float Mi,
@@ -89,7 +89,7 @@ __device__ __forceinline__ void viscous_from_lists(int cnt, const ListReader& lr
    }
 }
 
-// the row walk of one lane (k_particle_density's: pressure_kernels.h)
+// the row walk of one lane (pair_walk_rows', pair_walk.h)
 template <bool UNIT_SCALE, bool LAW>
 __device__ __forceinline__ void viscous_from_rows(int p, const CellGrid& g, const uint32_t* __restrict__ cell_start,
                                                   const PairConsts& k, float mu, const float4& pi, const ViscousRow& Ri,

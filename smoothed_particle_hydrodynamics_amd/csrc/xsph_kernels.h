@@ -4,24 +4,17 @@
 // launch_integrate picks, runs behind them from the velocities they leave.
 //
 // k_xsph_stage is k_scalars_stage's shape (scalar_kernels.h): one lane per live sorted slot writes R[p] = {v, 1/rho}.
-// k_xsph_apply is k_cohesion_apply's skeleton (cohesion_kernels.h) - a fifth consumer of the neighbour lists the
-// density pass left for the acceleration pass.  A lane takes its list a block of eight entries per trip, the next
-// block requested before this one's gathers; a workgroup or a lane without a list walks the nine cell rows as
-// k_particle_density does, by the scalar pass's route decisions (launch_policy.h: scalar_workgroup_route,
-// scalar_lane_route).  Same pairs, same order, same arithmetic: same bits.  It gathers posm[q] and R[q] - 32 bytes
-// per neighbour, no division per pair - and never another particle's velp; it writes its own velp[p] only.  So
-// nothing races, and every sum reads S_k's velocities (Jacobi, not Gauss-Seidel).  The only LDS is its copy of its
-// TileDesc, and every local array is indexed by unrolled constants (none lives in scratch memory).
+// k_xsph_apply is one of the consumers of the neighbour lists the density pass left for the acceleration pass: the
+// walk, on either route, is pair_walk.h's.  It gathers posm[q] and R[q] - 32 bytes per neighbour, no division per
+// pair - and never another particle's velp; it writes its own velp[p] only.  So nothing races, and every sum reads
+// S_k's velocities (Jacobi, not Gauss-Seidel).
 //
 // Nothing between the density pass and these kernels writes what they read: posm[cur], ncount, nlist,
 // nlist_overflow and tile_desc are written by the cell build and the density kernels only, rho by the density
 // kernels only, and velp[cur] of an unfused step by nothing in front of buoyancy (xsph, "The premise").
 #pragma once
 
-#include "cell_build.h"
-#include "full_tiled.h"
-#include "neighbor_lists.h"
-#include "pair_math.h"
+#include "pair_walk.h"
 #include "xsph_policy.h"
 
 static_assert(sizeof(XsphRow) == sizeof(float4), "a staged row is one float4");
@@ -41,67 +34,28 @@ k_xsph_stage(const float4* __restrict__ velp, const float* __restrict__ rho, con
 }
 
 // ---- the pass: one workgroup per 256 sorted particles ----------------------------------------------------------
-// one neighbour into the sum: the weight is the density pass's own pair term, formed as cohesion_add forms it
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void xsph_add(const PairConsts& k, const float4& pi, const XsphRow& Ri, const float4& pj,
-                                         const float4& rj, XsphSum& s)
-{
-   float dx, dy, dz;
-   float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
-   if (!UNIT_SCALE) d *= k.sim_scale;
-   const float w = density_term<UNIT_SCALE>(k, pj.w, d);
-   xsph_pair(s, w, Ri, xsph_row_of(rj));
-}
+// the pass's accumulator (pair_walk.h): the weight of a pair is the density pass's own pair term, formed as
+// cohesion's is
+struct XsphPairs {
+   const PairConsts& k;
+   const float4* __restrict__ R;
+   XsphRow Ri;
+   XsphSum s;
 
-// the list walk of one lane (cohesion_from_lists' loop: one 16-byte load per eight entries)
-template <bool UNIT_SCALE, bool WIDE>
-__device__ __forceinline__ void xsph_from_lists(int cnt, const ListReader& lr, const TileDesc& d, const PairConsts& k,
-                                                const float4& pi, const XsphRow& Ri, const float4* __restrict__ posm,
-                                                const float4* __restrict__ R, XsphSum& s)
-{
-   const int lastb = cnt > 0 ? (cnt - 1) >> 3 : 0;
-   uint4 blk = lr.block(0);
-   for (int j0 = 0; j0 < cnt; j0 += 8) {
-      uint32_t entry[8];
-      list_block_entries(blk, entry);
-      blk = lr.block(min((j0 >> 3) + 1, lastb));
-      float4 pj[8], rj[8];
-#pragma unroll
-      for (int u = 0; u < 8; u++) {
-         const uint32_t e = j0 + u < cnt ? entry[u] : entry[0];      // (entry 0 of a block in use is a neighbour)
-         const int q = ListEntry<WIDE>::tile(e) - ListEntry<WIDE>::shift(d, e);
-         pj[u] = posm[q];
-         rj[u] = R[q];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; u++)
-         if (j0 + u < cnt) xsph_add<UNIT_SCALE>(k, pi, Ri, pj[u], rj[u], s);
-   }
-}
+   using Payload = float4;   // R: the staged row of sorted particle q (k_xsph_stage)
+   template <class Index>
+   __device__ __forceinline__ Payload gather(Index q) const { return R[q]; }
 
-// the row walk of one lane (k_particle_density's: pressure_kernels.h)
-template <bool UNIT_SCALE>
-__device__ __forceinline__ void xsph_from_rows(int p, const CellGrid& g, const uint32_t* __restrict__ cell_start,
-                                               const PairConsts& k, const float4& pi, const XsphRow& Ri,
-                                               const float4* __restrict__ posm, const float4* __restrict__ R, XsphSum& s)
-{
-   int cx, cy, cz;
-   cell_of(g, pi.x, pi.y, pi.z, cx, cy, cz);
-   RowRanges r;
-   row_ranges(g, cell_start, cx, cy, cz, r);
-#pragma unroll 1
-   for (int row = 0; row < 9; row++) {
-      uint32_t b, e;
-      row_range(r, row, b, e);
-      for (uint32_t q = b; q < e; q++) {
-         if (q == (uint32_t)p) continue;
-         const float4 pj = posm[q];
-         float dx, dy, dz;
-         const float d2 = dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz);
-         if (d2 < k.h2) xsph_add<UNIT_SCALE>(k, pi, Ri, pj, R[q], s);
-      }
+   template <bool UNIT_SCALE>
+   __device__ __forceinline__ void add(const float4& pi, const float4& pj, const float4& rj)
+   {
+      float dx, dy, dz;
+      float d = sqrt_rn(dist2(pi.x, pi.y, pi.z, pj.x, pj.y, pj.z, dx, dy, dz));
+      if (!UNIT_SCALE) d *= k.sim_scale;
+      const float w = density_term<UNIT_SCALE>(k, pj.w, d);
+      xsph_pair(s, w, Ri, xsph_row_of(rj));
    }
-}
+};
 
 // One workgroup per 256 sorted particles of the live range.  tiled: the context's density pass wrote lists and
 // flags (else nlist, nlist_overflow, desc are not read).  eps and the constants arrive by value: a later setter
@@ -114,33 +68,15 @@ k_xsph_apply(const float4* __restrict__ posm, const float4* __restrict__ R, cons
              const uint32_t* __restrict__ nlist_overflow, int list_cap, int tiled, float4* __restrict__ velp)
 {
    __shared__ TileDesc sd;
-   const int begin = meta[META_SUM_BEGIN], end = meta[META_SUM_END];
-   const int tid = threadIdx.x;
-   const int wg = xcd_workgroup(blockIdx.x, gridDim.x);
-   const int p0 = begin + wg * TILE_THREADS;
-   if (p0 >= end) return;   // (the whole workgroup)
-   const int p = p0 + tid;
-   const bool live = p < end;
-   // (workgroup-uniform: the barrier inside tile_desc_load is reached by every lane or by none)
-   const uint32_t flag = tiled ? nlist_overflow[wg] : LISTS_NONE;
-   const int wg_route = scalar_workgroup_route(tiled != 0, false, flag);
-   if (wg_route == SCALAR_ROUTE_LISTS) tile_desc_load(desc, wg, sd);
-   if (!live) return;
+   const PairLane w = pair_workgroup(meta, tiled, 0, nlist_overflow, desc, sd);
+   if (!w.live) return;
+   const int p = w.p;
 
    const float4 pi = posm[p];
-   const XsphRow Ri = xsph_row_of(R[p]);
-   XsphSum s = {0.0f, 0.0f, 0.0f};
-   int lane_route = SCALAR_ROUTE_ROWS;
-   if (wg_route == SCALAR_ROUTE_LISTS) {
-      const int cnt = ncount[p];
-      const ListReader lr(nlist, wg, list_cap, tid);
-      const uint32_t first_word = (flag == LISTS_SOME && cnt > 0) ? (lr.no_list() ? NLIST_NO_LIST : 0u) : 0u;
-      lane_route = scalar_lane_route(wg_route, flag, cnt, first_word);
-      if (lane_route == SCALAR_ROUTE_LISTS) xsph_from_lists<UNIT_SCALE, WIDE>(cnt, lr, sd, k, pi, Ri, posm, R, s);
-   }
-   if (lane_route == SCALAR_ROUTE_ROWS) xsph_from_rows<UNIT_SCALE>(p, g, cell_start, k, pi, Ri, posm, R, s);
+   XsphPairs pairs = {k, R, xsph_row_of(R[p]), {0.0f, 0.0f, 0.0f}};
+   pair_walk<UNIT_SCALE, WIDE>(w, sd, ncount, nlist, list_cap, g, cell_start, k.h2, pi, posm, pairs);
 
-   const XsphSum dv = xsph_change(eps, s);
+   const XsphSum dv = xsph_change(eps, pairs.s);
    if (!xsph_acts(dv)) return;
    float4 v = velp[p];   // (.w, the id, is stored back as it was read)
    xsph_apply(dv, v.x, v.y, v.z);

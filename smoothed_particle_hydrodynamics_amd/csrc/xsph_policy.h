@@ -14,7 +14,7 @@
 //   weight    g_ij = w_j * (0.5f * (R_i.w + R_j.w)), w_j the density pass's pair term m_j * (kernel1 *
 //             (hscaled2 - d*d)^3) of d = sqrt(d2), correctly rounded, times sim_scale unless the context runs at unit
 //             scale.  w_j is density_term of pair_math.h, which only the device compiles: the kernel forms it as
-//             cohesion_add does and hands it to xsph_pair, and its rule for d > hscaled comes with it - such a member
+//             cohesion's add does and hands it to xsph_pair, and its rule for d > hscaled comes with it - such a member
 //             has w_j = +0.0f.  This is Monaghan's 2 m_j W / (rho_i + rho_j) with the arithmetic mean of the inverse
 //             densities in place of the inverse of their mean: symmetric in i and j for equal masses, and no
 //             division per pair.

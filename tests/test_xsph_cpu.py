@@ -393,6 +393,10 @@ def test_the_kernels_signatures():
     # the pair kernel never reads another particle's velp
     body = mine[mine.index("k_xsph_apply("):]
     assert body.count("velp[") == 2 and "velp[p]" in body and "velp[q]" not in mine
+    # (what it gathers for a neighbour is its accumulator's to say: the staged rows, and pair_walk.h adds posm[q])
+    pairs = mine[mine.index("struct XsphPairs {"):mine.index("k_xsph_apply(const float4* __restrict__ posm")]
+    assert "velp" not in pairs and "{ return R[q]; }" in pairs
+    assert "velp" not in open(os.path.join(CSRC, "pair_walk.h")).read().split("#pragma once")[1]
     tiled = open(os.path.join(CSRC, "full_tiled.h")).read()
     sig = tiled[tiled.index("k_full_accel_lists(const float4* __restrict__ posm"):]
     sig = sig[:sig.index(")\n{")]
