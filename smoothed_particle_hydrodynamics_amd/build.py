@@ -21,7 +21,7 @@ HEADERS = ["sph_device.h", "cell_build.h", "pair_math.h", "full_kernels.h", "ful
            "gauge_kernels.h", "gauge_policy.h", "pressure_kernels.h",
            "scalar_kernels.h", "scalar_policy.h", "buoyancy_kernels.h", "buoyancy_policy.h",
            "cohesion_kernels.h", "cohesion_policy.h", "xsph_kernels.h", "xsph_policy.h",
-           "viscous_kernels.h", "viscous_policy.h",
+           "viscous_kernels.h", "viscous_policy.h", "viscous_implicit_kernels.h", "viscous_implicit_policy.h",
            "monitor_kernels.h", "monitor_policy.h",
            "velgrad_kernels.h", "velgrad_policy.h", "pair_walk.h",
            os.path.join("..", "..", "include", "sph_hip.h")]

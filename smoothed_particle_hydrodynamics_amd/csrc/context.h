@@ -30,6 +30,7 @@
 #include "buoyancy_kernels.h"
 #include "cohesion_kernels.h"
 #include "xsph_kernels.h"
+#include "viscous_implicit_kernels.h"
 #include "viscous_kernels.h"
 #include "monitor_kernels.h"
 #include "velgrad_kernels.h"
@@ -451,6 +452,12 @@ struct sph_hip_context {
    sph_hip_viscosity_law viscous_law = {};
    DevBuf<float4> viscous_R;
    DevBuf<float> viscous_M;
+
+   // implicit viscous stress (sph_hip_set_viscous_implicit): the Jacobi sweeps the next enqueued steps take in the
+   // place of the explicit term while mu != 0 (0: the explicit term), dropped by an upload; the second row set of the
+   // ping-pong (viscous_R2) holds the capacity and is allocated by the first count of 2 or more
+   int viscous_sweeps = 0;
+   DevBuf<float4> viscous_R2;
 
    // step monitor (sph_hip_record_monitor): mon_rows rows; mon_step = steps enqueued since the call, mon_filled =
    // rows those steps have filled, mon_row_now = the row the step being enqueued fills (-1: none).  The partial

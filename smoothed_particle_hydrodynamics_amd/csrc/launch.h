@@ -964,6 +964,41 @@ int launch_cohesion(sph_hip_context* ctx)
    return SPH_HIP_OK;
 }
 
+// ---- implicit viscous stress (viscous_implicit_kernels.h; contract: viscous_implicit_policy.h) -------------------
+// What launch_viscous hands over to while the context's viscous setting carries a sweep count: the stage of S_k's
+// velocities as launch_viscous launches it, then K Jacobi sweeps over the lists and counts the density pass left.
+// The sweeps ping-pong between the two row sets (viscous_implicit_source, viscous_implicit_target); the last one
+// writes the velocities of the sorted state, and acc is never touched.  K + 1 launches; mu, the law and the
+// constants travel by value: a later setter does not reach the steps already queued.  Nothing synchronises.
+int launch_viscous_implicit(sph_hip_context* ctx)
+{
+   const bool law = ctx->have_viscous_law != 0;
+   const int K = ctx->viscous_sweeps;
+   float4* const rows[2] = {ctx->viscous_R.get(), ctx->viscous_R2.get()};
+   float4* const vel = ctx->velp[ctx->cur];
+   bind_flags([&](auto L) {
+      hipLaunchKernelGGL((k_viscous_stage<L.value>), dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream, vel,
+                         ctx->posm[ctx->cur], ctx->rho, ctx->meta, L.value ? ctx->scalar_Ts.get() : (const float4*)nullptr,
+                         ctx->viscous_mu, ctx->viscous_law, rows[0], L.value ? ctx->viscous_M.get() : (float*)nullptr);
+   }, law);
+   const PairConsts k = pair_consts(ctx->prm, ctx->fast != 0);
+   static_assert(TILE_THREADS == 256, "the sweep kernel maps one workgroup to 256 sorted particles");
+   for (int s = 0; s < K; s++) {
+      const int target = viscous_implicit_target(s, K);
+      const float4* const in = rows[viscous_implicit_source(s)];
+      bind_flags([&](auto U, auto W, auto L, auto LAST) {
+         hipLaunchKernelGGL((k_viscous_sweep<U.value, W.value, L.value, LAST.value>), dim3(div_up(ctx->n, TILE_THREADS)),
+                            dim3(TILE_THREADS), 0, ctx->stream, ctx->posm[ctx->cur],
+                            LAST.value ? (const float4*)nullptr : vel, in,
+                            L.value ? ctx->viscous_M.get() : (const float*)nullptr, ctx->ncount, ctx->cell_start, ctx->meta,
+                            ctx->grid, k, ctx->viscous_mu, ctx->tile_desc, ctx->nlist, ctx->nlist_overflow, ctx->list_cap,
+                            ctx->use_tiled ? 1 : 0, LAST.value ? vel : rows[target]);
+      }, unit_scale(ctx->prm), ctx->caps.wide != 0, law, target < 0);
+   }
+   SPH_TRY(hipGetLastError());
+   return SPH_HIP_OK;
+}
+
 // ---- viscous stress (viscous_kernels.h; contract: viscous_policy.h; decision: launch_policy.h) --------------------
 // Behind the step's acceleration pass and cohesion, in front of XSPH, buoyancy and the integrate: the stage of S_k's
 // velocities with the densities the step's density pass left (and, with a law, of the channels launch_scalars staged
@@ -972,6 +1007,7 @@ int launch_cohesion(sph_hip_context* ctx)
 // queued.  Nothing synchronises.
 int launch_viscous(sph_hip_context* ctx)
 {
+   if (ctx->viscous_sweeps > 0) return launch_viscous_implicit(ctx);   // (the implicit mode: its own stage and sweeps)
    const bool law = ctx->have_viscous_law != 0;
    bind_flags([&](auto L) {
       hipLaunchKernelGGL((k_viscous_stage<L.value>), dim3(div_up(ctx->n, 256)), dim3(256), 0, ctx->stream,

@@ -560,6 +560,7 @@ static int upload_impl(sph_hip_context* ctx, int n, const float* pos, const floa
    ctx->have_xsph = 0;       // and so is the velocity smoothing
    ctx->have_viscous = 0;    // and the viscous stress, with its law
    ctx->have_viscous_law = 0;
+   ctx->viscous_sweeps = 0;   // and its solver mode
    ctx->upload_mass_known = (n > 0 && mass) ? 1 : 0;
    ctx->upload_mass = (n > 0 && mass) ? mass[0] : 0.0f;
    ports_mass_rule(ctx, n == 0);
@@ -1331,6 +1332,7 @@ int sph_hip_set_ports(sph_hip_context* ctx, const sph_hip_emitter* emitters, int
    if (const char* why = cohesion_ports_check(ctx->have_cohesion != 0, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = xsph_ports_check(ctx->have_xsph != 0, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = viscous_ports_check(ctx->have_viscous != 0, ne, ns)) return refuse(ctx, who, why);
+   if (const char* why = viscous_implicit_ports_check(ctx->viscous_sweeps, ne, ns)) return refuse(ctx, who, why);
    if (const char* why = monitor_ports_check(ctx->mon_rows, ne, ns)) return refuse(ctx, who, why);
    // a pending prehash counted for a build whose entries the ports may change first
    if ((rc = drop_prehash(ctx))) return rc;
@@ -2294,6 +2296,46 @@ int sph_hip_set_viscous_stress(sph_hip_context* ctx, float mu, const sph_hip_vis
    ctx->viscous_mu = ctx->have_viscous ? mu : 0.0f;
    ctx->have_viscous_law = with_law ? 1 : 0;
    ctx->viscous_law = viscous_law_clean(with_law ? law : nullptr);
+   return SPH_HIP_OK;
+}
+
+// The solver mode of the setting above (viscous_implicit_kernels.h; contract and checks: viscous_implicit_policy.h).
+// It stands in front of the getter because it allocates the second row set of the sweeps' ping-pong.
+int sph_hip_set_viscous_implicit(sph_hip_context* ctx, int sweeps)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   const char* who = "sph_hip_set_viscous_implicit";
+   if (const char* why = viscous_implicit_sweeps_check(sweeps)) return refuse(ctx, who, why);
+   if (!viscous_implicit_is_off(sweeps)) {   // (switching to the explicit term is never refused)
+      const bool whole = ctx->plane_lo == 0 && ctx->plane_hi == ctx->grid.nz_global && !ctx->had_exchange;
+      if (const char* why = viscous_implicit_mode_check(ctx->mode == SPH_HIP_MODE_FULL)) return refuse(ctx, who, why);
+      if (const char* why = viscous_implicit_slab_check(whole)) return refuse(ctx, who, why);
+      if (const char* why = viscous_implicit_ports_set_check(ports_active(ctx->n_emit, ctx->n_sink)))
+         return refuse(ctx, who, why);
+      // the second row set: at the first count that needs it, so a context that never asks keeps its footprint
+      if (viscous_implicit_needs_second(sweeps) && !ctx->viscous_R2) {
+         DevBuf<float4> second;
+         if (dev_alloc(second, (size_t)ctx->capacity) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->err = "sph_hip_set_viscous_implicit: cannot allocate the second row set of " +
+                       std::to_string(ctx->capacity) + " particles";
+            return SPH_HIP_ERR_CAPACITY;
+         }
+         ctx->viscous_R2 = std::move(second);
+      }
+   }
+   // (a step takes the count by value: the steps already queued keep theirs)
+   ctx->viscous_sweeps = sweeps;
+   return SPH_HIP_OK;
+}
+
+int sph_hip_get_viscous_implicit(sph_hip_context* ctx, int* sweeps)
+{
+   int rc = check_ctx(ctx);
+   if (rc) return rc;
+   if (!sweeps) return refuse(ctx, "sph_hip_get_viscous_implicit", "null output");
+   *sweeps = ctx->viscous_sweeps;
    return SPH_HIP_OK;
 }
 

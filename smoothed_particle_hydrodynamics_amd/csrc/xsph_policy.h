@@ -6,7 +6,10 @@
 // tests/xsph_emulation.py).  Pure C++17 without HIP; the translation units that use it are compiled with
 // -ffp-contract=off.
 //
-// The contract.  All arithmetic is fp32, unfused, in the order written.  For particle i of the step's state S_k:
+// The contract.  All arithmetic is fp32, unfused, in the order written.  For particle i of the step's state S_k - with
+// one exception: in a context that takes its viscous stress implicitly (viscous_implicit_policy.h) the velocities the
+// stage reads are the ones the last viscous sweep of this step left, not S_k's; positions, masses and densities are
+// S_k's in either case:
 //   stage     every live sorted slot p: R[p] = {v.x, v.y, v.z, 1.0f / rho[p]}, v = velp[cur][p], rho what this
 //             step's density pass left; one correctly rounded division (xsph_stage)
 //   members   cohesion's exactly: j with d2 = (dx*dx + dy*dy) + dz*dz < h2, (dx, dy, dz) = r_i - r_j, i itself

@@ -193,6 +193,8 @@ PROTOTYPES = {
     "sph_hip_get_xsph": (C.c_int, [_ctx, _P(C.c_float)]),
     "sph_hip_set_viscous_stress": (C.c_int, [_ctx, C.c_float, _P(SphViscosityLaw)]),
     "sph_hip_get_viscous_stress": (C.c_int, [_ctx, _P(C.c_float), _P(SphViscosityLaw), _P(C.c_int)]),
+    "sph_hip_set_viscous_implicit": (C.c_int, [_ctx, C.c_int]),
+    "sph_hip_get_viscous_implicit": (C.c_int, [_ctx, _P(C.c_int)]),
     "sph_hip_record_monitor": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int]),
     "sph_hip_get_monitor_record": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "sph_hip_get_velocity_gradients": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

@@ -662,6 +662,23 @@ def dam_break_viscous(n, mu, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.
     return p, pos, vel, mass, float(mu)
 
 
+def viscous_number(p, mu, neighbors=32.0, mass=1.0):
+    """viscous_stable_mu's inverse: N = dt * (mu / rho) * kernel3 * pi * h^4 / 3 of the dynamic viscosity `mu` deep
+    inside a fluid of ~`neighbors` particles of `mass` inside radius h.  Up to 1 the explicit term damps; beyond it
+    take the term implicitly (SPH.setViscousSolver), whose error contracts like N / (1 + N) per sweep."""
+    return float(mu) / viscous_stable_mu(p, 1.0, neighbors, mass)
+
+
+def dam_break_honey(n, fraction=5.0, sweeps=8, surge=0.7, box=(1.0, 1.0, 1.0), fill=(0.1, 0.75, 1.0), neighbors=32.0,
+                    seed=42, gravity=-9.81):
+    """dam_break_viscous's dam as a fluid too thick for the explicit term: mu is `fraction` times the bulk's explicit
+    limit (viscous_stable_mu(p, fraction): viscous_number gives `fraction` back), taken by `sweeps` Jacobi sweeps.
+    Returns (params, pos, vel, mass, mu, sweeps): setParticles, setViscousStress(mu), then
+    setViscousSolver(sweeps)."""
+    p, pos, vel, mass, _ = dam_break_viscous(n, 0.0, surge, box, fill, neighbors, seed, gravity)
+    return p, pos, vel, mass, viscous_stable_mu(p, float(fraction), neighbors), int(sweeps)
+
+
 def shear_layer(n, speed, seed=42, neighbors=32.0, cells=None):
     """A resting block whose upper half moves: droplet's cubic random fill in the middle of the box (gravity and
     the central mass off, the walls on, unit masses) with the velocity (speed, 0, 0) for every particle above the

@@ -8,6 +8,7 @@ import math
 import numpy as np
 
 MAX_KEYS = 16         # SPH_HIP_MAX_VISCOSITY_KEYS
+MAX_SWEEPS = 64       # SPH_HIP_MAX_VISCOUS_SWEEPS (SPH.setViscousSolver)
 
 
 class SphViscosityLaw(C.Structure):
