@@ -231,10 +231,23 @@ __device__ __forceinline__ void tile_desc_load(const TileDesc* __restrict__ desc
 // most of their tile (each sorted particle is staged by ~6 workgroups): give every residue class
 // of blockIdx mod 8 a contiguous eighth of the workgroups, so the shared rows hit one L2.
 // Bijective for any grid size.  Only a placement hint: results do not depend on it.
+// (launch_policy.h: xcd_workgroup_ascending / _descending - the same functions on the host, for the tests)
 __device__ __forceinline__ int xcd_workgroup(int block, int nblocks)
 {
-   const int q = nblocks / 8, r = nblocks % 8, x = block % 8;
-   return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + block / 8;
+   return xcd_workgroup_ascending(block, nblocks);
+}
+// The direction in which the two big passes walk each XCD's share.  The density pass ascends; the
+// single-context acceleration launch descends, so that it begins with what the density pass wrote last
+// (profiles/accel_handover.txt).  Exactly one of the two is reversed: both reversed is both ascending.
+#ifndef DENSITY_DESCENDING
+#define DENSITY_DESCENDING 0
+#endif
+#ifndef ACCEL_DESCENDING
+#define ACCEL_DESCENDING 1
+#endif
+__device__ __forceinline__ int xcd_workgroup_handover(int block, int nblocks, bool descending)
+{
+   return descending ? xcd_workgroup_descending(block, nblocks) : xcd_workgroup_ascending(block, nblocks);
 }
 
 // The tile fill's view of the workgroup's descriptor: workgroup-uniform values read straight from
@@ -440,7 +453,7 @@ k_full_density_tiled(const float4* __restrict__ posm, const float4* __restrict__
    // workgroup per 256 particles of its CAPACITY, and dealing eighths of that grid left the XCDs
    // of the empty tail idle - 3 of 8 with the usual 1.5x head room)
    const int wgs = tile_stats[TSTAT_BLOCKS];
-   const int wg = (int)blockIdx.x < wgs ? xcd_workgroup(blockIdx.x, wgs) : (int)blockIdx.x;
+   const int wg = (int)blockIdx.x < wgs ? xcd_workgroup_handover(blockIdx.x, wgs, DENSITY_DESCENDING) : (int)blockIdx.x;
    const int p0 = begin + wg * TILE_THREADS;
    if (p0 >= end) return;
    const int p = p0 + tid;
@@ -921,7 +934,8 @@ __device__ __forceinline__ bool accel_part_has(int part, int p0, const int32_t* 
 __device__ __forceinline__ int accel_part_workgroup(int part, int block, int wgs, int begin,
                                                     const int32_t* __restrict__ meta)
 {
-   if (part == 0) return block < wgs ? xcd_workgroup(block, wgs) : -1;
+   // (the single-context launch: each XCD walks its share towards the density pass's start)
+   if (part == 0) return block < wgs ? xcd_workgroup_handover(block, wgs, ACCEL_DESCENDING) : -1;
    const int ob = meta[META_OWN_BEGIN], oe = meta[META_OWN_END];
    const int lo_end = min(meta[META_BND_LO_END], oe);
    const int hi_begin = min(max(meta[META_BND_HI_BEGIN], lo_end), oe);

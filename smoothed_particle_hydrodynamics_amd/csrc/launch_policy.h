@@ -45,6 +45,36 @@ struct TileCaps {
 #define SLAB_GROW_FILL_NUM 4
 #define SLAB_GROW_FILL_DEN 5
 
+// ---- placement of workgroups on the XCDs ---------------------------------------------------
+// Which of `nblocks` 256-particle workgroups hardware workgroup `block` computes.  The dispatcher deals
+// consecutive block indices round-robin over the 8 XCDs; every residue class of block mod 8 owns a
+// contiguous share of the workgroups (the first nblocks mod 8 classes one more than the others), so that
+// neighbouring workgroups, which share most of their tile, meet in one L2.  ascending: a class walks its
+// share from the bottom up, as the density pass does; descending: from the top down - the SAME share, so
+// the acceleration pass starts each XCD where the density pass has just ended it and reads what that
+// wrote (lists, rho, velB, auxc, counts) while it is still in that XCD's L2 and the Infinity Cache.
+// Bijective onto [0, nblocks) for any nblocks >= 1 either way.  A placement only: no result depends on it.
+#define XCD_COUNT 8
+constexpr inline int xcd_share_begin(int xcd, int nblocks)
+{
+   return xcd < nblocks % XCD_COUNT ? xcd * (nblocks / XCD_COUNT + 1)
+                                    : (nblocks % XCD_COUNT) * (nblocks / XCD_COUNT + 1) +
+                                         (xcd - nblocks % XCD_COUNT) * (nblocks / XCD_COUNT);
+}
+constexpr inline int xcd_share_size(int xcd, int nblocks)
+{
+   return nblocks / XCD_COUNT + (xcd < nblocks % XCD_COUNT ? 1 : 0);
+}
+constexpr inline int xcd_workgroup_ascending(int block, int nblocks)
+{
+   return xcd_share_begin(block % XCD_COUNT, nblocks) + block / XCD_COUNT;
+}
+constexpr inline int xcd_workgroup_descending(int block, int nblocks)
+{
+   return xcd_share_begin(block % XCD_COUNT, nblocks) + xcd_share_size(block % XCD_COUNT, nblocks) - 1 -
+          block / XCD_COUNT;
+}
+
 // ---- LDS tile capacity ---------------------------------------------------------------------
 // For every workgroups-per-CU count B a tiled kernel can reach, the largest tile (multiple of
 // 32 entries) that still lets B workgroups share a CU.  Registers and waves: the runtime's
